@@ -8,7 +8,13 @@ A "step" is one pass of the hot path over one batch of synthetic input already r
                                                               network produces degenerate detection counts)
 Image size is 544 (the reference cannot run at 550: SURVEY.md §0.1).  Weights: seeded random init.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg res101_coco] [--batch 1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg res101_coco] [--batch 1] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (`metric`, `value`, `unit`, `ms_per_step`, ...): nothing
+else.  `--full` adds everything else the record carries (spread repeats, per-request latency, roofline, the bs=8 / split-bf16 /
+other-size / post-processing / metric / augmentation legs, the eval and training loops, the CPU baseline: `roofline`,
+`cpu_baseline`, `extra`).  `--dump-outputs DIR` writes what the last timed step computed (`dump_outputs`) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 `--inflight S` (default 4 at bs=1): S independent bs=1 requests are in flight on S HIP streams (S engines with their own activations,
 split-K scratch, arrival counters and hipGraphs; GPU_MAX_HW_QUEUES=8 so that every stream has a hardware queue of its own).  A
@@ -58,8 +64,13 @@ def parse():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra', action='store_true', help='skip the bs=8 side measurements')
     ap.add_argument('--lean', action='store_true', help='profiler runs (tools/profile_round.sh): no spread repeats, no latency leg')
+    ap.add_argument('--full', action='store_true',
+                    help='measure and report everything beside the headline (roofline, cpu_baseline, extra); off: the headline only')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)')
     ap.add_argument('--mode', default='infer', choices=['infer', 'train'],
-                    help="what `value` reports; the other mode's numbers still appear under extra")
+                    help="what `value` reports (train: the DDP training leg, --train-steps steps); with --full the other mode's "
+                         "numbers still appear under extra")
     ap.add_argument('--train-batch', type=int, default=8, help='images per GPU per training step')
     ap.add_argument('--train-steps', type=int, default=6)
     ap.add_argument('--no-train', action='store_true', help='skip the DDP training measurement')
@@ -98,6 +109,7 @@ class Workload:
         self.anchors = torch.tensor(net.anchors, dtype=torch.float32).reshape(-1, 4).to(device)
         self.inflight = inflight
         self.pipe = None
+        self.last = self.result = None
         if self.inflight > 1:
             self.pipe = RequestPipeline(net, cfg, img_size, img_size, device, depth=self.inflight, out_hw=(480, 640), with_post=with_post,
                                         batch=batch, return_outputs=False, timed=timed)
@@ -107,10 +119,14 @@ class Workload:
             self.engine = net._engine(self.img)
 
     def flush(self):
+        """Finish what is in flight; returns the detections of the last request (kept by `step(keep=True)` without a pipeline)."""
         if self.pipe is not None:
-            self.pipe.drain()
+            done = self.pipe.drain()
+            return done[-1] if done else None
+        last, self.last = self.last, None
+        return last
 
-    def step(self):
+    def step(self, keep=False):
         from yolact_minimal_amd.utils.output_utils import nms, after_nms, nms_batch, after_nms_batch
         if self.pipe is not None:
             self.pipe.submit(self.img, self.head if self.batch == 1 else self.head_b)
@@ -119,26 +135,72 @@ class Workload:
         if self.with_post:
             if self.batch > 1:
                 hb = self.head_b if self.head_b is not None else self.engine.outputs()
-                after_nms_batch(nms_batch(*hb, self.anchors, self.cfg), 480, 640, self.cfg)
+                r = after_nms_batch(nms_batch(*hb, self.anchors, self.cfg), 480, 640, self.cfg)
             else:
                 cls, box, coef, proto = self.head if self.head is not None else self.engine.outputs()
                 r = nms(cls, box, coef, proto, self.anchors, self.cfg)
-                after_nms(r[0], r[1], r[2], r[3], r[4], 480, 640, self.cfg)
+                r = after_nms(r[0], r[1], r[2], r[3], r[4], 480, 640, self.cfg)
+            if keep:
+                self.last = r
+
+    def step_outputs(self):
+        """What the last request computed, as its caller receives it: the network's four outputs (the slot's own buffers, read
+        after `flush`) and the detections of `self.result` (set by `timed(..., keep_last=True)`; images concatenated)."""
+        eng = self.engine if self.pipe is None else self.pipe.engines[(self.pipe.submitted - 1) % self.pipe.depth]
+        out = dict(zip(('class_pred', 'box_pred', 'coef_pred', 'proto_out'), eng.outputs()))
+        res = self.result
+        if res is not None:
+            per_image = [res] if isinstance(res, tuple) else res
+            out['detections_per_image'] = torch.tensor([0 if r[0] is None else r[0].shape[0] for r in per_image])
+            for i, name in enumerate(('ids', 'scores', 'boxes_px', 'masks')):
+                parts = [r[i] for r in per_image if r[0] is not None]
+                if parts:
+                    out[name] = torch.cat(parts)
+        return out
 
 
-def timed(workload, steps, warmup, barrier):
+def timed(workload, steps, warmup, barrier, keep_last=False):
+    """Seconds of `steps` steps after `warmup` untimed ones.  `keep_last`: `workload.result` = the detections of the last step."""
     for _ in range(warmup):
         workload.step()
     workload.flush()
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        workload.step()
-    workload.flush()                 # (requests in flight: the host reads of the last ones)
+    for i in range(steps):
+        workload.step(keep=keep_last and i == steps - 1)
+    last = workload.flush()          # (requests in flight: the host reads of the last ones)
     torch.cuda.synchronize()
     barrier()
-    return time.perf_counter() - t0
+    t = time.perf_counter() - t0
+    if keep_last:
+        workload.result = last
+    return t
+
+
+def dump_outputs(out_dir, arrays, max_elems=1 << 21, limit_bytes=64 << 20):
+    """Write every tensor of `arrays` as `out_dir/<name>.npy`: floating tensors as float32 (float64 stays float64), integer ones as
+    float64.  A tensor of more than `max_elems` elements is written as `<name>_sample.npy`, the values at a fixed seeded set of
+    `max_elems` flat indices, and `<name>_rowsum.npy`, its float64 sum over everything but the first dimension (e.g. the area of
+    every mask).  Returns the names written."""
+    import numpy as np
+    files = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dtype = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+        if t.numel() > max_elems:
+            idx = torch.randint(t.numel(), (max_elems,), generator=torch.Generator().manual_seed(0)).sort()[0].to(t.device)
+            files[f'{name}_sample'] = t.reshape(-1)[idx].to(dtype)
+            files[f'{name}_rowsum'] = t.reshape(t.shape[0], -1).sum(dim=1, dtype=torch.float64)
+        else:
+            files[name] = t.to(dtype)
+    total = sum(v.numel() * v.element_size() for v in files.values())
+    if total > limit_bytes:
+        raise ValueError(f'dump_outputs: {total} bytes > {limit_bytes}')
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in files.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v.cpu().numpy())
+    return sorted(files)
 
 
 def conv_roofline(engine, img, iters=5):
@@ -596,9 +658,10 @@ def train_to_map_bench():
                                    source='tests/golden/overfit_reference_128.json (the real reference, imported, CPU)'))
 
 
-def train_bench(cfg_name, img_size, batch, steps, warmup, world, local_rank, device, barrier):
+def train_bench(cfg_name, img_size, batch, steps, warmup, world, local_rank, device, barrier, outputs=None):
     """DDP training: one step = forward + loss + backward (+ RCCL gradient all-reduce overlapped by DDP hooks) +
-    SGD step on `batch` synthetic images per GPU (targets: 4 boxes + rectangular masks per image)."""
+    SGD step on `batch` synthetic images per GPU (targets: 4 boxes + rectangular masks per image).
+    `outputs` (a dict): receives `losses`, what the last timed step returned."""
     from yolact_minimal_amd.utils.synthetic import synth_targets
     from yolact_minimal_amd.config import build_cfg
     from yolact_minimal_amd.modules.yolact import Yolact
@@ -625,6 +688,8 @@ def train_bench(cfg_name, img_size, batch, steps, warmup, world, local_rank, dev
     barrier()
     elapsed = reduce_max(time.perf_counter() - t0, device)
     timing = tr.timing_summary()
+    if outputs is not None:
+        outputs['losses'] = torch.stack([l.detach() for l in losses])
     flops_img = 3.0 * {'res101': 157.2e9, 'res50_': 113.4e9, 'swin_t': 119.2e9}.get(cfg_name[:6], 157.2e9)   # step ~ 3x forward
     opt = 'AdamW' if cfg_name.startswith('swin') else 'SGD'
     img_s = batch * world * steps / elapsed
@@ -731,6 +796,29 @@ def spawn_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
+def headline(args, world, inflight, elapsed, train=None):
+    """The fields of the result line that say what `value` is (a plain run prints these alone): inference over the `elapsed`
+    seconds of the timed steps (slowest rank), or the training leg `train` (`--mode train`)."""
+    return {
+        'metric': (f'img/s {args.cfg} 544x544 DDP training (bs={args.train_batch}/GPU)' if train else
+                   f'img/s {args.cfg} 544x544 inference (bs={args.batch}/GPU'
+                   + (f', {inflight} requests in flight)' if inflight > 1 else ')')),
+        'value': train['img_s'] if train else round(args.batch * args.steps * world / elapsed, 2), 'unit': 'img/s', 'n_gpus': world,
+        'steps': train['steps'] if train else args.steps, 'warmup': train['warmup'] if train else args.warmup,
+        'ms_per_step': train['ms_per_step'] if train else round(elapsed / args.steps * 1e3, 3),
+        'higher_is_better': True, 'scaling': 'weak',
+        'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'config': {'workload': f'{args.cfg} 544x544 (the reference\'s "550-class" size) bs={args.batch} inference: '
+                               f'forward + nms + after_nms(480x640) per image'
+                               + (f', {inflight} independent bs={args.batch} requests in flight on {inflight} HIP streams' if inflight > 1 else '')
+                               if not args.no_post else
+                               f'{args.cfg} 544x544 bs={args.batch} forward only',
+                   'global_batch': args.batch * world, 'parallelism': f'replicas x{world} (inference does not shard)',
+                   'weights': 'seeded random init', 'post_inputs': 'synthetic dense head outputs (17.8k candidates)',
+                   'requests_in_flight': inflight},
+    }
+
+
 def main():
     args = parse()
     if args.leg == 'eval_loop':
@@ -793,17 +881,38 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    net, cfg = build_net(args.cfg, args.img_size, device)
+    def write_record(out):
+        barrier()
+        if rank == 0:
+            os.write(record_fd, (json.dumps(out) + '\n').encode())
+        if dist is not None:
+            torch.cuda.synchronize()          # nothing in flight when the process group (and its watchdog thread) is torn down
+            dist.destroy_process_group()
+
+    dump = args.dump_outputs if rank == 0 else ''
     inflight = args.inflight if args.inflight > 0 else (4 if args.batch == 1 else 2)
+    if args.mode == 'train' and not args.full:
+        outputs = {}
+        train = train_bench(args.cfg, args.img_size, args.train_batch, args.train_steps, 2, world, local_rank, device, barrier,
+                            outputs=outputs)
+        if dump:
+            dump_outputs(dump, outputs)
+        return write_record(headline(args, world, inflight, None, train))
+
+    net, cfg = build_net(args.cfg, args.img_size, device)
     wl = Workload(net, cfg, args.batch, args.img_size, device, with_post=not args.no_post, inflight=inflight)
-    elapsed_local = timed(wl, args.steps, args.warmup, barrier)
+    dump_infer = dump if args.mode == 'infer' else ''
+    elapsed_local = timed(wl, args.steps, args.warmup, barrier, keep_last=bool(dump_infer))
     elapsed = elapsed_local
     if dist is not None:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    imgs = args.batch * args.steps * world
-    value = imgs / elapsed
+    if dump_infer:
+        dump_outputs(dump_infer, wl.step_outputs())
+        wl.result = None
+    if not args.full:
+        return write_record(headline(args, world, inflight, elapsed))
     region_flops = wl.engine.total_flops * args.steps          # conv flops this rank executed inside the region `value` times
     # spread: the driver's sample is K steps (20 steps = 33 ms at bs=1) -> the same region five more times, and five regions of
     # >= 200 steps (this rank's own clock; every rank takes part so that the barriers match)
@@ -820,10 +929,14 @@ def main():
     if not args.no_train:
         net._engines.clear()
         torch.cuda.empty_cache()
+        outputs = {}
         try:
-            train = train_bench(args.cfg, args.img_size, args.train_batch, args.train_steps, 2, world, local_rank, device, barrier)
+            train = train_bench(args.cfg, args.img_size, args.train_batch, args.train_steps, 2, world, local_rank, device, barrier,
+                                outputs=outputs)
         except Exception as e:        # the headline line must still be printed; the failure is reported under extra.train
             train = dict(error=f'{type(e).__name__}: {e}'[:400])
+        if dump and args.mode == 'train' and outputs:
+            dump_outputs(dump, outputs)
     train16 = None
     config4 = world == 8 or os.environ.get('YM_BENCH_CONFIG4', '0') == '1'          # (the env switch lets a 1-GPU test walk this path)
     if not args.no_train and config4 and args.train_batch != 16 and 'error' not in (train or {}):
@@ -1039,33 +1152,11 @@ def main():
         if train is not None and 'ddp' in train:          # N > 1: the north star's DDP curve is THIS block (`value` stays the replicas)
             extra['ddp'] = train['ddp']
         primary_train = args.mode == 'train' and train is not None and 'error' not in train
-        out = {
-            'metric': (f'img/s {args.cfg} 544x544 DDP training (bs={args.train_batch}/GPU)' if primary_train else
-                       f'img/s {args.cfg} 544x544 inference (bs={args.batch}/GPU'
-                       + (f', {inflight} requests in flight)' if inflight > 1 else ')')),
-            'value': train['img_s'] if primary_train else round(value, 2), 'unit': 'img/s', 'n_gpus': world,
-            # the reference's own loop (eval.py:36-69: one image at a time) on the same GPU, beside the overlapped figure
-            'value_single_request': single.get('img_s_with_post') if single else None,
-            'steps': train['steps'] if primary_train else args.steps, 'warmup': train['warmup'] if primary_train else args.warmup,
-            'ms_per_step': train['ms_per_step'] if primary_train else round(elapsed / args.steps * 1e3, 3),
-            'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': f'{args.cfg} 544x544 (the reference\'s "550-class" size) bs={args.batch} inference: '
-                                   f'forward + nms + after_nms(480x640) per image'
-                                   + (f', {inflight} independent bs={args.batch} requests in flight on {inflight} HIP streams' if inflight > 1 else '')
-                                   if not args.no_post else
-                                   f'{args.cfg} 544x544 bs={args.batch} forward only',
-                       'global_batch': args.batch * world, 'parallelism': f'replicas x{world} (inference does not shard)',
-                       'weights': 'seeded random init', 'post_inputs': 'synthetic dense head outputs (17.8k candidates)',
-                       'requests_in_flight': inflight},
-            'roofline': roofline, 'cpu_baseline': cpu, 'extra': extra,
-        }
-    barrier()
-    if rank == 0:
-        os.write(record_fd, (json.dumps(out) + '\n').encode())
-    if dist is not None:
-        torch.cuda.synchronize()          # nothing in flight when the process group (and its watchdog thread) is torn down
-        dist.destroy_process_group()
+        out = headline(args, world, inflight, elapsed, train if primary_train else None)
+        # the reference's own loop (eval.py:36-69: one image at a time) on the same GPU, beside the overlapped figure
+        out.update(value_single_request=single.get('img_s_with_post') if single else None, roofline=roofline, cpu_baseline=cpu,
+                   extra=extra)
+    write_record(out)
 
 
 if __name__ == '__main__':

@@ -4,8 +4,14 @@ import sys
 import pytest
 
 # RequestPipeline (bench.py's headline mode) overlaps requests on separate HIP streams; ROCm multiplexes streams onto
-# GPU_MAX_HW_QUEUES hardware queues (default 4) and reads the variable when the runtime starts -> set it before torch touches HIP
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
+# GPU_MAX_HW_QUEUES hardware queues (default 4) and reads the variable when the runtime starts -> set it before torch touches HIP.
+# An exported value below 8 (a machine may export the default 4) is raised: the pipeline tests need a queue per stream.
+try:
+    _queues = int(os.environ.get('GPU_MAX_HW_QUEUES', '0'))
+except ValueError:
+    _queues = 0
+if _queues < 8:
+    os.environ['GPU_MAX_HW_QUEUES'] = '8'
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:

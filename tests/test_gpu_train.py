@@ -761,7 +761,7 @@ def test_bench_under_torchrun_with_rccl_single_rank(tmp_path):
     from tests.conftest import REPO
     env = dict(os.environ, YM_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0', YM_BENCH_CONFIG4='1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
-           '--master-port', '29533', os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--cfg',
+           '--master-port', '29533', os.path.join(REPO, 'bench.py'), '--full', '--gpus', '1', '--steps', '2', '--warmup', '1', '--cfg',
            'res50_coco', '--no-extra', '--no-cpu-baseline', '--train-batch', '2', '--train-steps', '2']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     if out.returncode != 0:
@@ -1185,7 +1185,7 @@ def test_bench_eight_ranks_control_flow():
     from tests.conftest import REPO
     env = dict(os.environ, YM_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('WORLD_SIZE', None); env.pop('RANK', None); env.pop('LOCAL_RANK', None)
-    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '1', '--cfg', 'res50_coco',
+    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--gpus', '8', '--steps', '3', '--warmup', '1', '--cfg', 'res50_coco',
            '--img_size', '128', '--train-batch', '2', '--train-steps', '2', '--lean']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
@@ -1211,7 +1211,7 @@ def test_bench_two_ranks_control_flow():
     env = dict(os.environ, YM_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     # BARE command: bench.py itself re-execs under torch.distributed.run with one rank per GPU when WORLD_SIZE is unset
     env.pop('WORLD_SIZE', None); env.pop('RANK', None); env.pop('LOCAL_RANK', None)
-    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--cfg',
+    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--gpus', '2', '--steps', '3', '--warmup', '1', '--cfg',
            'res50_coco', '--img_size', '256', '--train-batch', '2', '--train-steps', '2']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])

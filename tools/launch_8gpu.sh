@@ -11,4 +11,4 @@ cd "$(dirname "$0")/.."
 export HSA_ENABLE_IPC_MODE_LEGACY=0            # the host driver only supports dmabuf IPC
 export NCCL_MIN_NCHANNELS="${NCCL_MIN_NCHANNELS:-16}"   # ring all-reduce over point-to-point xGMI is per-link bound: use the links
 exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "${MASTER_PORT:-29500}" \
-     bench.py --gpus "$N" --steps "${STEPS:-50}" --warmup "${WARMUP:-10}" "$@"
+     bench.py --full --gpus "$N" --steps "${STEPS:-50}" --warmup "${WARMUP:-10}" "$@"
