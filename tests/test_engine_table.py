@@ -20,43 +20,53 @@ def test_throughput_mode_reads_tp_entries_first(monkeypatch):
     assert E._entry('unknown') is None
 
 
-def test_grid_wgs_field_is_validated():
-    from yolact_minimal_amd import engine as E
-    assert E._grid_wgs([64, 64, 1, 0, 43, 0, 0, 768]) == 768 and E._grid_wgs([32, 32, 1, 1, 22, 0, 0, 1]) == 1
-    assert E._grid_wgs([64, 64, 1, 0, 2, 0, 0]) == 0
+def test_conv_plan_from_row_validates_grid_wgs():
+    from yolact_minimal_amd.conv_plan import ConvPlan
+
+    def grid(row):
+        return ConvPlan.from_row(row).grid_wgs
+
+    assert grid([64, 64, 1, 0, 43, 0, 0, 768]) == 768 and grid([32, 32, 1, 1, 22, 0, 0, 1]) == 1
+    assert grid([64, 64, 1, 0, 2, 0, 0]) == 0
     with pytest.raises(ValueError):
-        E._grid_wgs([64, 64, 1, 0, 43, 0, 0, 12.5])           # an old autotune detail row: a timing where grid_wgs belongs
+        grid([64, 64, 1, 0, 43, 0, 0, 12.5])           # an old autotune detail row: a timing where grid_wgs belongs
     with pytest.raises(ValueError):
-        E._grid_wgs([32, 32, 1, 4, 22, 0, 0, 768])            # a persistent-kernel grid on a wave-DMA row (there: waves per workgroup)
+        grid([32, 32, 1, 4, 22, 0, 0, 768])            # a persistent-kernel grid on a wave-DMA row (there: waves per workgroup)
     with pytest.raises(ValueError):
-        E._grid_wgs([32, 32, 1, 4, 22, 40, 4, 2])             # the wave kernel's tail split needs four-wave workgroups
-    assert E._grid_wgs([32, 32, 1, 4, 22, 40, 4, 4]) == 4 and E._grid_wgs([32, 32, 1, 2, 23, 0, 0, 2]) == 2
+        grid([32, 32, 1, 4, 22, 40, 4, 2])             # the wave kernel's tail split needs four-wave workgroups
+    assert grid([32, 32, 1, 4, 22, 40, 4, 4]) == 4 and grid([32, 32, 1, 2, 23, 0, 0, 2]) == 2
 
 
 def test_committed_table_is_well_formed():
     """Every row of yolact_minimal_amd/tuned_gfx950.json: conv rows have 7 or 8 integer fields (tile, ksplit, kwaves, stages, tail,
     [grid_wgs / waves per workgroup]), wave-kernel rows with DMA rings name a tile the kernel has, `_tp` rows shadow an existing
-    shape, weight-gradient rows have two fields."""
+    shape, weight-gradient rows have two fields; every row reads back as the plan it names (conv_plan.py).  Pyramid rows (`_L<n>`)
+    name no persistent or weight-stationary kernel: those are the stages the pyramid planner reads."""
     from yolact_minimal_amd import engine as E
+    from yolact_minimal_amd.conv_plan import ConvPlan, WgradPlan
     table = json.load(open(E.TUNED_PATH))
     assert len(table) > 400
     for key, row in table.items():
         assert all(isinstance(v, int) and not isinstance(v, bool) for v in row), (key, row)
         if key.startswith('W_'):
-            assert len(row) == 2, (key, row)
+            assert len(row) == 2 and WgradPlan.from_row(row).to_row() == row, (key, row)
             continue
         assert len(row) in (5, 7, 8), (key, row)
-        if len(row) >= 7 and row[3] > 0 and 22 <= row[4] <= 24:                      # conv_wdma_f32
-            assert (row[0], row[1]) in ((32, 32), (64, 32), (32, 64)) and row[3] in (1, 2, 4), (key, row)
-            wpb = row[7] if len(row) > 7 else 0
-            assert wpb in (0, 1, 2, 4) and (wpb == 0 or wpb >= row[3]), (key, row)
+        p = ConvPlan.from_row(row)
+        assert p.to_row() == row, (key, row)
+        if '_L' in key:
+            assert not (p.persistent or p.weight_stationary), (key, row)
+        if len(row) >= 7 and p.wave_dma:                                              # conv_wdma_f32
+            assert (p.tile_m, p.tile_n) in ((32, 32), (64, 32), (32, 64)) and p.kwaves in (1, 2, 4), (key, row)
+            wpb = p.grid_wgs
+            assert wpb in (0, 1, 2, 4) and (wpb == 0 or wpb >= p.kwaves), (key, row)
             # (K waves, ring depth, waves per workgroup) must be an instantiation csrc/conv_wave.hip builds (dispatch_dma)
             built = {(kw, ns, 4) for kw in (1, 2, 4) for ns in (2, 3)} | {(1, 2, 1), (1, 3, 1), (1, 2, 2), (1, 3, 2), (2, 2, 2), (2, 3, 2)}
-            if (row[0], row[1]) == (32, 32):
+            if (p.tile_m, p.tile_n) == (32, 32):
                 built |= {(1, 4, 4), (2, 4, 4), (4, 4, 4), (1, 4, 1), (1, 4, 2)}
-            assert (row[3], row[4] - 20, wpb or 4) in built, (key, row)
-            if row[5] or row[6]:                                                     # tail split: 32x32 tile, four K waves, <= 8 slices
-                assert (row[0], row[1], row[3]) == (32, 32, 4) and 2 <= row[6] <= 8 and wpb in (0, 4), (key, row)
+            assert (p.kwaves, p.ring, wpb or 4) in built, (key, row)
+            if p.tail_tiles or p.tail_ksplit:                                        # tail split: 32x32 tile, four K waves, <= 8 slices
+                assert (p.tile_m, p.tile_n, p.kwaves) == (32, 32, 4) and 2 <= p.tail_ksplit <= 8 and wpb in (0, 4), (key, row)
         if key.endswith('_tp'):
             assert key[:-3] in table or key[:-3].startswith('M'), key
 
@@ -75,6 +85,7 @@ def _desc_from_key(key, row):
     """A descriptor with the GEMM shape a forward-conv key names (M = B Ho Wo: any factorisation gives the same plan) and the
     row's tiling; pointers are placeholders (the planner never dereferences them)."""
     import re
+    from yolact_minimal_amd.conv_plan import ConvPlan
     from yolact_minimal_amd.hip import ConvDesc
     m = re.match(r'M(\d+)_N(\d+)_C(\d+)_k(\d+)_s(\d+)_seg(\d+)_r(\d+)', key)
     M, N, C, k, s, nseg, res = map(int, m.groups())
@@ -91,11 +102,7 @@ def _desc_from_key(key, row):
     for i in range(nseg):
         d.seg[i].n_begin, d.seg[i].n_end = cuts[i], cuts[i + 1]
         d.seg[i].out, d.seg[i].pitch, d.seg[i].batch_stride = 0x2000, cuts[i + 1] - cuts[i], ho * ho * (cuts[i + 1] - cuts[i])
-    d.tile_m, d.tile_n, d.ksplit = row[0], row[1], row[2]
-    d.kwaves = row[3] if len(row) > 3 else 0
-    d.stages = row[4] if len(row) > 4 else 0
-    d.tail_tiles, d.tail_ksplit = (row[5], row[6]) if len(row) > 6 else (0, 0)
-    d.grid_wgs = row[7] if len(row) > 7 else 0
+    ConvPlan.from_row(row).apply(d)
     d.tile_counters = 0x3000
     return d
 
@@ -108,6 +115,7 @@ def test_planner_accepts_every_forward_row_of_the_committed_table():
     import ctypes
     import re
     from yolact_minimal_amd import engine as E, hip
+    from yolact_minimal_amd.conv_plan import ConvPlan
     lib = hip.lib()
     table = json.load(open(E.TUNED_PATH))
     pat = re.compile(r'^M\d+_N\d+_C\d+_k\d+_s\d+_seg1_r[01](_tp)?$')
@@ -122,11 +130,12 @@ def test_planner_accepts_every_forward_row_of_the_committed_table():
         assert lib.ym_last_error() == sentinel, (key, row, lib.ym_last_error())
         tiles = lib.ym_conv2d_tile_counters(ctypes.byref(d))
         assert 0 <= tiles <= hip.TILE_COUNTERS, (key, row, tiles)
-        if row[0] > 0 and row[2] > 0:                  # (0 = the planner's own choice) scratch exactly when K slices meet in memory
-            tail = len(row) > 6 and row[5] > 0
-            in_workgroup = len(row) > 3 and row[3] > 0    # kwaves: the K split stays inside the workgroup
-            assert (nb > 0) == (tail or (row[2] > 1 and not in_workgroup)), (key, row, nb)
-        if len(row) > 4 and row[3] > 0 and 22 <= row[4] <= 24:
+        p = ConvPlan.from_row(row)
+        if p.tile_m > 0 and p.ksplit > 0:              # (0 = the planner's own choice) scratch exactly when K slices meet in memory
+            tail = p.tail_tiles > 0
+            in_workgroup = p.wave                         # kwaves: the K split stays inside the workgroup
+            assert (nb > 0) == (tail or (p.ksplit > 1 and not in_workgroup)), (key, row, nb)
+        if p.wave_dma:
             assert d.Cin % 32 == 0, (key, row)
             wave += 1
         split += int(nb > 0)

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ['YM_LIB_PATH'] = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'trace', 'libyolact_hip_trace.so')
 import torch  # noqa: E402
 from yolact_minimal_amd import hip  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 from tools.conv_sweep import make_desc  # noqa: E402
 
 bs = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -34,8 +35,7 @@ for spec in specs:
     d, keep = make_desc(*spec, dev)
     sig = f'M{spec[0] * d.Ho * d.Wo}_N{spec[4]}_C{spec[3]}_k{spec[5]}_s{spec[6]}_seg1_r{spec[7]}'
     hit = tuned.get(sig, [0, 0, 0, 0, 0, 0, 0])
-    d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = hit[0], hit[1], hit[2], hit[3], hit[4]
-    d.tail_tiles, d.tail_ksplit = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
+    ConvPlan.from_row(hit).apply(d)
     d.tile_counters = counters.data_ptr()
     descs.append((sig, hit, d, keep))
 # chain the buffers: conv1 reads the block input, conv2 reads conv1's output, conv3 reads conv2's output and writes the block input

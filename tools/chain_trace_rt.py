@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ['YM_LIB_PATH'] = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'trace', 'libyolact_hip_trace.so')
 import torch  # noqa: E402
 from yolact_minimal_amd import hip  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 from tools.conv_sweep import make_desc  # noqa: E402
 
 bs = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -36,8 +37,7 @@ for spec in specs:
     ov = os.environ.get('YM_CHAIN_CFG_' + str(len(descs)))          # e.g. "64,64,6,0,2,0,0": override the tuned entry of conv 0 / 1 / 2
     if ov:
         hit = [int(v) for v in ov.split(',')]
-    d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = hit[0], hit[1], hit[2], hit[3], hit[4]
-    d.tail_tiles, d.tail_ksplit = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
+    ConvPlan.from_row(hit).apply(d)
     d.tile_counters = counters.data_ptr()
     descs.append((sig, hit, d, keep))
 descs[0][2].inp = x_wide.data_ptr()

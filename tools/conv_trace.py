@@ -8,6 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ['YM_LIB_PATH'] = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'trace', 'libyolact_hip_trace.so')
 import torch  # noqa: E402
 from yolact_minimal_amd import hip  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 from tools.conv_sweep import make_desc  # noqa: E402
 
 dev = torch.device('cuda:0')
@@ -23,12 +24,10 @@ SPECS = {'bs1': ((1, 34, 34, 256, 1024, 1, 1, 1), (1, 34, 34, 1024, 256, 1, 1, 0
 for spec in SPECS[sys.argv[1] if len(sys.argv) > 1 else 'bs1']:
     d, keep = make_desc(*spec, dev)
     sig = f'M{spec[0] * d.Ho * d.Wo}_N{spec[4]}_C{spec[3]}_k{spec[5]}_s{spec[6]}_seg1_r{spec[7]}'
-    hit = tuned.get(sig, [0, 0, 0, 0, 0, 0, 0])
-    tile, ks = (hit[0], hit[1]), hit[2]
-    d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = hit[0], hit[1], hit[2], hit[3], hit[4]
-    d.tail_tiles, d.tail_ksplit = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
+    plan = ConvPlan.from_row(tuned.get(sig, []))
+    plan.apply(d)
     d.tile_counters = counters.data_ptr()
-    print(sig, hit)
+    print(sig, plan.to_row())
     for stg in (2, 22, 23, 33, 34):
         d.stages = stg
         for _ in range(3):
@@ -49,7 +48,7 @@ for spec in SPECS[sys.argv[1] if len(sys.argv) > 1 else 'bs1']:
                 spans.append(float(r[:, 3].max() - r[:, 0].min()))
                 spreads.append(float(r[:, 0].max() - r[:, 0].min()))
         t = torch.cat(rows)
-        print(f'M={M} N={spec[4]} K={d.k_pad} tile={tile} ks={ks} stages={stg}: {t.shape[0]} WGs stamped, event {e0.elapsed_time(e1) * 1e3:.1f} us')
+        print(f'M={M} N={spec[4]} K={d.k_pad} tile={(plan.tile_m, plan.tile_n)} ks={plan.ksplit} stages={stg}: {t.shape[0]} WGs stamped, event {e0.elapsed_time(e1) * 1e3:.1f} us')
         print(f'   (shader clock cycles) WG start spread per XCD {max(spreads):.0f}; prologue {((t[:, 1] - t[:, 0]).mean()):.0f}; '
               f'K loop {((t[:, 2] - t[:, 1]).mean()):.0f} (min {((t[:, 2] - t[:, 1]).min()):.0f}, max {((t[:, 2] - t[:, 1]).max()):.0f}); '
               f'epilogue {((t[:, 3] - t[:, 2]).mean()):.0f}; first start -> last end per XCD {max(spans):.0f}')

@@ -73,7 +73,6 @@ def main():
     with torch.cuda.stream(streams[0]):
         rows = eng.autotune(iters=10, cus=256 // args.parts)
     torch.cuda.synchronize()
-    rows = {k: (v if len(v) > 7 and v[7] else v[:7]) for k, v in rows.items()}
     table = E.tuned_table()
     for k in rows:
         table.pop(k + '_tp', None)

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     from yolact_minimal_amd import hip
+    from yolact_minimal_amd.conv_plan import ConvPlan
     from yolact_minimal_amd.config import build_cfg
     from yolact_minimal_amd.modules.yolact import Yolact
     name = sys.argv[1] if len(sys.argv) > 1 else 'res101_coco'
@@ -48,13 +49,13 @@ def main():
             snaps.append([t.clone() for t in owners])
         nondet = any(not torch.equal(a, b) for s in snaps[1:] for a, b in zip(snaps[0], s))
         # the same conv in its plain configuration
-        keep = (d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit)
-        d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit = 0, 0, 1, 0, 0, 0, 0
+        keep = ConvPlan.of(d)
+        ConvPlan(ksplit=1).apply(d)
         big = torch.empty(max(hip.conv_workspace_bytes(d), 256), device=dev, dtype=torch.uint8)
         hip.conv2d_fwd(d, big)
         torch.cuda.synchronize()
         plain = [t.clone() for t in owners]
-        d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit = keep
+        keep.apply(d)
         hip.conv2d_fwd(d, ws)
         torch.cuda.synchronize()
         err = max(float((a - b).abs().max()) for a, b in zip(owners, plain))

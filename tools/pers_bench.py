@@ -14,6 +14,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from yolact_minimal_amd import hip  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 from tools.conv_sweep import make_desc  # noqa: E402
 
 dev = torch.device('cuda:0')
@@ -105,9 +106,7 @@ def main():
         nkt = d.k_pad // 32
         hit = tuned.get(sig) or [0, 0, 0, 0, 0, 0, 0]
         d.tile_counters = counters.data_ptr()
-        d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = hit[0], hit[1], hit[2], hit[3], hit[4]
-        d.tail_tiles, d.tail_ksplit = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
-        d.grid_wgs = hit[7] if len(hit) > 7 else 0
+        ConvPlan.from_row(hit).apply(d)
         t_old = time_desc(d)
         flops = 2.0 * M * spec[4] * d.k_pad
         print(f'== {sig}: tuned {hit} {t_old:.1f} us {flops / t_old / 1e6:.1f} TF', flush=True)

@@ -19,6 +19,7 @@ from yolact_minimal_amd.config import build_cfg  # noqa: E402
 from yolact_minimal_amd.modules.yolact import Yolact  # noqa: E402
 from yolact_minimal_amd.trainer import Trainer  # noqa: E402
 from yolact_minimal_amd import train_engine as T, hip  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--cfg', default='res101_coco')
@@ -93,17 +94,18 @@ for key, n in counts.items():
         cfg_s = f'{d.tile_m}x{d.tile_n} ks{d.ksplit} st{d.stages} tail{d.tail_tiles}x{d.tail_ksplit}' + (' +bnsum' if d.bn_sum else '') + (' +bnb' if d.bnb_y else '')
         if (args.tune_ws and key[0] == 'f' and d.bn_sum and (d.KH, d.KW, d.stride, d.pad, d.nseg) == (1, 1, 1, 0, 1) and d.Cin % 32 == 0 and
                 d.Cin <= 256 and d.seg[0].act in (0, 1)):
-            keep = (d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs)
+            keep = ConvPlan.of(d)
             best = (us, None)
             for tm, tn in ((64, 256), (128, 128), (256, 64)):
                 if tn * d.Cin * 4 > 64 * 1024:
                     continue
                 for st in (52, 53, 54):
-                    d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs = tm, tn, 1, 0, st, 0, 0, 0
+                    cand = ConvPlan(tm, tn, 1, 0, st)
+                    cand.apply(d)
                     t = timeit(lambda: hip.conv2d_fwd(d, big))
                     if t < best[0]:
-                        best = (t, [tm, tn, 1, 0, st, 0, 0])
-            d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs = keep
+                        best = (t, cand.to_row())
+            keep.apply(d)
             name = f'M{M}_N{N}_C{d.Cin}_k1_s1_seg1_r{int(bool(d.residual))}_st'
             print(f'  ws: {name:44s} x{n:2d} {us:7.1f} -> {best[0]:7.1f} us {best[1]}', flush=True)
             if best[1] is not None and best[0] < 0.97 * us:

@@ -16,7 +16,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
-from yolact_minimal_amd import hip, engine as E  # noqa: E402
+from yolact_minimal_amd import hip, engine as E, plan_transfer  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan, from_entry  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--batch', type=int, default=1)
@@ -101,15 +102,11 @@ def forward_ms():
     return best
 
 
-def get(c):
-    return [c.tile[0], c.tile[1], c.ksplit, c.kwaves, c.stages, c.tail[0], c.tail[1], c.grid_wgs]
-
-
 def put(sig, v):
     for e in (pipe.engines if pipe is not None else [eng]):
         for c in e.convs:
             if c.sig == sig:
-                c.tile, c.ksplit, c.kwaves, c.stages, c.tail, c.grid_wgs = (v[0], v[1]), v[2], v[3], v[4], (v[5], v[6]), v[7]
+                c.plan = v
         e.retune()
 
 
@@ -130,40 +127,37 @@ for sig, cs in groups.items():
 for _, sig, t0 in sorted(order):
     cs = groups[sig]
     c, d = cs[0], cs[0].desc
-    cur = get(c)
+    cur = c.plan
     M = d.B * d.Ho * d.Wo
     cands = []
     for tm, tn in ((32, 32), (64, 32), (32, 64)):
         for kwv in (1, 2, 4):
             if kwv > d.k_pad // 32:
                 continue
-            vs = [[tm, tn, 1, kwv, 22, 0, 0, 0]]
+            vs = [ConvPlan(tm, tn, 1, kwv, 22)]
             if kwv < 4:                                   # fewer waves per workgroup: single tiles are balanced over the CUs
-                vs += [[tm, tn, 1, kwv, 22, 0, 0, wpb] for wpb in (1, 2) if wpb >= kwv]
+                vs += [ConvPlan(tm, tn, 1, kwv, 22, grid_wgs=wpb) for wpb in (1, 2) if wpb >= kwv]
             tiles = -(-M // 32) * -(-d.Cout // 32)
             if (tm, tn, kwv) == (32, 32, 4) and tiles > 256 and d.nseg == 1 and d.tile_counters:
                 # tail split: the tiles past the last full round of 256 CUs are computed as K slices in the CUs' second slots
                 for ts in (4, 6, 8):
                     if ts * 2 <= d.k_pad // 32:
-                        vs.append([tm, tn, 1, kwv, 22, tiles % 256 or 256, ts, 0])
+                        vs.append(ConvPlan(tm, tn, 1, kwv, 22, tiles % 256 or 256, ts))
             for v in vs:
-                keep = (d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs)
-                d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs = v
+                keep = ConvPlan.of(d)
+                v.apply(d)
                 t = launch_time(d)
-                d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs = keep
+                keep.apply(d)
                 if t is not None:
                     cands.append((t, v))
     if pipe is not None:              # the latency entry is a candidate too (the slot may currently run a `_tp` row)
-        alt = E.tuned_table().get(sig)
-        if alt:
-            cands.append((0.0, list(alt[:7]) + [alt[7] if len(alt) > 7 else 0]))
+        alt = from_entry(E.tuned_table().get(sig))
+        if alt is not None:
+            cands.append((0.0, alt))
     for tab in alts:                  # another table's choice for this shape (its own row, or the nearest tuned shape's, re-derived)
-        from yolact_minimal_amd import plan_transfer
-        row, _ = plan_transfer.lookup(tab, sig, M, d.Cout, d.k_pad // 32, d.nseg)
-        if row is not None:
-            row = list(row[:7]) + [0] * (7 - len(row[:7])) + [row[7] if len(row) > 7 else 0]
-            if row != cur and all(row != v for _, v in cands):
-                cands.append((0.0, row))
+        alt = from_entry(plan_transfer.lookup(tab, sig, M, d.Cout, d.k_pad // 32, d.nseg)[0])
+        if alt is not None and alt != cur and all(alt != v for _, v in cands):
+            cands.append((0.0, alt))
     cands.sort()
     tried = 0
     t_ref = min([t0] + [t for t, _ in cands if t > 0])
@@ -177,8 +171,8 @@ for _, sig, t0 in sorted(order):
         if ms < cur_ms * 0.998:
             ms2 = forward_ms()
             if max(ms, ms2) < cur_ms * 0.998:
-                cur_ms, cur, kept[sig], tag = max(ms, ms2), v, (v if v[7] else v[:7]), '  <-- kept'
-        print(f'{sig:42s} x{len(cs):2d} launch {t0:6.2f} -> {t:6.2f} us {v} forward {ms:.4f} ms{tag}', flush=True)
+                cur_ms, cur, kept[sig], tag = max(ms, ms2), v, v.to_row(), '  <-- kept'
+        print(f'{sig:42s} x{len(cs):2d} launch {t0:6.2f} -> {t:6.2f} us {list(v)} forward {ms:.4f} ms{tag}', flush=True)
         put(sig, cur)
 final = forward_ms()
 print(f'final: forward {base_ms:.4f} -> {final:.4f} ms; {len(kept)} entries change', flush=True)

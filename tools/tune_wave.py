@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
 from yolact_minimal_amd import hip, engine as E  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--batch', type=int, default=1)
@@ -63,10 +64,7 @@ for c in eng.convs:
     if c.sig in seen or c.stem or d.nlevels or d.Cin % 32 or M > args.max_m:
         continue
     seen.add(c.sig)
-    keep = (d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs)
-
-    def set_cfg(v):
-        d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs = v
+    keep = ConvPlan.of(d)
 
     # reference output of the tuned kernel on the plan's own buffers (single plain output only; segmented heads: checked by the tests)
     ref = None
@@ -92,8 +90,8 @@ for c in eng.convs:
             for stg in (22, 23, 24):
                 if stg == 24 and (tm, tn) != (32, 32):
                     continue
-                cand = (tm, tn, 1, kwv, stg, 0, 0, 0)
-                set_cfg(cand)
+                cand = ConvPlan(tm, tn, 1, kwv, stg)
+                cand.apply(d)
                 t = time_desc(d)
                 if t is None:
                     continue
@@ -103,18 +101,18 @@ for c in eng.convs:
                     err = float((view - ref).abs().max()) / max(1e-30, float(ref.abs().max()))
                     worst = max(worst, err)
                     if not err < 1e-5:
-                        print(f'  MISMATCH {c.sig} {cand}: max rel err {err:.3e}', flush=True)
+                        print(f'  MISMATCH {c.sig} {tuple(cand)}: max rel err {err:.3e}', flush=True)
                         continue
                 if os.environ.get('YM_TUNE_VERBOSE') and c.sig in os.environ['YM_TUNE_VERBOSE']:
                     print(f'      {cand[:5]} {t:7.2f} us', flush=True)
                 if t < best[0] * args.margin:
                     best = (t, cand)
-    set_cfg(keep)
+    keep.apply(d)
     tot0 += base
     tot1 += best[0]
     print(f'{c.sig:42s} {list(keep[:7])} {base:7.2f} us -> {list(best[1][:7])} {best[0]:7.2f} us', flush=True)
     if best[1] != keep:
-        new[c.sig] = list(best[1][:7])
+        new[c.sig] = best[1].to_row()
 print(f'{len(seen)} shapes (M <= {args.max_m}): {tot0:.1f} -> {tot1:.1f} us summed over distinct shapes; {len(new)} entries change; worst candidate error {worst:.2e}')
 if args.out:
     json.dump(new, open(args.out, 'w'), indent=0, sort_keys=True)

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
 from yolact_minimal_amd import hip, engine as E  # noqa: E402
+from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--batch', type=int, default=8)
@@ -64,18 +65,19 @@ for cfg_name in args.cfgs.split(','):
             continue
         seen.add(c.sig)
         n_same = sum(1 for o in eng.convs if o.sig == c.sig)
-        keep = (d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs)
+        keep = ConvPlan.of(d)
         t0 = launch_time(d)
         best = (t0, None)
         for tm, tn in ((64, 256), (128, 128), (256, 64)):
             if tn * d.Cin * 4 > 64 * 1024:
                 continue
             for st in (52, 53, 54):
-                d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs = tm, tn, 1, 0, st, 0, 0, 0
+                cand = ConvPlan(tm, tn, 1, 0, st)
+                cand.apply(d)
                 t = launch_time(d)
                 if t is not None and t < best[0]:
-                    best = (t, [tm, tn, 1, 0, st, 0, 0])
-        d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages, d.tail_tiles, d.tail_ksplit, d.grid_wgs = keep
+                    best = (t, cand.to_row())
+        keep.apply(d)
         gain = best[1] is not None and best[0] < 0.97 * t0
         gf = c.flops / 1e9
         print(f'{cfg_name:14s} {c.sig:40s} x{n_same:2d} {t0:7.1f} us ({gf / t0 * 1e3:5.1f} TF) -> {best[0]:7.1f} us ({gf / best[0] * 1e3:5.1f} TF) '

@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from yolact_minimal_amd import hip  # noqa: E402
+from yolact_minimal_amd.conv_plan import WgradPlan  # noqa: E402
 from yolact_minimal_amd.hip import WgradDesc  # noqa: E402
 
 dev = torch.device('cuda:0')
@@ -19,7 +20,7 @@ IN_OF = {272: 544, 136: 136, 68: 68, 34: 34, 17: 17, 9: 9, 5: 5}
 S2_IN = {272: 544, 68: 136, 34: 68, 17: 34, 9: 17, 5: 9}
 big = torch.empty(1 << 29, dtype=torch.uint8, device=dev)
 rows = []
-for key, hit in sorted(table.items()):
+for key, row in sorted(table.items()):
     m = re.match(r'W_M(\d+)_N(\d+)_C(\d+)_k(\d+)_s(\d+)$', key)
     if not m:
         continue
@@ -37,8 +38,8 @@ for key, hit in sorted(table.items()):
     d = WgradDesc()
     d.x, d.dy, d.dw = x.data_ptr(), dy.data_ptr(), dw.data_ptr()
     d.B, d.H, d.W, d.Cin, d.Cin_real, d.Cout, d.Cout_real = b, h, h, c, cin_real, n, n
-    d.KH, d.KW, d.stride, d.pad, d.Ho, d.Wo, d.msplit = k, k, s, pad, ho, ho, hit[0]
-    d.lds_buffers = hit[1] if len(hit) > 1 else 2
+    d.KH, d.KW, d.stride, d.pad, d.Ho, d.Wo = k, k, s, pad, ho, ho
+    WgradPlan.from_row(row).apply(d)
     need = hip.lib().ym_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
     if need == 0 or need > big.numel():
         print(key, 'skipped', need)
@@ -56,7 +57,7 @@ for key, hit in sorted(table.items()):
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / 5 * 1e3
     gf = 2.0 * M * n * k * k * c / 1e9
-    rows.append((key, hit[0], us, gf / us * 1e-3 * 1e3))
+    rows.append((key, d.msplit, us, gf / us * 1e-3 * 1e3))
     del x, dy, dw
 for key, ms, us, tf in sorted(rows, key=lambda r: -r[2]):
     print(f'{key:34s} msplit={ms:4d} {us:9.1f} us {tf:7.1f} TF')

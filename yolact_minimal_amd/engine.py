@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import hip, plan_transfer
+from .conv_plan import ConvPlan, from_entry
 from .hip import ConvDesc, ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU
 
 
@@ -38,22 +39,6 @@ _tuned = None
 def conv_mma():
     """YM_CONV_MMA = 0 (default: f32 MFMA, the parity mode) | 3 (bf16x3) | 6 (bf16x6): see ym_conv_desc.mma."""
     return int(os.environ.get('YM_CONV_MMA', '0') or 0)
-
-
-def _grid_wgs(hit):
-    """Eighth field of a tuned entry = `grid_wgs` of the persistent kernel.  (Old detail rows of `InferEngine.autotune` carried a
-    timing there: anything that is not a non-negative integer is rejected instead of landing in a c_int32 field.)"""
-    if len(hit) <= 7:
-        return 0
-    g = hit[7]
-    if isinstance(g, bool) or not isinstance(g, int) or g < 0:
-        raise ValueError(f'tuned entry {hit}: field 7 must be grid_wgs (a non-negative integer)')
-    if hit[3] > 0 and 22 <= hit[4] <= 24:
-        # wave kernel with DMA rings (conv_wdma_f32): the field is WAVES PER WORKGROUP, not a grid size -- a row edited over from
-        # the persistent kernel (hundreds of workgroups) would be rejected by the launch, or silently lose its tail split
-        if g not in (0, 1, 2, 4) or (g and g < hit[3]) or ((hit[5] or hit[6]) and g not in (0, 4)):
-            raise ValueError(f'tuned entry {hit}: field 7 of a wave-DMA row is waves per workgroup (0 / 1 / 2 / 4, >= kwaves; 0 / 4 with a tail)')
-    return g
 
 
 def autotune_on():
@@ -165,14 +150,9 @@ class _Conv:
         self.k_pad = _round_up(self.kh * self.kw * self.cin_pad, 32)
         self.weight = self.scale = self.shift = None
         self.desc = None
-        self.tile = (0, 0)
-        self.ksplit = 0
-        self.kwaves = 0
-        self.stages = 0
-        self.tail = (0, 0)           # (tail_tiles, tail_ksplit): see ym_conv_desc
-        self.grid_wgs = 0            # persistent kernel (stages 4x): workgroups launched, 0 = as many as the CUs hold
+        self.plan = ConvPlan()       # tile / K split / kernel family of the launch (conv_plan.py); all zeros = the planner's heuristic
         self.mma = 0                 # 0 = f32 MFMA (parity mode); 3 / 6 = split-bf16 products (ym_conv_desc.mma)
-        self._hit = None             # the plan row this conv was bound with, and where it came from (_entry)
+        self._hit = None             # the plan this conv was bound with, and where it came from (_entry)
         self._shape = (0, 0, 0, 1)   # (M, N, K tiles, output segments) of the bound launch
         self.plan_source = 'heuristic'
 
@@ -218,29 +198,18 @@ class _Conv:
             d.seg[i].n_begin, d.seg[i].n_end = n0, n1
             d.seg[i].out = base_ptr
             d.seg[i].batch_stride, d.seg[i].pitch, d.seg[i].act = bstride, pitch, act
-        d.tile_m, d.tile_n = self.tile
-        d.ksplit = self.ksplit
-        d.kwaves = self.kwaves
-        d.stages = self.stages
         self.desc = d
         self._bind_params()
         self.out_hw = (ho, wo)
         self.flops = 2.0 * b * ho * wo * self.cout * self.kh * self.kw * self.cin
         self.sig = f'M{b * ho * wo}_N{self.cout}_C{cin}_k{self.kh}_s{self.stride}_seg{len(segs)}_r{int(residual is not None)}'
         self._shape = (b * ho * wo, self.cout, self.k_pad // 32, len(segs))
-        hit, self.plan_source = _entry(self.sig, *self._shape, with_source=True)
-        self._hit = hit
-        if hit and self.tile == (0, 0) and self.ksplit == 0 and self.kwaves == 0:
-            self.tile, self.ksplit, self.kwaves = (hit[0], hit[1]), hit[2], (hit[3] if len(hit) > 3 else 0)
-            self.stages = hit[4] if len(hit) > 4 else 0
-            self.tail = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
-            d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = hit[0], hit[1], hit[2], self.kwaves, self.stages
-            d.tail_tiles, d.tail_ksplit = self.tail
-            self.grid_wgs = d.grid_wgs = _grid_wgs(hit)         # persistent kernel (stages 4x): workgroups launched
-            cap = int(os.environ.get('YM_MAX_KSPLIT', '0') or 0)     # experiment knob: cap the K split of the tuned choice
-            if cap and self.ksplit > cap:
-                self.ksplit = d.ksplit = cap
-        self.apply_mma(conv_mma())
+        row, self.plan_source = _entry(self.sig, *self._shape, with_source=True)
+        self._hit = hit = from_entry(row)
+        p = self.plan
+        if hit is not None and p.tile_m == p.tile_n == p.ksplit == p.kwaves == 0:
+            self.plan = hit
+        self.apply_mma(conv_mma())                  # (writes the plan into the descriptor)
         return ho, wo
 
     def tuned_key(self):
@@ -252,36 +221,24 @@ class _Conv:
         d = self.desc
         ok = mma in (3, 6) and not self.stem and d.Cin % 32 == 0 and d.nlevels == 0
         self.mma = mma if ok else 0
-        hit = None
+        plan = None
         if self.mma and os.environ.get('YM_NO_TUNED', '0') != '1':      # this pipe's own row: exact, or the nearest tuned shape's
-            hit, _ = plan_transfer.lookup(tuned_table(), self.tuned_key(), *self._shape)
-        if hit is None:
-            hit = self._hit                 # (no entry for this pipe: the f32 choice, incl. its wave kernel for tiny layers)
-            if self.mma and hit and len(hit) > 4 and 52 <= hit[4] <= 54:
-                hit = [0, 0, 0, 0, 0, 0, 0]  # (the f32 choice is the weight-stationary kernel, whose tiles the split-bf16 kernel does not have)
-            if self.mma and hit and self.plan_source != 'table' and len(hit) > 3 and hit[3] > 0:
-                hit = [0, 0, 0, 0, 0, 0, 0]  # (a TRANSFERRED f32 row naming the wave kernel is no measurement against this pipe)
-        d.mma = self.mma
-        if hit and os.environ.get('YM_NO_TUNED', '0') != '1':     # each matrix pipe has its own measured tile / split-K / tail choice
-            self.tile, self.ksplit, self.kwaves = (hit[0], hit[1]), hit[2], (hit[3] if len(hit) > 3 else 0)
-            self.stages = hit[4] if len(hit) > 4 else 0
-            self.tail = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
-            cap = int(os.environ.get('YM_MAX_KSPLIT', '0') or 0)     # experiment knob: cap the K split of the tuned choice
-            if cap and self.ksplit > cap:
-                self.ksplit = cap
-            d.tile_m, d.tile_n, d.ksplit, d.kwaves = self.tile[0], self.tile[1], self.ksplit, self.kwaves
-            d.tail_tiles, d.tail_ksplit = self.tail
-            self.grid_wgs = d.grid_wgs = _grid_wgs(hit)
-            if self.kwaves:                                         # the tuner may prefer the f32 wave kernel for a tiny layer
+            plan = from_entry(plan_transfer.lookup(tuned_table(), self.tuned_key(), *self._shape)[0])
+        if plan is None:
+            plan = self._hit                # (no entry for this pipe: the f32 choice, incl. its wave kernel for tiny layers)
+            # (not the weight-stationary kernel, whose tiles this pipe lacks; nor a TRANSFERRED wave-kernel row: not measured on it)
+            if self.mma and plan is not None and (plan.weight_stationary or (self.plan_source != 'table' and plan.wave)):
+                plan = ConvPlan()
+        if plan is not None and os.environ.get('YM_NO_TUNED', '0') != '1':     # each matrix pipe has its own measured choice
+            self.plan = plan
+            if plan.wave:                                           # the tuner may prefer the f32 wave kernel for a tiny layer
                 self.mma = 0
-                d.mma = 0
         if self.mma:
             # split modes stage through registers: 0/2 = one register set (fewer VGPRs: two workgroups per CU on the big tiles),
             # 3 = two sets (the tile being converted arrived an iteration earlier: wins where occupancy is one wave per SIMD anyway)
-            self.stages = 3 if self.stages == 3 else 0
-            if os.environ.get('YM_MMA_STAGES'):
-                self.stages = int(os.environ['YM_MMA_STAGES'])
-        d.stages = self.stages
+            self.plan = self.plan._replace(stages=3 if self.plan.stages == 3 else 0)
+        self.plan.apply(d)
+        d.mma = self.mma
 
 
 def _bind_pyramid(layer, pyr, batch, shapes, segs):
@@ -307,15 +264,11 @@ def _bind_pyramid(layer, pyr, batch, shapes, segs):
     layer.flops = 2.0 * rows * layer.cout * layer.kh * layer.kw * layer.cin
     layer.sig = f'M{rows}_N{layer.cout}_C{cin}_k{layer.kh}_s1_seg{len(segs)}_r0_L{len(shapes)}'
     layer._shape = (rows, layer.cout, layer.k_pad // 32, len(segs))
-    hit, layer.plan_source = _entry(layer.sig, *layer._shape, with_source=True)
-    layer._hit = hit
-    if hit:
-        layer.tile, layer.ksplit, layer.kwaves = (hit[0], hit[1]), hit[2], 0
-        layer.stages = 0
-        layer.tail = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
-    d.tile_m, d.tile_n = layer.tile
-    d.ksplit = layer.ksplit
-    d.tail_tiles, d.tail_ksplit = layer.tail
+    row, layer.plan_source = _entry(layer.sig, *layer._shape, with_source=True)
+    layer._hit = hit = from_entry(row)
+    if hit is not None:                # (tile, K split and tail; set_mma writes the whole row, whose stages the pyramid launch ignores)
+        layer.plan = ConvPlan(hit.tile_m, hit.tile_n, hit.ksplit, tail_tiles=hit.tail_tiles, tail_ksplit=hit.tail_ksplit)
+    layer.plan.apply(d)
 
 
 class InferEngine:
@@ -361,12 +314,11 @@ class InferEngine:
         if not todo:
             return
         rows = self.autotune(iters=10, skip=have)
-        rows = {k: (v if len(v) > 7 and v[7] else v[:7]) for k, v in rows.items()}
         tuned_table().update(rows)
         plan_transfer._index_cache.clear()
         for c in self.convs:
             if c.sig in rows:
-                c.plan_source, c._hit = 'autotuned', rows[c.sig]
+                c.plan_source, c._hit = 'autotuned', ConvPlan.from_row(rows[c.sig])
         try:
             _store_user_rows(rows)
         except OSError as e:
@@ -632,14 +584,9 @@ class InferEngine:
         self.graph = None
 
     def retune(self):
-        """Re-read tile/ksplit knobs of every conv into its descriptor (after changing `layer.tile/ksplit`)."""
+        """Re-read the plan of every conv into its descriptor (after changing `layer.plan` / `layer.mma`)."""
         for c in self.convs:
-            c.desc.tile_m, c.desc.tile_n = c.tile
-            c.desc.ksplit = c.ksplit
-            c.desc.kwaves = c.kwaves
-            c.desc.stages = c.stages
-            c.desc.tail_tiles, c.desc.tail_ksplit = c.tail
-            c.desc.grid_wgs = c.grid_wgs
+            c.plan.apply(c.desc)
             c.desc.mma = c.mma
         self._alloc_workspaces()
         self.graph = None
@@ -656,7 +603,7 @@ class InferEngine:
 
     def autotune(self, iters=10, verbose=False, mma=0, concurrent=False, skip=(), cus=256):
         """Time every (tile, ksplit) candidate of every distinct conv shape on this GPU; keep the fastest.
-        Returns {signature: [tile_m, tile_n, ksplit, kwaves, stages, tail_tiles, tail_ksplit, grid_wgs]} = rows of the tuned table;
+        Returns {signature: ConvPlan.to_row()} = rows of the tuned table;
         the timings are left in `self.autotune_detail` = {signature: (best_us, default_us)}.  Persistent candidates (stages 4x) are
         timed and kept with grid_wgs = 0 (as many workgroups as the CUs hold; tools/pers_bench.py sweeps the grid).
         `concurrent`: tune for THROUGHPUT with requests in flight (bench.py --inflight 2) instead of for the latency of a launch
@@ -686,12 +633,10 @@ class InferEngine:
                     with torch.cuda.stream(side):
                         hip.conv2d_fwd(d2[i], big_ws2[i])
 
-        def time_cfg(c, tile, ks, kwv=0, stg=0, tail=(0, 0), gw=0):
+        def time_cfg(c, plan):
             d = c.desc
-            d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = tile[0], tile[1], ks, kwv, stg
-            d.mma = mma if (split_ok(c) and kwv == 0) else 0
-            d.tail_tiles, d.tail_ksplit = tail
-            d.grid_wgs = gw                      # (never the previous table entry's grid; wave kernel with DMA rings: waves per workgroup)
+            plan.apply(d)                        # (never the previous table entry's grid; wave kernel with DMA rings: waves per workgroup)
+            d.mma = mma if (split_ok(c) and not plan.wave) else 0
             need = hip.conv_workspace_bytes(d)
             if need > big_ws.numel():
                 return None
@@ -732,14 +677,14 @@ class InferEngine:
             if c.sig + (f'_mma{mma}' if mma else '') in skip:
                 continue
             if c.sig in seen:
-                c.tile, c.ksplit, c.kwaves, c.stages, c.tail, c.grid_wgs = seen[c.sig]
-                c.mma = mma if (mma and c.kwaves == 0) else 0
+                c.plan = seen[c.sig]
+                c.mma = mma if (mma and not c.plan.wave) else 0
                 continue
             d = c.desc
             M, nkt = d.B * d.Ho * d.Wo, d.k_pad // 32
             if d.nlevels:
                 M = sum(d.B * d.level_h[l] * d.level_w[l] for l in range(d.nlevels))
-            base = time_cfg(c, (0, 0), 0, 0)
+            base = time_cfg(c, ConvPlan())
             cands, wave_cands = [], []
             tiles = [(128, 64)] if c.stem else [(128, 128), (128, 64), (64, 128), (64, 64)]
             for tm, tn in tiles:
@@ -747,21 +692,21 @@ class InferEngine:
                 for ks in (1, 2, 3, 4, 6, 8, 12, 16, 24):
                     if ks > 1 and (wgs >= 1024 or ks * 2 > nkt or wgs * ks > 8192):
                         continue
-                    cands.append(((tm, tn), ks, 0, 2, (0, 0)))
+                    cands.append(ConvPlan(tm, tn, ks, 0, 2))
                     if (tm, tn) != (128, 128) and nkt // ks >= 3:
-                        cands.append(((tm, tn), ks, 0, 3, (0, 0)))
+                        cands.append(ConvPlan(tm, tn, ks, 0, 3))
                     if not c.stem:                       # direct-to-LDS staging, ring of 2 / 3 (/ 4)
-                        cands.append(((tm, tn), ks, 0, 22, (0, 0)))
+                        cands.append(ConvPlan(tm, tn, ks, 0, 22))
                         if nkt // ks >= 3:
-                            cands.append(((tm, tn), ks, 0, 23, (0, 0)))
+                            cands.append(ConvPlan(tm, tn, ks, 0, 23))
                         if (tm, tn) == (64, 64) and nkt // ks >= 4:
-                            cands.append(((tm, tn), ks, 0, 24, (0, 0)))
+                            cands.append(ConvPlan(tm, tn, ks, 0, 24))
                         if (tm, tn) == (64, 64) and nkt // ks >= 2:    # + software-pipelined fragments
-                            cands.append(((tm, tn), ks, 0, 33, (0, 0)))
-                            cands.append(((tm, tn), ks, 0, 34, (0, 0)))
+                            cands.append(ConvPlan(tm, tn, ks, 0, 33))
+                            cands.append(ConvPlan(tm, tn, ks, 0, 34))
                         if (tm, tn) == (64, 64) and d.nseg == 1 and d.tile_counters and c.act in (ACT_NONE, ACT_RELU):
-                            cands.append(((tm, tn), ks, 0, 43, (0, 0)))    # persistent kernel (conv_persist.hip), ring of 3 / 6
-                            cands.append(((tm, tn), ks, 0, 46, (0, 0)))
+                            cands.append(ConvPlan(tm, tn, ks, 0, 43))    # persistent kernel (conv_persist.hip), ring of 3 / 6
+                            cands.append(ConvPlan(tm, tn, ks, 0, 46))
                 # workgroup-quantisation fix: split the tiles of the last partial round (over 256 CUs x 1 or 2 workgroups)
                 if not c.stem and d.nseg == 1 and d.tile_counters and cus < wgs <= hip.TILE_COUNTERS:
                     for r in sorted({wgs % cus, wgs % (2 * cus)} - {0}):
@@ -769,7 +714,7 @@ class InferEngine:
                             if ts * 2 > nkt or r * ts > 2048:
                                 continue
                             for stg in ((2, 3, 22, 23) + ((33, 34) if (tm, tn) == (64, 64) else ()) if (tm, tn) != (128, 128) and nkt // ts >= 3 else (2, 22)):
-                                cands.append(((tm, tn), 1, 0, stg, (r, ts)))
+                                cands.append(ConvPlan(tm, tn, 1, 0, stg, r, ts))
             if not c.stem:
                 for tm, tn in ((32, 32), (64, 32), (32, 64), (64, 64)):
                     waves = -(-M // tm) * -(-d.Cout // tn)
@@ -780,7 +725,7 @@ class InferEngine:
                             continue
                         if waves * kwv > 65536:
                             continue
-                        cands.append(((tm, tn), 1, kwv, 0, (0, 0)))
+                        cands.append(ConvPlan(tm, tn, 1, kwv))
                 # the wave kernel with private DMA rings (conv_wdma_f32): K split inside the workgroup, no K-slice exchange; one- and
                 # two-wave workgroups where the waves share nothing; the tail split of a 32x32 / four-K-wave plan.  (A launch repeated
                 # back to back undervalues it against the kernels with a cross-workgroup exchange: tools/tune_forward.py judges the
@@ -789,26 +734,24 @@ class InferEngine:
                     for tm, tn in ((32, 32), (64, 32), (32, 64)):
                         for kwv in (1, 2, 4):
                             if kwv <= nkt:
-                                wave_cands.append(((tm, tn), 1, kwv, 22, (0, 0), 0))
-                                wave_cands += [((tm, tn), 1, kwv, 22, (0, 0), wpb) for wpb in (1, 2) if wpb >= kwv and kwv < 4]
+                                wave_cands.append(ConvPlan(tm, tn, 1, kwv, 22))
+                                wave_cands += [ConvPlan(tm, tn, 1, kwv, 22, grid_wgs=wpb) for wpb in (1, 2) if wpb >= kwv and kwv < 4]
                     tiles32 = -(-M // 32) * -(-d.Cout // 32)
                     if cus < tiles32 <= hip.TILE_COUNTERS and d.nseg == 1 and d.tile_counters:
-                        wave_cands += [((32, 32), 1, 4, 22, (tiles32 % cus or cus, ts), 0) for ts in (4, 6, 8) if ts * 2 <= nkt]
+                        wave_cands += [ConvPlan(32, 32, 1, 4, 22, tiles32 % cus or cus, ts) for ts in (4, 6, 8) if ts * 2 <= nkt]
             if mma:                                          # split-bf16: register staging with one (0) or two (3) register sets
-                cands = sorted({(tile, ks, kwv, st, tail) for tile, ks, kwv, stg, tail in cands for st in ((0, 3) if kwv == 0 else (0,))})
-            best = (base, (0, 0), 0, 0, 0, (0, 0), 0)
-            for cand in [cd + (0,) for cd in cands] + ([] if mma else wave_cands):
-                tile, ks, kwv, stg, tail, gw = cand
-                t = time_cfg(c, tile, ks, kwv, stg, tail, gw)
-                if t is not None and t < best[0] * 0.98:
-                    best = (t, tile, ks, kwv, stg, tail, gw)
-            c.tile, c.ksplit, c.kwaves, c.stages, c.tail, c.grid_wgs = best[1], best[2], best[3], best[4], best[5], best[6]
-            c.mma = mma if (mma and c.kwaves == 0) else 0
-            seen[c.sig] = (c.tile, c.ksplit, c.kwaves, c.stages, c.tail, c.grid_wgs)
-            results[c.sig + (f'_mma{mma}' if mma else '')] = [best[1][0], best[1][1], best[2], best[3], best[4], best[5][0], best[5][1], best[6]]
-            self.autotune_detail[c.sig + (f'_mma{mma}' if mma else '')] = (round(best[0], 2), round(base, 2))
+                cands = sorted({p._replace(stages=st) for p in cands for st in ((0, 3) if not p.wave else (0,))})
+            best, p = base, ConvPlan()
+            for cand in cands + ([] if mma else wave_cands):
+                t = time_cfg(c, cand)
+                if t is not None and t < best * 0.98:
+                    best, p = t, cand
+            c.plan = seen[c.sig] = p
+            c.mma = mma if (mma and not p.wave) else 0
+            results[c.sig + (f'_mma{mma}' if mma else '')] = p.to_row()
+            self.autotune_detail[c.sig + (f'_mma{mma}' if mma else '')] = (round(best, 2), round(base, 2))
             if verbose:
-                print(f'{c.sig:44s} default {base:8.1f} us -> {best[1]} ks={best[2]} kw={best[3]} st={best[4]} tail={best[5]} {best[0]:8.1f} us', flush=True)
+                print(f'{c.sig:44s} default {base:8.1f} us -> {p.to_row()} {best:8.1f} us', flush=True)
         del big_ws
         self.retune()
         return results

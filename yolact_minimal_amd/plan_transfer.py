@@ -23,6 +23,8 @@ import math
 import os
 import re
 
+from .conv_plan import ConvPlan, WgradPlan
+
 _SIG = re.compile(r'^(T_|W_)?M(\d+)_N(\d+)_C(\d+)_k(\d+)_s(\d+)(?:_seg(\d+)_r(\d))?(_L\d+)?(_st|_tp|_mma\d)?$')
 _KS_ALLOWED = (1, 2, 3, 4, 6, 8, 12, 16, 24)
 TILE_COUNTERS = 16384        # = hip.TILE_COUNTERS (int32 arrival counters the engines allocate)
@@ -89,13 +91,12 @@ def _cdiv(a, b):
 
 
 def transfer_conv(row, M_donor, M, N, nkt, nseg=1, counters=True):
-    """Row of a forward / data-gradient launch ([tile_m, tile_n, ksplit, kwaves, stages, tail_tiles, tail_ksplit(, grid_wgs)]) of a
-    donor with M_donor rows, re-derived for M rows (N output channels, nkt K tiles of 32, nseg output segments; `counters`: the
-    caller provides arrival counters, without which a tail split is not possible)."""
-    row = list(row) + [0] * (8 - len(row))
-    tm, tn, ks, kw, st, tail_t, tail_k, g = row[:8]
+    """Row of a forward / data-gradient launch (conv_plan.ConvPlan) of a donor with M_donor rows, re-derived for M rows (N output
+    channels, nkt K tiles of 32, nseg output segments; `counters`: the caller provides arrival counters, without which a tail
+    split is not possible)."""
+    tm, tn, ks, kw, _, tail_t, tail_k, g = plan = ConvPlan.from_row(row)
     if tm == 0 or tn == 0:
-        return [0, 0, 0, 0, 0, 0, 0]
+        return ConvPlan().to_row()
     w_d, w = _cdiv(M_donor, tm) * _cdiv(N, tn), _cdiv(M, tm) * _cdiv(N, tn)
     out_ks, out_tail = ks, (0, 0)
     if kw == 0:
@@ -117,7 +118,7 @@ def transfer_conv(row, M_donor, M, N, nkt, nseg=1, counters=True):
                 out_tail = (r, ts)
     else:
         out_ks = 1
-        if tail_t > 0 and tail_k > 1 and counters and nseg == 1 and (tm, tn) == (32, 32) and kw == 4 and 22 <= st <= 24 and \
+        if tail_t > 0 and tail_k > 1 and counters and nseg == 1 and (tm, tn) == (32, 32) and kw == 4 and plan.wave_dma and \
                 256 < w <= TILE_COUNTERS and g in (0, 4):
             ts = tail_k
             while ts > 1 and ts * 2 > nkt:
@@ -126,19 +127,16 @@ def transfer_conv(row, M_donor, M, N, nkt, nseg=1, counters=True):
                 out_tail = (w % 256 or 256, ts)
         if kw > nkt:                                 # K waves of the wave kernel: 1 / 2 / 4 / 8, at most one per K tile
             kw = max(k for k in (1, 2, 4, 8) if k <= max(1, nkt))
-    out = [tm, tn, out_ks, kw, st, out_tail[0], out_tail[1]]
-    if g:
-        out.append(g)
-    return out
+    return plan._replace(ksplit=out_ks, kwaves=kw, tail_tiles=out_tail[0], tail_ksplit=out_tail[1]).to_row()
 
 
 def transfer_wgrad(row, M_donor, M):
-    """Row of a weight-gradient launch ([msplit, ring]): the pixel split follows the tile count of (Cout, K), not M; it is only
-    capped so that a slice keeps at least 128 pixels."""
-    ms = row[0]
-    if ms > 1 and M // ms < 128:
-        ms = max(1, M // 128)
-    return [ms] + list(row[1:])
+    """Row of a weight-gradient launch (conv_plan.WgradPlan): the pixel split follows the tile count of (Cout, K), not M; it is
+    only capped so that a slice keeps at least 128 pixels."""
+    plan = WgradPlan.from_row(row)
+    if plan.msplit > 1 and M // plan.msplit < 128:
+        plan = plan._replace(msplit=max(1, M // 128))
+    return plan.to_row()
 
 
 def lookup(table, sig, M, N, nkt, nseg=1, counters=True):

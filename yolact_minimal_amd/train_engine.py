@@ -18,7 +18,8 @@ import weakref
 import torch
 import torch.nn.functional as F
 
-from . import hip
+from . import hip, plan_transfer
+from .conv_plan import ConvPlan, WgradPlan, from_entry
 from .hip import ConvDesc, WgradDesc, ACT_NONE, ACT_RELU, ACT_TANH
 
 _scratch = {}
@@ -88,12 +89,11 @@ def _configure_conv(d, key, stats=False):
     """Set tile/ksplit/kwaves of a ConvDesc from the tuned table (or sweep it when YM_TUNE_TRAIN=1).  `stats`: the launch carries
     fused BatchNorm sums, which the persistent kernel does not do: `<key>_st` holds the per-item choice measured for such launches
     where the plain entry (shared with inference) selects the persistent kernel."""
-    from . import plan_transfer
     M_rows = d.B * d.Ho * d.Wo
-    hit = None
+    plan = None
     if plan_transfer.mode() != 'only':
-        hit = (_table().get(key + '_st') if stats else None) or _table().get(key)
-    if hit is None and not _tuning() and plan_transfer.mode() != 'off':
+        plan = from_entry((_table().get(key + '_st') if stats else None) or _table().get(key))
+    if plan is None and not _tuning() and plan_transfer.mode() != 'off':
         # another --img_size / batch: the row of the nearest tuned shape of the family, re-derived for this M (plan_transfer.py);
         # with fused statistics the `_st` family competes with the plain one, the donor nearer in M wins
         only = plan_transfer.mode() == 'only'
@@ -101,52 +101,44 @@ def _configure_conv(d, key, stats=False):
                   for nb in [plan_transfer.nearest(_table(), k, only)] if nb is not None]
         if donors:
             k = min(donors)[2]
-            hit, _ = plan_transfer.lookup(_table(), k, M_rows, d.Cout, d.k_pad // 32, d.nseg)
-            if hit is not None and stats and k == key and len(hit) > 4 and 42 <= hit[4] <= 48:
-                hit = list(hit[:7])
-                hit[4] = 22 if hit[4] == 42 else 23     # the persistent walker does not cover launches with fused BatchNorm sums
-    if hit is None and _tuning():
+            plan = from_entry(plan_transfer.lookup(_table(), k, M_rows, d.Cout, d.k_pad // 32, d.nseg)[0])
+            if plan is not None and stats and k == key:
+                plan = plan.with_bn_sums()
+    if plan is None and _tuning():
         M, nkt = d.B * d.Ho * d.Wo, d.k_pad // 32
         big = scratch(torch.device('cuda', torch.cuda.current_device()), 1 << 28)
         d.tile_counters = _tile_counters(torch.device('cuda', torch.cuda.current_device()))
-        cands = [((0, 0), 0, 0, 0, (0, 0))]
+        cands = [ConvPlan()]
         for tm, tn in ((128, 128), (128, 64), (64, 128), (64, 64)):
             wgs = -(-M // tm) * -(-d.Cout // tn)
             for ks in (1, 2, 3, 4, 6, 8, 12, 16):
                 if ks > 1 and (wgs >= 1024 or ks * 2 > nkt or wgs * ks > 8192):
                     continue
-                cands.append(((tm, tn), ks, 0, 2, (0, 0)))
-                cands.append(((tm, tn), ks, 0, 22, (0, 0)))         # direct-to-LDS staging
+                cands.append(ConvPlan(tm, tn, ks, 0, 2))
+                cands.append(ConvPlan(tm, tn, ks, 0, 22))         # direct-to-LDS staging
                 if (tm, tn) == (64, 64) and nkt // ks >= 3:
-                    cands.append(((tm, tn), ks, 0, 3, (0, 0)))
-                    cands.append(((tm, tn), ks, 0, 23, (0, 0)))
+                    cands.append(ConvPlan(tm, tn, ks, 0, 3))
+                    cands.append(ConvPlan(tm, tn, ks, 0, 23))
             if 256 < wgs <= hip.TILE_COUNTERS:          # split the last partial round of tiles (ym_conv_desc.tail_tiles)
                 for r in sorted({wgs % 256, wgs % 512} - {0}):
                     for ts in (2, 3, 4, 6, 8):
                         if ts * 2 <= nkt and r * ts <= 2048:
-                            cands.append(((tm, tn), 1, 0, 2, (r, ts)))
-                            cands.append(((tm, tn), 1, 0, 22, (r, ts)))
-        best = (1e30, (0, 0), 0, 0, 0, (0, 0))
-        for tile, ks, kwv, stg, tail in cands:
-            d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = tile[0], tile[1], ks, kwv, stg
-            d.tail_tiles, d.tail_ksplit = tail
+                            cands.append(ConvPlan(tm, tn, 1, 0, 2, r, ts))
+                            cands.append(ConvPlan(tm, tn, 1, 0, 22, r, ts))
+        best, plan = 1e30, ConvPlan()
+        for cand in cands:
+            cand.apply(d)
             if hip.conv_workspace_bytes(d) > big.numel():
                 continue
             try:
                 t = _time_launch(lambda: hip.conv2d_fwd(d, big))
             except RuntimeError:
                 continue
-            if t < best[0] * 0.98:
-                best = (t, tile, ks, kwv, stg, tail)
-        hit = [best[1][0], best[1][1], best[2], best[3], best[4], best[5][0], best[5][1]]
-        _remember(key, hit)
-    if hit is not None:
-        d.tile_m, d.tile_n, d.ksplit = hit[0], hit[1], hit[2]
-        d.kwaves = hit[3] if len(hit) > 3 else 0
-        d.stages = hit[4] if len(hit) > 4 else 0
-        d.tail_tiles, d.tail_ksplit = (hit[5], hit[6]) if len(hit) > 6 else (0, 0)
-        from .engine import _grid_wgs
-        d.grid_wgs = _grid_wgs(hit)                             # persistent kernel (stages 4x): workgroups launched
+            if t < best * 0.98:
+                best, plan = t, cand
+        _remember(key, plan.to_row())
+    if plan is not None:
+        plan.apply(d)
     force = os.environ.get('YM_FORCE_STAGES')        # experiments / tests: e.g. 43 = every conv the persistent kernel covers runs on it
     if force:
         d.tile_m, d.tile_n, d.kwaves, d.stages, d.grid_wgs = 64, 64, 0, int(force), int(os.environ.get('YM_FORCE_GRID', '0'))
@@ -157,27 +149,22 @@ def _configure_conv(d, key, stats=False):
         # opt-in FAST training mode (YM_TRAIN_MMA=3): forward and data-gradient convs on the bf16 MFMA (split-bf16 products, see
         # ym_conv_desc.mma).  NOT the parity mode: per-product error ~2^-17 instead of 2^-24, which the ill-conditioned backward of
         # a random-init net amplifies beyond the fp32 reference's own noise (tests keep the default, f32).
-        hit3 = _table().get(key + f'_mma{mma}')
-        if hit3 is not None:
-            d.tile_m, d.tile_n, d.ksplit, d.kwaves = hit3[0], hit3[1], hit3[2], (hit3[3] if len(hit3) > 3 else 0)
-            d.tail_tiles, d.tail_ksplit = (hit3[5], hit3[6]) if len(hit3) > 6 else (0, 0)
+        plan = from_entry(_table().get(key + f'_mma{mma}'))
+        if plan is not None:            # (tile, K split, K waves and tail: the staging and grid of the f32 choice stay)
+            plan._replace(stages=d.stages, grid_wgs=d.grid_wgs).apply(d)
         if d.kwaves == 0:
             d.mma, d.stages = mma, 0
 
 
-_MSPLIT_SCALE = float(os.environ.get('YM_WGRAD_MSPLIT_SCALE', '1'))
-
-
 def _configure_wgrad(d, key):
-    from . import plan_transfer
-    hit = _table().get(key) if plan_transfer.mode() != 'only' else None
-    if hit is None and not _tuning():
+    plan = from_entry(_table().get(key), WgradPlan) if plan_transfer.mode() != 'only' else None
+    if plan is None and not _tuning():
         p = plan_transfer.parse(key)
         if p:
-            hit, _ = plan_transfer.lookup(_table(), key, p[1], p[2], 0)
-    if hit is None and _tuning():
+            plan = from_entry(plan_transfer.lookup(_table(), key, p[1], p[2], 0)[0], WgradPlan)
+    if plan is None and _tuning():
         big = scratch(torch.device('cuda', torch.cuda.current_device()), 1 << 28)
-        best = (1e30, 0, 2)
+        best, plan = 1e30, WgradPlan(0, 2)
         tbn = 64 if d.Cout_real <= 64 else 128
         tiles = -(-d.Cout // tbn) * -(-(d.KH * d.KW * d.Cin) // 128)
         # (22 / 23 / 24: the DMA rings; layers with <= 64 output channels have the 32-pixel ring only, at 48 KB = 3 workgroups per CU)
@@ -188,21 +175,17 @@ def _configure_wgrad(d, key):
             half = slots // 2
             fill = {max(1, round(half * j / tiles)) for j in (1, 2, 3, 4, 6, 8, 12, 16)} | {max(1, (half * j) // tiles) for j in (2, 4, 6, 8)}
             for ms in sorted({0, 1, 2, 4, 8, 16, 32, 64, 128, 256} | {m_ for m_ in fill if m_ <= 256}):
-                d.msplit, d.lds_buffers = ms, nb
+                WgradPlan(ms, nb).apply(d)
                 need = hip.lib().ym_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
                 if need == 0 or need > big.numel():
                     continue
                 t = _time_launch(lambda: hip.check(hip.lib().ym_conv2d_wgrad(ctypes.byref(d), ctypes.c_void_p(big.data_ptr()),
                                                                             big.numel(), hip.stream_ptr()), 'wgrad'))
-                if t < best[0] * 0.98:
-                    best = (t, ms, nb)
-        hit = [best[1], best[2]]
-        _remember(key, hit)
-    if hit is not None:
-        d.msplit = hit[0]
-        d.lds_buffers = hit[1] if len(hit) > 1 else 2
-        if _MSPLIT_SCALE != 1.0 and d.msplit > 1:    # experiment knob: the table was tuned with the chip to itself
-            d.msplit = max(1, int(round(d.msplit * _MSPLIT_SCALE)))
+                if t < best * 0.98:
+                    best, plan = t, WgradPlan(ms, nb)
+        _remember(key, plan.to_row())
+    if plan is not None:
+        plan.apply(d)
 
 
 def dump_new_entries(path):
