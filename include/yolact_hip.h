@@ -535,6 +535,45 @@ int ym_after_nms_batch(const float* proto, const float* coefs, float* boxes, con
                        int Wp, int K, int img_h, int img_w, int do_crop, float* masks, int32_t* boxes_px, void* workspace,
                        size_t workspace_bytes, ym_stream_t s);
 
+/* draw_img (utils/output_utils.py:327-369) on the device: masks blended with the class palette, box outlines, label plates, label
+ * text, the fps overlay and the cutout matte, for B frames in the padded layout of ym_after_nms_batch.  Everything is integer
+ * arithmetic, so the result is exact:
+ *   masks (unless YM_DRAW_HIDE_MASK): s = (sum_i int(masks[i]) * (ids[i] + 1)) mod (num_classes - 1), every pixel becomes
+ *     (4 * palette[s] + 6 * img + 5) / 10  ==  cv2.addWeighted(colour, 0.4, img, 0.6, 0);
+ *   boxes (unless YM_DRAW_HIDE_BBOX): per pixel the smallest i that touches it wins (the reference draws i = n-1 .. 0): the 1-px
+ *     outline through (x1,y1)-(x2,y2), the filled plate x1..x1+text_w, y1..y1+text_h+5 (inclusive) in palette[ids[i] + 1], the
+ *     label "{name}: {score:.2f}" ("{name}" with YM_DRAW_HIDE_SCORE) in white with its baseline at (x1, y1 + 15);
+ *   YM_DRAW_REAL_TIME: pixels y < text_h + 8, x < text_w + 8 become 3 * v / 5, then fps_text in white, baseline (0, text_h + 2);
+ *   cutout_total (optional, [B][H][W][3]): img where s != 0, else 255.
+ * Text uses the caller's 1-bit fixed-cell font: uint16 font[95][YM_DRAW_FONT_HEIGHT], codes 0x20..0x7E, bit x of a row = column x of
+ * the YM_DRAW_FONT_ADVANCE wide cell; text_w = len * YM_DRAW_FONT_ADVANCE, text_h = YM_DRAW_FONT_HEIGHT.  The score text is
+ * formatted on the device: cents = rint(double(score) * 100), round-half-to-even, i.e. Python's format.
+ * img / out uint8 [B][H][W][3] BGR (out may be img); masks f32 [B][max_det][H][W] holding 0 / 1; ids int64, scores f32,
+ * boxes_px int32 x4 [B][max_det]; counts int32[B] on the DEVICE (NULL = all max_det rows valid; B = 1 with max_det = n is the
+ * single-picture call).  Rows past the count, and rows with score < visual_thre when visual_thre > 0, are skipped on the device; a
+ * frame without a surviving row is copied unchanged.  palette uint8 [palette_n][3]; names char [num_names][YM_DRAW_NAME_STRIDE],
+ * NUL-padded; labels are cut at YM_DRAW_LABEL_MAX characters.  fps_text is a HOST string (<= 32 characters).  No host
+ * synchronisation, no device-to-host copy.  workspace >= ym_draw_workspace_bytes(B, max_det), max_det <= YM_DRAW_MAX_DET. */
+#define YM_DRAW_HIDE_MASK 1
+#define YM_DRAW_HIDE_BBOX 2
+#define YM_DRAW_HIDE_SCORE 4
+#define YM_DRAW_REAL_TIME 8
+#define YM_DRAW_FONT_ADVANCE 12
+#define YM_DRAW_FONT_HEIGHT 14
+#define YM_DRAW_NAME_STRIDE 40
+#define YM_DRAW_LABEL_MAX 44
+#define YM_DRAW_MAX_DET 512
+size_t ym_draw_workspace_bytes(int B, int max_det);
+int ym_draw_detections_batch(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores, const int32_t* boxes_px,
+                             const int32_t* counts, int B, int max_det, int H, int W, const uint8_t* palette, int palette_n,
+                             int num_classes, const char* names, int num_names, const uint16_t* font, int flags, float visual_thre,
+                             const char* fps_text, uint8_t* out, uint8_t* cutout_total, void* workspace, size_t workspace_bytes,
+                             ym_stream_t s);
+
+/* The per-object mattes of cfg.cutout: out[i] = img where masks[i] != 0, else 255; img uint8 [H][W][3], masks f32 [n][H][W],
+ * out uint8 [n][H][W][3] (full frames: the caller slices [y1:y2, x1:x2]). */
+int ym_draw_cutout_objects(const uint8_t* img, const float* masks, int n, int H, int W, uint8_t* out, ym_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,9 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('YM_LIB_PATH') or os.path.join(_PKG, 'libyolact_hip.so')   # override: debug builds only
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU = 0, 1, 2, 3
+# YM_DRAW_* of include/yolact_hip.h (tests/test_draw_cpu.py compares them with the header)
+DRAW_HIDE_MASK, DRAW_HIDE_BBOX, DRAW_HIDE_SCORE, DRAW_REAL_TIME = 1, 2, 4, 8
+DRAW_FONT_ADVANCE, DRAW_FONT_HEIGHT, DRAW_NAME_STRIDE, DRAW_LABEL_MAX, DRAW_MAX_DET = 12, 14, 40, 44, 512
 
 # every symbol include/yolact_hip.h declares (checked by tests/test_abi.py without a GPU)
 ABI_SYMBOLS = (
@@ -31,6 +34,7 @@ ABI_SYMBOLS = (
     'ym_swin_window_attention_bwd', 'ym_adamw_step', 'ym_drop_path_add', 'ym_drop_path_bwd', 'ym_select_positives',
     'ym_match_anchors', 'ym_match_anchors_batch', 'ym_loss_workspace_bytes', 'ym_class_box_loss', 'ym_semantic_loss',
     'ym_semantic_loss_batch',
+    'ym_draw_workspace_bytes', 'ym_draw_detections_batch', 'ym_draw_cutout_objects',
     'ym_bn_train_bwd_workspace_bytes', 'ym_bn_train_bwd', 'ym_bn_train_bwd_apply', 'ym_act_bias_bwd', 'ym_conv2d_fuses_bn_stats', 'ym_bn_train_fwd_stats', 'ym_maxpool3x3s2_bwd', 'ym_maxpool3x3s2_fwd_idx', 'ym_maxpool3x3s2_bwd_idx', 'ym_bilinear2x_bwd', 'ym_sgd_step',
 )
 
@@ -207,12 +211,17 @@ def lib():
         L.ym_maxpool3x3s2_bwd_idx.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
         L.ym_bilinear2x_bwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
         L.ym_sgd_step.argtypes = [vp, vp, vp, i64, f32, f32, f32, i32, vp]
+        L.ym_draw_workspace_bytes.argtypes = [i32, i32]
+        L.ym_draw_workspace_bytes.restype = sz
+        L.ym_draw_detections_batch.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp, i32, f32,
+                                               ctypes.c_char_p, vp, vp, vp, sz, vp]
+        L.ym_draw_cutout_objects.argtypes = [vp, vp, i32, i32, i32, vp, vp]
         for name in ABI_SYMBOLS:
             fn = getattr(L, name)
             if name not in ('ym_last_error', 'ym_conv2d_workspace_bytes', 'ym_nms_workspace_bytes',
                             'ym_greedy_nms_workspace_bytes', 'ym_conv2d_wgrad_workspace_bytes',
                             'ym_sizeof_conv_desc', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
-                            'ym_ann_to_mask_workspace_bytes'):
+                            'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

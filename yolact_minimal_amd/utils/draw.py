@@ -1,0 +1,188 @@
+"""`draw_img` with the reference's signature, rendered on the device (csrc/draw.hip).
+
+Reference: `utils/output_utils.py:327-369`.  The reference starts by downloading all `n x img_h x img_w` float32 masks and draws
+with cv2 on the host; here the masks, ids, scores and boxes stay where `after_nms` left them and only the finished frame
+(`img_h x img_w x 3` bytes) comes back — or nothing at all when the frame is a device tensor.
+
+    draw_img(ids_p, class_p, box_p, mask_p, img_origin, cfg, img_name=None, fps=None) -> frame
+        `img_origin`: numpy uint8 [H, W, 3] BGR (one upload, one download, a numpy array comes back, so cv2.imwrite /
+        VideoWriter.write work unchanged) or a device uint8 tensor (a device tensor comes back, nothing crosses PCIe).
+        `ids_p is None` returns `img_origin` itself, like the reference.
+    cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg) -> (total, [obj_0, ...])      what cfg.cutout writes to disk
+    draw_batch(dets_padded, imgs, cfg, fps=None) -> uint8 [B, H, W, 3]
+        for `after_nms_batch(..., sync=False)`: counts, scores and cfg.visual_thre are consumed on the device, no host read.
+
+Mask colours, blend, outline / plate geometry, draw order and the score formatting are the reference's, exactly (integer arithmetic
+throughout).  The label PIXELS are this package's own fixed-cell bitmap font (`utils/font.py`), not cv2's anti-aliased Hershey Duplex.
+The detections must be device tensors; there is no CPU path.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import hip
+from ..config import COLORS
+from . import font as _font
+
+_res_cache = {}
+
+
+def _flag(cfg, name):
+    return bool(getattr(cfg, name, False))
+
+
+def _resources(device, cfg):
+    """Palette, class-name table and font on `device`: uploaded once per (device, class names) and kept."""
+    names = tuple(cfg.class_names)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), names)
+    res = _res_cache.get(key)
+    if res is None:
+        assert (_font.ADVANCE, _font.HEIGHT) == (hip.DRAW_FONT_ADVANCE, hip.DRAW_FONT_HEIGHT)
+        table = np.zeros((max(len(names), 1), hip.DRAW_NAME_STRIDE), dtype=np.uint8)
+        for k, name in enumerate(names):
+            raw = _font.sanitize(str(name))[:hip.DRAW_NAME_STRIDE - 1].encode('ascii')
+            table[k, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+        palette = np.ascontiguousarray(np.asarray(COLORS), dtype=np.uint8)
+        res = _res_cache[key] = dict(
+            palette=torch.from_numpy(palette).to(device), palette_n=palette.shape[0],
+            names=torch.from_numpy(table).to(device), num_names=len(names),
+            font=torch.from_numpy(_font.FONT.astype(np.int16)).to(device))          # bit patterns of the uint16 rows
+    return res
+
+
+def _flags(cfg):
+    return ((hip.DRAW_HIDE_MASK if _flag(cfg, 'hide_mask') else 0) | (hip.DRAW_HIDE_BBOX if _flag(cfg, 'hide_bbox') else 0) |
+            (hip.DRAW_HIDE_SCORE if _flag(cfg, 'hide_score') else 0) | (hip.DRAW_REAL_TIME if _flag(cfg, 'real_time') else 0))
+
+
+def _launch(imgs, masks, ids, scores, boxes, counts, batch, max_det, cfg, flags, visual_thre, fps, out, cutout_total):
+    from .output_utils import _scratch
+    device = imgs.device
+    _, h, w, _ = imgs.shape
+    res = _resources(device, cfg)
+    fps_text = None
+    if flags & hip.DRAW_REAL_TIME:
+        if fps is None:
+            raise RuntimeError('draw_img: cfg.real_time needs the fps value')
+        fps_text = f'fps: {fps:.2f}'.encode('ascii', 'replace')
+    L = hip.lib()
+    with torch.cuda.device(device):
+        nbytes = L.ym_draw_workspace_bytes(batch, max_det)
+        if nbytes == 0:
+            raise RuntimeError('ym_draw_workspace_bytes: ' + L.ym_last_error().decode())
+        ws = _scratch(device, nbytes)
+        hip.check(L.ym_draw_detections_batch(
+            hip.ptr(imgs, torch.uint8), hip.ptr(masks) if masks is not None else None, hip.ptr(ids, torch.int64),
+            hip.ptr(scores) if scores is not None else None, hip.ptr(boxes, torch.int32),
+            hip.ptr(counts, torch.int32) if counts is not None else None, batch, max_det, h, w,
+            hip.ptr(res['palette'], torch.uint8), res['palette_n'], int(cfg.num_classes), hip.ptr(res['names'], torch.uint8),
+            res['num_names'], hip.ptr(res['font'], torch.int16), flags, float(visual_thre), fps_text,
+            hip.ptr(out, torch.uint8), hip.ptr(cutout_total, torch.uint8) if cutout_total is not None else None,
+            ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()), 'ym_draw_detections_batch')
+
+
+def _device_of(ids_p, what):
+    if not torch.is_tensor(ids_p) or not ids_p.is_cuda:
+        raise RuntimeError(f'yolact_minimal_amd.utils.draw.{what} needs the detections as CUDA (HIP) tensors, as after_nms returns '
+                           f'them; there is no CPU path.')
+    return ids_p.device
+
+
+def _frame_on(img_origin, device):
+    """-> (uint8 [1, H, W, 3] on `device`, came_from_numpy)"""
+    if isinstance(img_origin, np.ndarray):
+        if img_origin.dtype != np.uint8 or img_origin.ndim != 3 or img_origin.shape[2] != 3:
+            raise RuntimeError(f'draw_img: expected a uint8 [H, W, 3] frame, got {img_origin.dtype} {img_origin.shape}')
+        return torch.from_numpy(np.ascontiguousarray(img_origin)).to(device)[None], True
+    if not torch.is_tensor(img_origin) or not img_origin.is_cuda or img_origin.dtype != torch.uint8 or img_origin.dim() != 3 or \
+            img_origin.shape[2] != 3:
+        raise RuntimeError('draw_img: the frame is a numpy uint8 [H, W, 3] array or a uint8 [H, W, 3] tensor on the device')
+    if img_origin.device != device:
+        raise RuntimeError(f'draw_img: frame on {img_origin.device}, detections on {device}')
+    return img_origin.contiguous()[None], False
+
+
+def _single_inputs(ids_p, class_p, box_p, mask_p, frame, need_masks, need_scores):
+    n = ids_p.shape[0]
+    if n > hip.DRAW_MAX_DET:
+        raise RuntimeError(f'draw_img: {n} detections, at most {hip.DRAW_MAX_DET} are drawn')
+    _, h, w, _ = frame.shape
+    masks = None
+    if need_masks:
+        if mask_p is None or tuple(mask_p.shape) != (n, h, w):
+            raise RuntimeError(f'draw_img: masks {None if mask_p is None else tuple(mask_p.shape)} do not fit {n} detections on a '
+                               f'{h} x {w} frame')
+        masks = mask_p.contiguous()
+    if tuple(box_p.shape) != (n, 4):
+        raise RuntimeError(f'draw_img: boxes {tuple(box_p.shape)} for {n} detections')
+    scores = class_p.contiguous() if need_scores else None
+    return n, masks, ids_p.contiguous(), scores, box_p.contiguous()
+
+
+def draw_img(ids_p, class_p, box_p, mask_p, img_origin, cfg, img_name=None, fps=None):
+    if ids_p is None:
+        return img_origin
+    device = _device_of(ids_p, 'draw_img')
+    frame, from_numpy = _frame_on(img_origin, device)
+    flags = _flags(cfg)
+    n, masks, ids, scores, boxes = _single_inputs(ids_p, class_p, box_p, mask_p, frame, not flags & hip.DRAW_HIDE_MASK,
+                                                  not flags & hip.DRAW_HIDE_SCORE)
+    out = torch.empty_like(frame)
+    _launch(frame, masks, ids, scores, boxes, None, 1, n, cfg, flags, 0.0, fps, out, None)
+    return out[0].cpu().numpy() if from_numpy else out[0]
+
+
+def cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg):
+    """What the reference's `cfg.cutout` branch writes (`utils/output_utils.py:346-358`), as arrays: `total` = the frame where any
+    mask colour is drawn (class sum modulo != 0) and 255 elsewhere; `objs[i]` = (frame where masks[i] != 0 else 255)[y1:y2, x1:x2]
+    with Python's slice rules.  numpy frame in -> numpy arrays out, device frame in -> device tensors out.  Reads the boxes on the
+    host (the slice bounds).  `(None, [])` without detections."""
+    if ids_p is None:
+        return None, []
+    if _flag(cfg, 'hide_mask'):
+        raise RuntimeError('cutout_mattes: cfg.cutout needs the masks (cfg.hide_mask is set)')
+    device = _device_of(ids_p, 'cutout_mattes')
+    frame, from_numpy = _frame_on(img_origin, device)
+    n, masks, ids, _, boxes = _single_inputs(ids_p, None, box_p, mask_p, frame, True, False)
+    _, h, w, _ = frame.shape
+    total = torch.empty_like(frame)
+    _launch(frame, masks, ids, None, boxes, None, 1, n, cfg, hip.DRAW_HIDE_BBOX | hip.DRAW_HIDE_SCORE, 0.0, None,
+            torch.empty_like(frame), total)
+    objs = []
+    if n:
+        full = torch.empty(n, h, w, 3, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            hip.check(hip.lib().ym_draw_cutout_objects(hip.ptr(frame, torch.uint8), hip.ptr(masks), n, h, w, hip.ptr(full, torch.uint8),
+                                                       hip.stream_ptr()), 'ym_draw_cutout_objects')
+        for i, (x1, y1, x2, y2) in enumerate(boxes.tolist()):
+            objs.append(full[i][y1:y2, x1:x2, :])
+    if from_numpy:
+        return total[0].cpu().numpy(), [o.cpu().numpy() for o in objs]
+    return total[0], objs
+
+
+def draw_batch(dets_padded, imgs, cfg, fps=None):
+    """Render B frames from `after_nms_batch(dets, img_h, img_w, cfg, sync=False)` = (ids, scores, boxes_px, masks, counts), all
+    padded to max_detections rows, in one launch set.  `imgs` is a device uint8 [B, H, W, 3] tensor; so is the result.  Frame b
+    equals `draw_img` on `after_nms`'s result for image b: rows past counts[b] and rows under cfg.visual_thre are dropped ON THE
+    DEVICE, a frame left without detections comes back unchanged.  No host synchronisation and no device-to-host copy (the palette /
+    class-name / font tables are uploaded by the first call for a (device, class names) pair)."""
+    ids, scores, boxes, masks, counts = dets_padded
+    device = _device_of(ids, 'draw_batch')
+    if not torch.is_tensor(imgs) or not imgs.is_cuda or imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3 or \
+            imgs.device != device:
+        raise RuntimeError('draw_batch: imgs is a uint8 [B, H, W, 3] tensor on the device of the detections')
+    batch, max_det = ids.shape
+    _, h, w, _ = imgs.shape
+    if imgs.shape[0] != batch or max_det > hip.DRAW_MAX_DET:
+        raise RuntimeError(f'draw_batch: {imgs.shape[0]} frames for {batch} detection sets of {max_det} rows (at most {hip.DRAW_MAX_DET})')
+    flags = _flags(cfg)
+    need_masks = not flags & hip.DRAW_HIDE_MASK
+    if need_masks and tuple(masks.shape) != (batch, max_det, h, w):
+        raise RuntimeError(f'draw_batch: masks {tuple(masks.shape)} do not fit [{batch}, {max_det}, {h}, {w}]')
+    out = torch.empty_like(imgs, memory_format=torch.contiguous_format)
+    _launch(imgs.contiguous(), masks.contiguous() if need_masks else None, ids.contiguous(), scores.contiguous(), boxes.contiguous(),
+            counts.contiguous() if counts is not None else None, batch, max_det, cfg, flags,
+            float(getattr(cfg, 'visual_thre', 0) or 0), fps, out, None)
+    return out

@@ -12,6 +12,8 @@ Same call shapes and return conventions:
       `box_p` is scaled IN PLACE like the reference (:230).
 The only host<->device synchronisation is one 4-byte read of the detection count at the end of `nms`
 (the reference's boolean-mask gathers synchronise several times per call).
+
+`draw_img` (`:327-369`), `draw_batch` and `cutout_mattes` are the device renderer of `utils/draw.py`, re-exported here.
 """
 import ctypes
 import os
@@ -240,3 +242,6 @@ def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True):
             r = tuple(t[keep] for t in r) if bool(keep.any()) else (None, None, None, None)
         out.append(r)
     return out
+
+
+from .draw import draw_img, draw_batch, cutout_mattes  # noqa: E402,F401  (the device renderer; it imports _scratch from here lazily)
