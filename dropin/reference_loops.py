@@ -108,12 +108,14 @@ def train_loop(net, optimizer, cfg, data_loader, start_step=0, max_steps=None, o
 IOU_THRES = [x / 100 for x in range(50, 100, 5)]                              # eval.py:24
 
 
-def eval_loop(net, cfg, data_loader, image_ids=None, coco_api=False, make_json=None, sync_stages=True):
+def eval_loop(net, cfg, data_loader, image_ids=None, coco_api=False, make_json=None, sync_stages=True, packed_masks=False):
     """eval.py:35-69 for every `(img, gt, gt_masks, img_h, img_w)` of `data_loader`, one image at a time.  `coco_api`: the
     `--coco_api` branch (eval.py:60-67: boxes and the dense fp32 masks cross PCIe, `MakeJson.add_bbox/add_mask`; 'device' = the
     same records with the RLE strings made on the GPU); otherwise
     `prep_metrics` on the device tensors (eval.py:69).  `sync_stages`: the reference's `timer.counter` fences every stage with a
     device synchronize (utils/timer.py:63-76); False leaves the fences out (the loop is otherwise unchanged).
+    `packed_masks`: `after_nms(..., packed=True)` — the masks are a `PackedMasks` (1 bit per pixel) in all three branches; for
+    `coco_api=True` the host masks come from `PackedMasks.numpy()` (the words cross PCIe, numpy unpacks them).
     Returns (ap_data, make_json, images with detections, seconds)."""
     ap_data = {'box': [[APDataObject() for _ in cfg.class_names] for _ in IOU_THRES],
                'mask': [[APDataObject() for _ in cfg.class_names] for _ in IOU_THRES]}
@@ -136,7 +138,10 @@ def eval_loop(net, cfg, data_loader, image_ids=None, coco_api=False, make_json=N
             ids_p, class_p, box_p, coef_p, proto_p = nms(class_p, box_p, coef_p, proto_p, net.anchors, cfg)
 
         with counter('after_nms'):
-            ids_p, class_p, boxes_p, masks_p = after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w)
+            if packed_masks:
+                ids_p, class_p, boxes_p, masks_p = after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, packed=True)
+            else:
+                ids_p, class_p, boxes_p, masks_p = after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w)
             if ids_p is None:
                 continue
 
@@ -156,7 +161,7 @@ def eval_loop(net, cfg, data_loader, image_ids=None, coco_api=False, make_json=N
                         make_json.add_mask(image_id, ids_p[j], rles[j], class_p[j])
             elif coco_api:
                 boxes_p = boxes_p.cpu().numpy()
-                masks_p = masks_p.cpu().numpy()
+                masks_p = masks_p.numpy() if packed_masks else masks_p.cpu().numpy()
 
                 for j in range(masks_p.shape[0]):
                     if (boxes_p[j, 3] - boxes_p[j, 1]) * (boxes_p[j, 2] - boxes_p[j, 0]) > 0:

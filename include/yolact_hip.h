@@ -574,6 +574,42 @@ int ym_draw_detections_batch(const uint8_t* img, const float* masks, const int64
  * out uint8 [n][H][W][3] (full frames: the caller slices [y1:y2, x1:x2]). */
 int ym_draw_cutout_objects(const uint8_t* img, const float* masks, int n, int H, int W, uint8_t* out, ym_stream_t s);
 
+
+/* ---- bit-packed instance masks --------------------------------------------------------------------------------------------
+ * Every consumer of a detection mask asks one question of a pixel (0 or 1), so the masks can travel as 1 bit per pixel:
+ *   bits: uint64 [n][H][Wq], Wq = ceil(W / 64), contiguous.  Bit k (LSB = 0) of word j of row y of mask i is pixel (y, 64*j + k);
+ *   bits at x >= W are ZERO (producers guarantee it, consumers rely on it).  In the padded batch form [B][max_det][H][Wq] the rows
+ *   at or past an image's count are unspecified, like the dense tensor's.
+ * 100 x 480 x 640 masks are 3.84 MB instead of 122.88 MB.  One wave-wide ballot over 64 consecutive pixels is one word.
+ * Host view (little-endian): numpy.unpackbits(bits.view(uint8).reshape(n, H, Wq * 8), axis=-1, bitorder='little')[..., :W].
+ *
+ * ym_after_nms_batch_packed: ym_after_nms_batch with the masks written as bits.  Per pixel the arithmetic is the dense kernel's
+ * (same patch, same source coordinates, same interpolation expression), so a bit equals (dense value != 0) exactly; the dense
+ * tensor exists nowhere, not in the workspace either.  Same workspace as ym_after_nms_batch (ym_after_nms_batch_workspace_bytes:
+ * the soft masks of the strongly down-scaled case). */
+int ym_after_nms_batch_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
+                              int Wp, int K, int img_h, int img_w, int do_crop, uint64_t* mask_bits, int32_t* boxes_px,
+                              void* workspace, size_t workspace_bytes, ym_stream_t s);
+/* dense masks [n][H][W] (float32, or uint8 when is_u8; nonzero = foreground) -> bits, and bits -> float32 0.0 / 1.0. */
+int ym_pack_masks(const void* masks, int is_u8, int n, int H, int W, uint64_t* bits, ym_stream_t s);
+int ym_unpack_masks(const uint64_t* bits, int n, int H, int W, float* masks, ym_stream_t s);
+/* ym_mask_iou on bit rows: bits_a [n][words], bits_b [g][words], words = H * Wq < 2^18.  Exact integers through the same
+ * finalize step, so bit-identical to ym_mask_iou on the dense masks (0/0 -> NaN). */
+size_t ym_mask_iou_packed_workspace_bytes(int n, int g, int64_t words);
+int ym_mask_iou_packed(const uint64_t* bits_a, int n, const uint64_t* bits_b, int g, int64_t words, float* iou, void* workspace,
+                       size_t workspace_bytes, ym_stream_t s);
+/* ym_rle_encode from bits [n][H][Wq]: same outputs, same "buffers too small" protocol. */
+int ym_rle_encode_packed(const uint64_t* bits, int n, int H, int W, uint32_t* counts, int cap_runs, int32_t* nruns, uint8_t* str,
+                         int cap_str, int32_t* str_len, void* workspace, size_t workspace_bytes, ym_stream_t s);
+/* ym_draw_detections_batch / ym_draw_cutout_objects with the mask term read from bits [B][max_det][H][Wq] / [n][H][Wq]: output
+ * bytes identical to the dense calls. */
+int ym_draw_detections_batch_packed(const uint8_t* img, const uint64_t* mask_bits, const int64_t* ids, const float* scores,
+                                    const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
+                                    const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
+                                    const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
+                                    uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s);
+int ym_draw_cutout_objects_packed(const uint8_t* img, const uint64_t* mask_bits, int n, int H, int W, uint8_t* out, ym_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

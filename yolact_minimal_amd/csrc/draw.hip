@@ -9,6 +9,8 @@
 //                   12 output bytes leave as three dword stores.  Bound by the n*H*W*4 mask bytes it reads.
 //                   The <false> instance is the element-wise path for rows whose width is not a multiple of 4 (or unaligned bases).
 //  k_cutout_object: per-detection matte (img where mask != 0 else 255), full frame; the caller slices the box window.
+//  k_draw_frame<VEC, true> / k_cutout_object_packed: the mask term read from bit-packed masks (one 8-byte word serves 64 pixels
+//                   of a detection), same bytes out.
 // All arithmetic is integer; results are exact (tests compare with tolerance 0).
 #include "ym_common.h"
 
@@ -204,8 +206,28 @@ __device__ __forceinline__ void mask_batch(const int* recs, const float* mp, siz
         for (int k = 0; k < 4; ++k) s[k] += (int)m[u][k] * w[u];
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __restrict__ img, const float* __restrict__ masks,
+// The same for bit-packed masks (include/yolact_hip.h "bit-packed instance masks"): `bp` points at the word of detection slot 0 that
+// holds this thread's 4 pixels (4 | 64: never two words), `sh` is their bit offset.  A wave's 256 pixels lie in at most 5 words
+// per detection, so these are broadcast loads.
+template <int U>
+__device__ __forceinline__ void bits_batch(const int* recs, const unsigned long long* bp, size_t HWq, int sh, int (&s)[4]) {
+    unsigned long long m[U];
+    int w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        w[u] = recs[u * REC + R_ID] + 1;
+        m[u] = bp[(size_t)recs[u * REC + R_SRC] * HWq];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const unsigned nib = (unsigned)(m[u] >> sh);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] += (int)((nib >> k) & 1u) * w[u];
+    }
+}
+
+template <bool VEC, bool PACKED>
+__global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __restrict__ img, const void* __restrict__ masks_v,
                                                               const int* __restrict__ ws, int max_det, int H, int W,
                                                               const uint8_t* __restrict__ palette, int palette_n, int modulus,
                                                               const uint16_t* __restrict__ font, int flags, uint8_t* out,
@@ -257,10 +279,18 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __r
 
     if (!(flags & YM_DRAW_HIDE_MASK)) {
         int s[4] = {0, 0, 0, 0};
-        const size_t HW = (size_t)H * W;
-        const float* mp = masks + (size_t)b * max_det * HW + (size_t)y * W + x0;
         int i = 0;
-        if (VEC) {
+        if (PACKED) {
+            const int wq = (W + 63) >> 6, sh = x0 & 63;
+            const size_t HWq = (size_t)H * wq;
+            const unsigned long long* bp = static_cast<const unsigned long long*>(masks_v) + (size_t)b * max_det * HWq + (size_t)y * wq + (x0 >> 6);
+            for (; i + 16 <= n; i += 16) bits_batch<16>(recs + i * REC, bp, HWq, sh, s);
+            for (; i + 4 <= n; i += 4) bits_batch<4>(recs + i * REC, bp, HWq, sh, s);
+            for (; i < n; ++i) bits_batch<1>(recs + i * REC, bp, HWq, sh, s);
+        }
+        const size_t HW = (size_t)H * W;
+        const float* mp = static_cast<const float*>(masks_v) + (size_t)b * max_det * HW + (size_t)y * W + x0;
+        if (VEC && !PACKED) {
             for (; i + 16 <= n; i += 16) mask_batch<16>(recs + i * REC, mp, HW, s);
             for (; i + 4 <= n; i += 4) mask_batch<4>(recs + i * REC, mp, HW, s);
         }
@@ -338,6 +368,17 @@ __global__ __launch_bounds__(256) void k_cutout_object(const uint8_t* __restrict
     for (int c = 0; c < 3; ++c) out[o * 3 + c] = in ? img[(size_t)p * 3 + c] : (uint8_t)255;
 }
 
+__global__ __launch_bounds__(256) void k_cutout_object_packed(const uint8_t* __restrict__ img, const unsigned long long* __restrict__ bits,
+                                                              int H, int W, uint8_t* __restrict__ out) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= H * W) return;
+    const int y = p / W, x = p - y * W, wq = (W + 63) >> 6;
+    const size_t o = (size_t)blockIdx.y * H * W + p;
+    const bool in = (bits[((size_t)blockIdx.y * H + y) * wq + (x >> 6)] >> (x & 63)) & 1ull;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[o * 3 + c] = in ? img[(size_t)p * 3 + c] : (uint8_t)255;
+}
+
 bool frame_dims_ok(int H, int W) { return H >= 1 && W >= 1 && H <= 16384 && W <= 16384; }
 
 }  // namespace
@@ -350,11 +391,12 @@ extern "C" size_t ym_draw_workspace_bytes(int B, int max_det) {
     return (size_t)B * (HDR + (size_t)max_det * REC) * sizeof(int);
 }
 
-extern "C" int ym_draw_detections_batch(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores,
-                                        const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
-                                        const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
-                                        const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
-                                        uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+// `masks`: float [B][max_det][H][W], or (packed) the bit rows uint64 [B][max_det][H][ceil(W / 64)]
+static int draw_detections(const uint8_t* img, const void* masks, bool packed, const int64_t* ids, const float* scores,
+                           const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
+                           const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
+                           const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
+                           uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
     YM_REQUIRE(B >= 1 && B <= 65535 && max_det >= 0 && max_det <= YM_DRAW_MAX_DET, "ym_draw_detections_batch: 1 <= B <= 65535 and 0 <= max_det <= %d required (B=%d max_det=%d)",
                YM_DRAW_MAX_DET, B, max_det);
     YM_REQUIRE(frame_dims_ok(H, W), "ym_draw_detections_batch: frame %dx%d out of range (1..16384)", H, W);
@@ -389,14 +431,33 @@ extern "C" int ym_draw_detections_batch(const uint8_t* img, const float* masks, 
     const size_t lds = (size_t)(PAL + HDR + max_det * REC) * sizeof(int);
     const dim3 grid(ym_cdiv(H * ((W + 3) / 4), FRAME_THREADS), B);
     const bool vec = (W % 4 == 0) && ((uintptr_t)img % 4 == 0) && ((uintptr_t)out % 4 == 0) && (!cutout_total || (uintptr_t)cutout_total % 4 == 0) &&
-                     (hide_mask || (uintptr_t)masks % 16 == 0);
-    if (vec)
-        k_draw_frame<true><<<grid, FRAME_THREADS, lds, st>>>(img, masks, (const int*)workspace, max_det, H, W, palette, palette_n,
-                                                             num_classes - 1, font, flags, out, cutout_total);
-    else
-        k_draw_frame<false><<<grid, FRAME_THREADS, lds, st>>>(img, masks, (const int*)workspace, max_det, H, W, palette, palette_n,
-                                                              num_classes - 1, font, flags, out, cutout_total);
+                     (hide_mask || (uintptr_t)masks % 16 == 0 || (packed && (uintptr_t)masks % 8 == 0));
+    YM_REQUIRE(!packed || (uintptr_t)masks % 8 == 0, "ym_draw_detections_batch_packed: the mask words must be 8-byte aligned");
+#define YM_DRAW_FRAME(V, P)                                                                                                         \
+    k_draw_frame<V, P><<<grid, FRAME_THREADS, lds, st>>>(img, masks, (const int*)workspace, max_det, H, W, palette, palette_n,     \
+                                                         num_classes - 1, font, flags, out, cutout_total)
+    if (packed) { if (vec) YM_DRAW_FRAME(true, true); else YM_DRAW_FRAME(false, true); }
+    else { if (vec) YM_DRAW_FRAME(true, false); else YM_DRAW_FRAME(false, false); }
+#undef YM_DRAW_FRAME
     return ym_check_launch("k_draw_frame");
+}
+
+extern "C" int ym_draw_detections_batch(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores,
+                                        const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
+                                        const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
+                                        const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
+                                        uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    return draw_detections(img, masks, false, ids, scores, boxes_px, counts, B, max_det, H, W, palette, palette_n, num_classes, names,
+                           num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, s);
+}
+
+extern "C" int ym_draw_detections_batch_packed(const uint8_t* img, const uint64_t* mask_bits, const int64_t* ids, const float* scores,
+                                               const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
+                                               const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
+                                               const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
+                                               uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    return draw_detections(img, mask_bits, true, ids, scores, boxes_px, counts, B, max_det, H, W, palette, palette_n, num_classes, names,
+                           num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, s);
 }
 
 extern "C" int ym_draw_cutout_objects(const uint8_t* img, const float* masks, int n, int H, int W, uint8_t* out, ym_stream_t s) {
@@ -404,4 +465,11 @@ extern "C" int ym_draw_cutout_objects(const uint8_t* img, const float* masks, in
     YM_REQUIRE(img && masks && out, "ym_draw_cutout_objects: null pointer");
     k_cutout_object<<<dim3(ym_cdiv(H * W, 256), n), 256, 0, (hipStream_t)s>>>(img, masks, H * W, out);
     return ym_check_launch("k_cutout_object");
+}
+
+extern "C" int ym_draw_cutout_objects_packed(const uint8_t* img, const uint64_t* mask_bits, int n, int H, int W, uint8_t* out, ym_stream_t s) {
+    YM_REQUIRE(n >= 1 && n <= 65535 && frame_dims_ok(H, W), "ym_draw_cutout_objects_packed: 1 <= n <= 65535 and a frame of 1..16384 per side required (n=%d %dx%d)", n, H, W);
+    YM_REQUIRE(img && mask_bits && out, "ym_draw_cutout_objects_packed: null pointer");
+    k_cutout_object_packed<<<dim3(ym_cdiv(H * W, 256), n), 256, 0, (hipStream_t)s>>>(img, reinterpret_cast<const unsigned long long*>(mask_bits), H, W, out);
+    return ym_check_launch("k_cutout_object_packed");
 }

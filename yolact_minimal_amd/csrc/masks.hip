@@ -8,6 +8,8 @@
 //                    Algorithmic bytes: P*32*4 (proto, read once) + n*P*4 (masks, written once): HBM-bound.
 //  k_mask_resize   : bilinear (align_corners=False) to S x S, > 0.5, cropped to img_h x img_w; the output
 //                    (n*img_h*img_w*4 B) dominates, written with 16-byte stores.
+//  k_masks_fused    : after_nms in one launch (below);  k_masks_fused_packed / k_mask_resize_packed: the same pixels written as
+//                    1 bit each (one ballot = one 64-pixel word), k_pack_masks / k_unpack_masks: dense <-> bits.
 #pragma clang fp contract(off)
 #include "ym_common.h"
 
@@ -231,6 +233,176 @@ __global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ p
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Bit-packed output (include/yolact_hip.h "bit-packed instance masks"): bits [slot][img_h][wq] uint64, wq = ceil(img_w / 64), bit k
+// of word j of row y = pixel (y, 64j + k), bits at x >= img_w zero.  k_masks_fused_packed is k_masks_fused with another lane ->
+// pixel map and another store: the tile, the LDS patch and every floating-point expression are the dense kernel's, so a bit equals
+// (dense value != 0).  A lane owns pixels ox0 + 64e + lane (e = 0..3) of its wave's four rows: one ballot per (row, e) IS one word,
+// lane k < 16 keeps word k and the wave's 16 words leave as one 8-byte store per lane (four 32-byte row pieces).  A tile outside
+// the crop window stores its 16 x 4 zero words (512 B) and exits; the dense [n][img_h][img_w] tensor exists nowhere.
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_masks_fused_packed(const float* __restrict__ proto, const float* __restrict__ coefs,
+                                                             const float* __restrict__ boxes, const int32_t* __restrict__ counts,
+                                                             int max_det, int Hp, int Wp, int img_h, int img_w, int do_crop,
+                                                             unsigned long long* __restrict__ out) {
+    static_assert(FT_W == 256 && FT_H == 16, "4 words x (4 waves x 4 rows) per tile");
+    __shared__ float patch[FP_H * FP_W];
+    __shared__ __attribute__((aligned(16))) float cf[32];
+    const int b = blockIdx.z, d = blockIdx.y;
+    const int n = counts ? counts[b] : max_det;
+    if (d >= n) return;
+    const int tiles_x = (img_w + FT_W - 1) / FT_W;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int oy0 = ty * FT_H, ox0 = tx * FT_W;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int S = img_h > img_w ? img_h : img_w;
+    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
+    const size_t slot = (size_t)b * max_det + d;
+
+    float x1 = 0.f, x2 = (float)Wp, y1 = 0.f, y2 = (float)Hp;
+    if (do_crop) {
+        const f32x4 bx = *reinterpret_cast<const f32x4*>(boxes + slot * 4);
+        crop_span(bx[0], bx[2], (float)Wp, x1, x2);
+        crop_span(bx[1], bx[3], (float)Hp, y1, y2);
+    }
+    int py0, py1, px0, px1, t0, t1; float l;
+    const int oy_last = min(oy0 + FT_H, img_h) - 1, ox_last = min(ox0 + FT_W, img_w) - 1;
+    src_coord(oy0, sy, Hp, py0, t1, l);
+    src_coord(oy_last, sy, Hp, t0, py1, l);
+    src_coord(ox0, sx, Wp, px0, t1, l);
+    src_coord(ox_last, sx, Wp, t0, px1, l);
+    const int ph = py1 - py0 + 1, pw = px1 - px0 + 1;
+    const bool active = (float)px1 >= x1 && (float)px0 < x2 && (float)py1 >= y1 && (float)py0 < y2;
+    const int wq = (img_w + 63) >> 6;
+    // lane k < 16 stores word (k & 3) of row (k >> 2) of this wave's four rows
+    const int my_y = oy0 + wave * (FT_H / 4) + (lane >> 2), my_j = (ox0 >> 6) + (lane & 3);
+    const bool stores = lane < 16 && my_y < img_h && my_j < wq;
+    unsigned long long* dst = out + (slot * (size_t)img_h + my_y) * wq + my_j;
+    if (!active) {
+        if (stores) *dst = 0ull;
+        return;
+    }
+    if (tid < 32) cf[tid] = coefs[slot * 32 + tid];
+    __syncthreads();
+    const float* pimg = proto + (size_t)b * Hp * Wp * 32;
+    for (int i = tid; i < ph * pw; i += 256) {
+        const int r = i / pw, c = i - r * pw;
+        const int py = py0 + r, px = px0 + c;
+        const float fx = (float)px, fy = (float)py;
+        float v = 0.f;
+        if (fx >= x1 && fx < x2 && fy >= y1 && fy < y2) {
+            const f32x4* pr = reinterpret_cast<const f32x4*>(pimg + ((size_t)py * Wp + px) * 32);
+            float acc = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const f32x4 pv = pr[q];
+                const f32x4 cv = *reinterpret_cast<const f32x4*>(cf + q * 4);
+                acc = __builtin_fmaf(cv[0], pv[0], acc);
+                acc = __builtin_fmaf(cv[1], pv[1], acc);
+                acc = __builtin_fmaf(cv[2], pv[2], acc);
+                acc = __builtin_fmaf(cv[3], pv[3], acc);
+            }
+            v = 1.f / (1.f + expf(-acc));
+        }
+        patch[r * FP_W + c] = v;
+    }
+    __syncthreads();
+    unsigned long long mine = 0ull;
+#pragma unroll
+    for (int r = 0; r < FT_H / 4; ++r) {
+        const int y = oy0 + wave * (FT_H / 4) + r;
+        if (y >= img_h) continue;                                // (wave-uniform: rows past the image own no patch rows)
+        int y0, y1i; float ly;
+        src_coord(y, sy, Hp, y0, y1i, ly);
+        const float hy = 1.f - ly;
+        const float* r0 = patch + (y0 - py0) * FP_W - px0;
+        const float* r1 = patch + (y1i - py0) * FP_W - px0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (ox0 + 64 * e >= img_w) continue;                 // (wave-uniform: this word does not exist)
+            const int x = ox0 + 64 * e + lane;
+            int x0, x1i; float lx;
+            src_coord(x < img_w ? x : img_w - 1, sx, Wp, x0, x1i, lx);
+            const float hx = 1.f - lx;
+            const float v = hy * (hx * r0[x0] + lx * r0[x1i]) + ly * (hx * r1[x0] + lx * r1[x1i]);
+            const unsigned long long w = __ballot(x < img_w && v > 0.5f);
+            mine = lane == r * 4 + e ? w : mine;
+        }
+    }
+    if (stores) *dst = mine;
+}
+
+// the two-kernel path's resize with packed output: a wave per word, lane = pixel (k_mask_resize's expression per pixel)
+__global__ __launch_bounds__(256) void k_mask_resize_packed(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
+                                                             unsigned long long* __restrict__ out) {
+    const int S = img_h > img_w ? img_h : img_w;
+    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
+    const int wq = (img_w + 63) >> 6, lane = threadIdx.x & 63;
+    const size_t total = (size_t)n * img_h * wq;
+    for (size_t i = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < total; i += (size_t)gridDim.x * 4) {
+        const int j = (int)(i % wq);
+        size_t t = i / wq;
+        const int y = (int)(t % img_h);
+        const int d = (int)(t / img_h);
+        int y0, y1; float ly;
+        src_coord(y, sy, Hp, y0, y1, ly);
+        const float hy = 1.f - ly;
+        const float* r0 = masks + ((size_t)d * Hp + y0) * Wp;
+        const float* r1 = masks + ((size_t)d * Hp + y1) * Wp;
+        const int x = j * 64 + lane;
+        int x0, x1; float lx;
+        src_coord(x < img_w ? x : img_w - 1, sx, Wp, x0, x1, lx);
+        const float hx = 1.f - lx;
+        const float v = hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
+        const unsigned long long w = __ballot(x < img_w && v > 0.5f);
+        if (lane == 0) out[i] = w;
+    }
+}
+
+// dense {0, nonzero} rows -> words.  A wave takes PK consecutive words of the flat [rows][wq] output (PK row pieces of 64 pixels in
+// flight per lane), lane u keeps word u: one 8 * PK byte store per wave.
+constexpr int PK = 8;
+template <typename T>
+__global__ __launch_bounds__(256) void k_pack_masks(const T* __restrict__ m, long long rows, int W, unsigned long long* __restrict__ out) {
+    const int wq = (W + 63) >> 6, lane = threadIdx.x & 63;
+    const long long total = rows * wq;
+    for (long long g = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * PK; g < total; g += (long long)gridDim.x * 4 * PK) {
+        T v[PK];
+#pragma unroll
+        for (int u = 0; u < PK; ++u) {
+            const long long w = g + u < total ? g + u : total - 1;
+            const long long row = w / wq;
+            const int x = (int)(w - row * wq) * 64 + lane;
+            v[u] = x < W ? m[row * W + x] : (T)0;
+        }
+        unsigned long long mine = 0ull;
+#pragma unroll
+        for (int u = 0; u < PK; ++u) {
+            const unsigned long long w = __ballot(v[u] != (T)0);
+            mine = lane == u ? w : mine;
+        }
+        if (lane < PK && g + lane < total) out[g + lane] = mine;
+    }
+}
+
+// words -> the reference's float tensor (exactly 0.0f / 1.0f): a thread owns 4 consecutive pixels (never across a word boundary)
+__global__ __launch_bounds__(256) void k_unpack_masks(const unsigned long long* __restrict__ bits, long long rows, int W, int vec,
+                                                       float* __restrict__ out) {
+    const int wq = (W + 63) >> 6, Q = (W + 3) >> 2;
+    const long long total = rows * Q;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long row = i / Q;
+        const int x0 = (int)(i - row * Q) * 4;
+        const unsigned nib = (unsigned)(bits[row * wq + (x0 >> 6)] >> (x0 & 63)) & 15u;
+        float* dst = out + row * W + x0;
+        if (vec) {
+            *reinterpret_cast<f32x4*>(dst) = f32x4{(float)(nib & 1u), (float)((nib >> 1) & 1u), (float)((nib >> 2) & 1u), (float)(nib >> 3)};
+        } else {
+            for (int e = 0; e < 4 && x0 + e < W; ++e) dst[e] = (float)((nib >> e) & 1u);
+        }
+    }
+}
+
 __global__ void k_boxes_to_pixels(float* boxes, int32_t* px, int count, float S) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) {
@@ -314,4 +486,61 @@ extern "C" int ym_after_nms_batch(const float* proto, const float* coefs, float*
 
 extern "C" size_t ym_after_nms_batch_workspace_bytes(int max_det, int Hp, int Wp, int img_h, int img_w) {
     return fused_fits(Hp, Wp, img_h, img_w) ? 0 : (size_t)max_det * Hp * Wp * sizeof(float);
+}
+
+extern "C" int ym_after_nms_batch_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
+                                         int Hp, int Wp, int K, int img_h, int img_w, int do_crop, uint64_t* mask_bits,
+                                         int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    YM_REQUIRE(K == 32, "after_nms_packed: coefficient dim must be 32, got %d", K);
+    YM_REQUIRE(B >= 1 && B <= 65535 && max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0 && img_h > 0 && img_w > 0, "after_nms_packed: bad shape");
+    YM_REQUIRE(proto && coefs && boxes && mask_bits && boxes_px, "after_nms_packed: null pointer");
+    hipStream_t st = (hipStream_t)s;
+    unsigned long long* bits = reinterpret_cast<unsigned long long*>(mask_bits);
+    const int wq = ym_cdiv(img_w, 64);
+    if (fused_fits(Hp, Wp, img_h, img_w)) {
+        const int tiles = ym_cdiv(img_w, FT_W) * ym_cdiv(img_h, FT_H);
+        hipLaunchKernelGGL(k_masks_fused_packed, dim3(tiles, max_det, B), dim3(256), 0, st, proto, coefs, boxes, counts, max_det, Hp, Wp,
+                           img_h, img_w, do_crop, bits);
+    } else {
+        const size_t soft_bytes = (size_t)max_det * Hp * Wp * sizeof(float);
+        if (!workspace || workspace_bytes < soft_bytes) { ym_set_error("after_nms_packed: workspace %zu B < %zu B", workspace_bytes, soft_bytes); return YM_ENOSPC; }
+        const size_t words = (size_t)max_det * img_h * wq;
+        const int grid = (int)((words + 3) / 4 > 16384 ? 16384 : (words + 3) / 4);     // a wave per word, grid-strided
+        for (int b = 0; b < B; ++b) {
+            const size_t slot = (size_t)b * max_det;
+            int rc = ym_mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, K, do_crop,
+                                      (float*)workspace, s);
+            if (rc != YM_OK) return rc;
+            hipLaunchKernelGGL(k_mask_resize_packed, dim3(grid), dim3(256), 0, st, (const float*)workspace, max_det, Hp, Wp, img_h, img_w,
+                               bits + slot * (size_t)img_h * wq);
+        }
+    }
+    const int S = img_h > img_w ? img_h : img_w;
+    const int cnt = B * max_det * 4;
+    hipLaunchKernelGGL(k_boxes_to_pixels, dim3(ym_cdiv(cnt, 256)), dim3(256), 0, st, boxes, boxes_px, cnt, (float)S);
+    return ym_check_launch("after_nms_batch_packed");
+}
+
+extern "C" int ym_pack_masks(const void* masks, int is_u8, int n, int H, int W, uint64_t* bits, ym_stream_t s) {
+    YM_REQUIRE(n >= 0 && H > 0 && W > 0, "pack_masks: bad shape");
+    if (n == 0) return YM_OK;
+    YM_REQUIRE(masks && bits, "pack_masks: null pointer");
+    const long long rows = (long long)n * H, groups = (rows * ym_cdiv(W, 64) + PK - 1) / PK;
+    const int grid = (int)((groups + 3) / 4 > 16384 ? 16384 : (groups + 3) / 4);
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(bits);
+    if (is_u8) hipLaunchKernelGGL(k_pack_masks<uint8_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const uint8_t*)masks, rows, W, out);
+    else hipLaunchKernelGGL(k_pack_masks<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)masks, rows, W, out);
+    return ym_check_launch("pack_masks");
+}
+
+extern "C" int ym_unpack_masks(const uint64_t* bits, int n, int H, int W, float* masks, ym_stream_t s) {
+    YM_REQUIRE(n >= 0 && H > 0 && W > 0, "unpack_masks: bad shape");
+    if (n == 0) return YM_OK;
+    YM_REQUIRE(masks && bits, "unpack_masks: null pointer");
+    const long long rows = (long long)n * H, total = rows * ((W + 3) / 4);
+    const int grid = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
+    const int vec = (W & 3) == 0 && ((uintptr_t)masks & 15) == 0;
+    hipLaunchKernelGGL(k_unpack_masks, dim3(grid), dim3(256), 0, (hipStream_t)s, reinterpret_cast<const unsigned long long*>(bits), rows, W,
+                       vec, masks);
+    return ym_check_launch("unpack_masks");
 }

@@ -3,6 +3,7 @@
 // (utils/box_utils.py:8-37) and the greedy per-class matching of prep_metrics (utils/common_utils.py:174-216).
 // The masks are {0,1}, so the matmul is a popcount of ANDed bit rows: HBM-bound (every mask read exactly once, 123 MB for 100
 // masks at 480x640), exact in integers -> the IoU is bit-identical to the reference's fp32 result (counts < 2^24).
+// ym_mask_iou_packed takes masks that already ARE bit rows (utils/packed_masks.py): 3.84 MB instead of 123 MB, same counts.
 #pragma clang fp contract(off)
 #include "ym_common.h"
 
@@ -100,6 +101,54 @@ __global__ __launch_bounds__(512) void k_mask_inter(const float* __restrict__ A,
             int c = 0;
 #pragma unroll 8
             for (int w = 0; w < WORDS; ++w) c += __popcll(sa[i][w] & sb[j][w]);
+            inter[(size_t)(a0 + i) * g + g0 + j] = c;
+        }
+    }
+}
+
+// Both operands already are bit rows (include/yolact_hip.h "bit-packed instance masks": [.][Pw] words, Pw = H * ceil(W / 64), pad
+// bits zero): the ballot pass of k_mask_inter disappears, words go from HBM straight into the same LDS arrays and the same pair
+// loop.  PWORDS words per chunk: 480x640 masks = 4800 words = 240 chunks, one round over the 256 CUs.  Same partial-count layout,
+// same finalize kernel, no global atomics.
+constexpr int PWORDS = 20;
+__global__ __launch_bounds__(512) void k_mask_inter_packed(const unsigned long long* __restrict__ A, int n,
+                                                           const unsigned long long* __restrict__ Bm, int g, long long Pw,
+                                                           int* __restrict__ inter, int* __restrict__ area_a, int* __restrict__ area_b) {
+    __shared__ unsigned long long sa[MAXR][PWORDS + 1];
+    __shared__ unsigned long long sb[MAXR][PWORDS + 1];
+    const int tid = threadIdx.x;
+    const long long w0 = (long long)blockIdx.x * PWORDS;
+    const int nwd = (int)min((long long)PWORDS, Pw - w0);
+    const int g0 = blockIdx.y * MAXR, gn = min(MAXR, g - g0);
+    inter += (size_t)blockIdx.x * n * g;
+    area_a += (size_t)blockIdx.x * n;
+    area_b += (size_t)blockIdx.x * g;
+    for (int a0 = 0; a0 < n; a0 += MAXR) {
+        const int an = min(MAXR, n - a0);
+        __syncthreads();
+        const int rows = an + (a0 == 0 ? gn : 0);          // (the gt rows stay in LDS for the later passes over A)
+        for (int idx = tid; idx < rows * PWORDS; idx += 512) {
+            const int rr = idx / PWORDS, q = idx - rr * PWORDS;
+            const bool is_a = rr < an;
+            const unsigned long long* row = is_a ? A + (size_t)(a0 + rr) * Pw : Bm + (size_t)(g0 + rr - an) * Pw;
+            const unsigned long long v = q < nwd ? __builtin_nontemporal_load(row + w0 + q) : 0ull;
+            (is_a ? sa[rr] : sb[rr - an])[q] = v;
+        }
+        __syncthreads();
+        for (int rr = tid; rr < rows; rr += 512) {
+            const bool is_a = rr < an;
+            const unsigned long long* w = is_a ? sa[rr] : sb[rr - an];
+            int c = 0;
+#pragma unroll
+            for (int q = 0; q < PWORDS; ++q) c += __popcll(w[q]);
+            if (is_a) { if (blockIdx.y == 0) area_a[a0 + rr] = c; }
+            else area_b[g0 + rr - an] = c;
+        }
+        for (int pr = tid; pr < an * gn; pr += 512) {
+            const int i = pr / gn, j = pr - i * gn;
+            int c = 0;
+#pragma unroll
+            for (int w = 0; w < PWORDS; ++w) c += __popcll(sa[i][w] & sb[j][w]);
             inter[(size_t)(a0 + i) * g + g0 + j] = c;
         }
     }
@@ -219,6 +268,29 @@ extern "C" int ym_mask_iou(const float* masks_a, int n, const float* masks_b, in
     else hipLaunchKernelGGL(k_mask_inter<5>, grid, dim3(512), 0, st, masks_a, n, masks_b, g, (long long)P, inter, area_a, area_b);
     hipLaunchKernelGGL(k_mask_iou_finalize, dim3((n * g + 63) / 64), dim3(64 * FSL), 0, st, inter, area_a, area_b, chunks, n, g, iou);
     return ym_check_launch("mask_iou");
+}
+
+extern "C" size_t ym_mask_iou_packed_workspace_bytes(int n, int g, int64_t words) {
+    const size_t chunks = (size_t)((words + PWORDS - 1) / PWORDS);
+    return chunks * ((size_t)n * g + n + g) * sizeof(int) + 256;
+}
+
+extern "C" int ym_mask_iou_packed(const uint64_t* bits_a, int n, const uint64_t* bits_b, int g, int64_t words, float* iou, void* workspace,
+                                  size_t workspace_bytes, ym_stream_t s) {
+    YM_REQUIRE(bits_a && bits_b && iou && workspace, "mask_iou_packed: null pointer");
+    YM_REQUIRE(n > 0 && g > 0 && words > 0 && words < (1ll << 18), "mask_iou_packed: n, g > 0 and 0 < words < 2^18 (exact fp32 counts)");
+    YM_REQUIRE((long long)n * g < (1ll << 24), "mask_iou_packed: n*g too large");
+    if (workspace_bytes < ym_mask_iou_packed_workspace_bytes(n, g, words)) { ym_set_error("mask_iou_packed: workspace too small"); return YM_ENOSPC; }
+    hipStream_t st = (hipStream_t)s;
+    const int chunks = (int)((words + PWORDS - 1) / PWORDS);
+    int* inter = (int*)workspace;
+    int* area_a = inter + (size_t)chunks * n * g;
+    int* area_b = area_a + (size_t)chunks * n;
+    const dim3 grid((unsigned)chunks, (unsigned)((g + MAXR - 1) / MAXR));
+    hipLaunchKernelGGL(k_mask_inter_packed, grid, dim3(512), 0, st, reinterpret_cast<const unsigned long long*>(bits_a), n,
+                       reinterpret_cast<const unsigned long long*>(bits_b), g, (long long)words, inter, area_a, area_b);
+    hipLaunchKernelGGL(k_mask_iou_finalize, dim3((n * g + 63) / 64), dim3(64 * FSL), 0, st, inter, area_a, area_b, chunks, n, g, iou);
+    return ym_check_launch("mask_iou_packed");
 }
 
 extern "C" int ym_box_iou(const float* boxes_a, int n, const float* boxes_b, int g, float* iou, ym_stream_t s) {

@@ -5,7 +5,7 @@
 // on: its difference to the count two places back) is written as little-endian 5-bit groups + continuation bit, +48.
 // One workgroup per mask, one thread per image column (row-major rows are read coalesced across the columns), two passes over
 // the mask (count transitions, then place them) = 2*H*W*4 bytes of HBM reads; the result is a few hundred bytes per mask
-// instead of a 1.2 MB dense D2H copy.
+// instead of a 1.2 MB dense D2H copy.  ym_rle_encode_packed is the same kernel reading bit-packed masks (BitSrc below).
 #include "ym_common.h"
 
 namespace {
@@ -36,35 +36,96 @@ __device__ __forceinline__ int block_exscan(int v, int* total, int* s_wave /*[NT
     return s_wave[wave] + inc - v;
 }
 
-__global__ __launch_bounds__(NT) void k_rle_encode(const float* __restrict__ masks, int H, int W, uint32_t* __restrict__ pos_ws,
+// Where a pixel comes from: the dense fp32 mask, or the bit rows of include/yolact_hip.h "bit-packed instance masks".  The dense
+// walk is a chain of H / UNR dependent load batches per pass (latency bound).  The 64 columns of a wave are ONE word per row, so
+// the packed walk loads 64 ROWS at once (lane = row) and turns the 64 x 64 bit block around with 64 ballots (lane k keeps the
+// ballot of bit k = its column's 64 rows): H / 64 loads per pass, and the transitions of 64 rows are one xor + popcount.
+struct DenseSrc {
+    typedef float T;
+    static constexpr bool kBits = false;
+    const float* m;
+    int W;
+    __device__ __forceinline__ DenseSrc(const void* base, int mask, int H, int W_) : m((const float*)base + (size_t)mask * H * W_), W(W_) {}
+    __device__ __forceinline__ T load(int y, int x) const { return m[(size_t)y * W + x]; }
+    __device__ __forceinline__ static bool on(T v, int) { return v != 0.f; }
+};
+struct BitSrc {
+    typedef unsigned long long T;
+    static constexpr bool kBits = true;
+    const unsigned long long* m;
+    int wq;
+    __device__ __forceinline__ BitSrc(const void* base, int mask, int H, int W_)
+        : m((const unsigned long long*)base + (size_t)mask * H * ((W_ + 63) >> 6)), wq((W_ + 63) >> 6) {}
+    __device__ __forceinline__ T load(int y, int x) const { return m[(size_t)y * wq + (x >> 6)]; }
+    __device__ __forceinline__ static bool on(T v, int x) { return (v >> (x & 63)) & 1ull; }
+    // rows y0 .. y0+63 of column 64 j + lane as bits 0 .. 63 (rows past H: 0).  Every lane of the wave must call it.
+    __device__ __forceinline__ unsigned long long column_block(int y0, int j, int H, int lane) const {
+        const int y = y0 + lane;
+        const unsigned long long w = y < H ? m[(size_t)y * wq + j] : 0ull;
+        const unsigned lo = (unsigned)w, hi = (unsigned)(w >> 32);
+        unsigned long long mine = 0ull;
+#pragma unroll
+        for (int k = 0; k < 64; ++k) {
+            const unsigned long long b = __ballot(((k < 32 ? lo : hi) >> (k & 31)) & 1u);
+            mine = lane == k ? b : mine;
+        }
+        return mine;
+    }
+};
+
+// transitions inside a block of nv <= 64 rows of one column (bit r set: row r differs from the row before it; `prev` = the pixel
+// before row 0); updates `prev` to the block's last row
+__device__ __forceinline__ unsigned long long block_transitions(unsigned long long col, int nv, bool& prev) {
+    unsigned long long t = col ^ ((col << 1) | (prev ? 1ull : 0ull));
+    if (nv < 64) t &= (1ull << nv) - 1ull;
+    prev = (col >> (nv - 1)) & 1ull;
+    return t;
+}
+
+template <class Src>
+__global__ __launch_bounds__(NT) void k_rle_encode(const void* __restrict__ masks, int H, int W, uint32_t* __restrict__ pos_ws,
                                                    uint32_t* __restrict__ counts, int cap, int32_t* __restrict__ nruns,
                                                    uint8_t* __restrict__ str, int cap_str, int32_t* __restrict__ str_len) {
+    typedef typename Src::T Px;
     __shared__ int s_col[MAXW];
     __shared__ int s_wave[NT / 64 + 1];
     const int tid = threadIdx.x;
-    const float* m = masks + (size_t)blockIdx.x * H * W;
+    const Src m(masks, blockIdx.x, H, W);
     uint32_t* pos = pos_ws + (size_t)blockIdx.x * cap;
     uint32_t* cnt = counts + (size_t)blockIdx.x * cap;
     uint8_t* out = str + (size_t)blockIdx.x * cap_str;
     const unsigned P = (unsigned)H * (unsigned)W;
 
     // pass 1: transitions per column (the pixel before (0, x) in column-major order is (H-1, x-1); before (0,0): background)
+    if constexpr (Src::kBits) {
+        const int lane = tid & 63;
+        for (int xb = tid - lane; xb < W; xb += NT) {            // (wave-uniform: the block transpose needs all 64 lanes)
+            const int x = xb + lane;
+            bool prev = x > 0 && x < W && Src::on(m.load(H - 1, x - 1), x - 1);
+            int c = 0;
+            for (int y0 = 0; y0 < H; y0 += 64) {
+                const unsigned long long col = m.column_block(y0, xb >> 6, H, lane);
+                c += __popcll(block_transitions(col, min(64, H - y0), prev));
+            }
+            if (x < W) s_col[x] = c;
+        }
+    } else
     for (int x = tid; x < W; x += NT) {
-        bool prev = x > 0 && m[(size_t)(H - 1) * W + x - 1] != 0.f;
+        bool prev = x > 0 && Src::on(m.load(H - 1, x - 1), x - 1);
         int c = 0, y = 0;
         for (; y + UNR <= H; y += UNR) {          // UNR independent row loads in flight per lane (the walk is latency bound)
-            float v[UNR];
+            Px v[UNR];
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) v[u] = m[(size_t)(y + u) * W + x];
+            for (int u = 0; u < UNR; ++u) v[u] = m.load(y + u, x);
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
-                const bool cur = v[u] != 0.f;
+                const bool cur = Src::on(v[u], x);
                 c += cur != prev;
                 prev = cur;
             }
         }
         for (; y < H; ++y) {
-            const bool cur = m[(size_t)y * W + x] != 0.f;
+            const bool cur = Src::on(m.load(y, x), x);
             c += cur != prev;
             prev = cur;
         }
@@ -90,22 +151,39 @@ __global__ __launch_bounds__(NT) void k_rle_encode(const float* __restrict__ mas
         return;
     }
     // pass 2: positions of the transitions, in column-major order
+    if constexpr (Src::kBits) {
+        const int lane = tid & 63;
+        for (int xb = tid - lane; xb < W; xb += NT) {
+            const int x = xb + lane;
+            bool prev = x > 0 && x < W && Src::on(m.load(H - 1, x - 1), x - 1);
+            int o = x < W ? s_col[x] : 0;
+            for (int y0 = 0; y0 < H; y0 += 64) {
+                const unsigned long long col = m.column_block(y0, xb >> 6, H, lane);
+                unsigned long long t = block_transitions(col, min(64, H - y0), prev);
+                if (x >= W) t = 0ull;
+                while (t) {
+                    pos[o++] = (unsigned)x * (unsigned)H + (unsigned)(y0 + __builtin_ctzll(t));
+                    t &= t - 1ull;
+                }
+            }
+        }
+    } else
     for (int x = tid; x < W; x += NT) {
-        bool prev = x > 0 && m[(size_t)(H - 1) * W + x - 1] != 0.f;
+        bool prev = x > 0 && Src::on(m.load(H - 1, x - 1), x - 1);
         int o = s_col[x], y = 0;
         for (; y + UNR <= H; y += UNR) {
-            float v[UNR];
+            Px v[UNR];
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) v[u] = m[(size_t)(y + u) * W + x];
+            for (int u = 0; u < UNR; ++u) v[u] = m.load(y + u, x);
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
-                const bool cur = v[u] != 0.f;
+                const bool cur = Src::on(v[u], x);
                 if (cur != prev) pos[o++] = (unsigned)x * (unsigned)H + (unsigned)(y + u);
                 prev = cur;
             }
         }
         for (; y < H; ++y) {
-            const bool cur = m[(size_t)y * W + x] != 0.f;
+            const bool cur = Src::on(m.load(y, x), x);
             if (cur != prev) pos[o++] = (unsigned)x * (unsigned)H + (unsigned)y;
             prev = cur;
         }
@@ -151,13 +229,26 @@ __global__ __launch_bounds__(NT) void k_rle_encode(const float* __restrict__ mas
 
 }  // namespace
 
+template <class Src>
+static int rle_encode_launch(const char* what, const void* masks, int n, int H, int W, uint32_t* counts, int cap_runs, int32_t* nruns,
+                             uint8_t* str, int cap_str, int32_t* str_len, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    YM_REQUIRE(masks && counts && nruns && str && str_len && workspace, "%s: null pointer", what);
+    YM_REQUIRE(n > 0 && H > 0 && W > 0 && W <= MAXW && cap_runs > 0 && cap_str > 0, "%s: need 0 < W <= %d", what, MAXW);
+    YM_REQUIRE((long long)H * W < (1ll << 31), "%s: mask too large", what);
+    if (workspace_bytes < (size_t)n * cap_runs * 4) { ym_set_error("%s: workspace < n*cap_runs*4 bytes", what); return YM_ENOSPC; }
+    hipLaunchKernelGGL(k_rle_encode<Src>, dim3(n), dim3(NT), 0, (hipStream_t)s, masks, H, W, (uint32_t*)workspace, counts, cap_runs, nruns,
+                       str, cap_str, str_len);
+    return ym_check_launch(what);
+}
+
 extern "C" int ym_rle_encode(const float* masks, int n, int H, int W, uint32_t* counts, int cap_runs, int32_t* nruns, uint8_t* str,
                              int cap_str, int32_t* str_len, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    YM_REQUIRE(masks && counts && nruns && str && str_len && workspace, "rle_encode: null pointer");
-    YM_REQUIRE(n > 0 && H > 0 && W > 0 && W <= MAXW && cap_runs > 0 && cap_str > 0, "rle_encode: need 0 < W <= %d", MAXW);
-    YM_REQUIRE((long long)H * W < (1ll << 31), "rle_encode: mask too large");
-    if (workspace_bytes < (size_t)n * cap_runs * 4) { ym_set_error("rle_encode: workspace < n*cap_runs*4 bytes"); return YM_ENOSPC; }
-    hipLaunchKernelGGL(k_rle_encode, dim3(n), dim3(NT), 0, (hipStream_t)s, masks, H, W, (uint32_t*)workspace, counts, cap_runs, nruns,
-                       str, cap_str, str_len);
-    return ym_check_launch("rle_encode");
+    return rle_encode_launch<DenseSrc>("rle_encode", masks, n, H, W, counts, cap_runs, nruns, str, cap_str, str_len, workspace,
+                                       workspace_bytes, s);
+}
+
+extern "C" int ym_rle_encode_packed(const uint64_t* bits, int n, int H, int W, uint32_t* counts, int cap_runs, int32_t* nruns, uint8_t* str,
+                                    int cap_str, int32_t* str_len, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    return rle_encode_launch<BitSrc>("rle_encode_packed", bits, n, H, W, counts, cap_runs, nruns, str, cap_str, str_len, workspace,
+                                     workspace_bytes, s);
 }

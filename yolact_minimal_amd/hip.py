@@ -35,6 +35,8 @@ ABI_SYMBOLS = (
     'ym_match_anchors', 'ym_match_anchors_batch', 'ym_loss_workspace_bytes', 'ym_class_box_loss', 'ym_semantic_loss',
     'ym_semantic_loss_batch',
     'ym_draw_workspace_bytes', 'ym_draw_detections_batch', 'ym_draw_cutout_objects',
+    'ym_after_nms_batch_packed', 'ym_pack_masks', 'ym_unpack_masks', 'ym_mask_iou_packed_workspace_bytes', 'ym_mask_iou_packed',
+    'ym_rle_encode_packed', 'ym_draw_detections_batch_packed', 'ym_draw_cutout_objects_packed',
     'ym_bn_train_bwd_workspace_bytes', 'ym_bn_train_bwd', 'ym_bn_train_bwd_apply', 'ym_act_bias_bwd', 'ym_conv2d_fuses_bn_stats', 'ym_bn_train_fwd_stats', 'ym_maxpool3x3s2_bwd', 'ym_maxpool3x3s2_fwd_idx', 'ym_maxpool3x3s2_bwd_idx', 'ym_bilinear2x_bwd', 'ym_sgd_step',
 )
 
@@ -216,12 +218,21 @@ def lib():
         L.ym_draw_detections_batch.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp, i32, f32,
                                                ctypes.c_char_p, vp, vp, vp, sz, vp]
         L.ym_draw_cutout_objects.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+        L.ym_after_nms_batch_packed.argtypes = L.ym_after_nms_batch.argtypes
+        L.ym_pack_masks.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+        L.ym_unpack_masks.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.ym_mask_iou_packed_workspace_bytes.argtypes = [i32, i32, i64]
+        L.ym_mask_iou_packed_workspace_bytes.restype = sz
+        L.ym_mask_iou_packed.argtypes = L.ym_mask_iou.argtypes
+        L.ym_rle_encode_packed.argtypes = L.ym_rle_encode.argtypes
+        L.ym_draw_detections_batch_packed.argtypes = L.ym_draw_detections_batch.argtypes
+        L.ym_draw_cutout_objects_packed.argtypes = L.ym_draw_cutout_objects.argtypes
         for name in ABI_SYMBOLS:
             fn = getattr(L, name)
             if name not in ('ym_last_error', 'ym_conv2d_workspace_bytes', 'ym_nms_workspace_bytes',
                             'ym_greedy_nms_workspace_bytes', 'ym_conv2d_wgrad_workspace_bytes',
                             'ym_sizeof_conv_desc', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
-                            'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes'):
+                            'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

@@ -50,10 +50,13 @@ class RequestPipeline:
     fresh tensors the caller owns (network outputs are copied off the slot's buffers before the slot runs again).
     `return_outputs=False` (throughput measurements of the forward alone): `submit()` / `drain()` hand back nothing for
     `with_post=False` and the copy is skipped.  `timed=True`: every request is bracketed by HIP events on its slot's stream and
-    `latencies_ms` collects the per-request device latency (bench.py: p50 / p99 and the Little's-law check)."""
+    `latencies_ms` collects the per-request device latency (bench.py: p50 / p99 and the Little's-law check).
+    `packed_masks=True`: the fourth result is a `PackedMasks` (1 bit per pixel: 3.84 MB instead of 123 MB per request at 480x640,
+    for the `depth` results in flight and for whatever the caller still owns)."""
 
     def __init__(self, net, cfg, height, width, device, depth=4, out_hw=(480, 640), with_post=True, batch=1, return_outputs=True,
-                 timed=False):
+                 timed=False, packed_masks=False):
+        self.packed_masks = bool(packed_masks)          # results carry PackedMasks (utils/packed_masks.py) instead of float32 masks
         self.net, self.cfg, self.device, self.depth, self.batch = net, cfg, torch.device(device), depth, batch
         self.out_hw, self.with_post, self.return_outputs, self.timed = out_hw, with_post, return_outputs, timed
         if depth > 1 and not hw_queues_ok(depth):
@@ -133,7 +136,7 @@ class RequestPipeline:
             if n == 0:
                 out.append((None, None, None, None))
                 continue
-            r = (ids[b, :n], scores[b, :n], box_px[b, :n], masks[b, :n])
+            r = (ids[b, :n], scores[b, :n], box_px[b, :n], masks[b][:n])
             if self.vt > 0:                               # detect.py's score filter, as in `after_nms` / `after_nms_batch(sync=True)`
                 keep = r[1] >= self.vt
                 r = tuple(t[keep] for t in r) if bool(keep.any()) else (None, None, None, None)
@@ -163,7 +166,7 @@ class RequestPipeline:
             if self.with_post:
                 cls, box, coef, proto = head_outputs if head_outputs is not None else eng.outputs()
                 r = after_nms_batch(nms_batch(cls, box, coef, proto, self.anchors, self.cfg), self.out_hw[0], self.out_hw[1], self.cfg,
-                                    sync=False)
+                                    sync=False, packed=self.packed_masks)
                 self.counts_host[slot].copy_(r[4], non_blocking=True)
                 if self.timed:
                     self.t1[slot].record()

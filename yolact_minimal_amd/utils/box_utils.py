@@ -6,6 +6,8 @@ same arithmetic order is kept here (`(i + 0.5) / conv_w`, `scale * sqrt(ar) / im
 """
 from math import sqrt
 
+from .packed_masks import PackedMasks, mask_iou_packed
+
 
 def make_anchors(cfg, conv_h, conv_w, scale):
     roots = [sqrt(ar) for ar in cfg.aspect_ratios]
@@ -44,6 +46,8 @@ def mask_iou(mask1, mask2, to_cpu=True):
     import ctypes
     import torch
     from .. import hip
+    if isinstance(mask1, PackedMasks) or isinstance(mask2, PackedMasks):
+        return mask_iou_packed(mask1, mask2, to_cpu)            # same exact integer counts from 1/32 of the bytes
     a, b = _f32(mask1), _f32(mask2)
     if not a.is_cuda:
         raise RuntimeError('yolact_minimal_amd has no CPU path: mask_iou needs CUDA/HIP tensors')
@@ -55,3 +59,4 @@ def mask_iou(mask1, mask2, to_cpu=True):
         hip.check(hip.lib().ym_mask_iou(hip.ptr(a), n, hip.ptr(b), g, p, hip.ptr(out), ctypes.c_void_p(ws.data_ptr()), nb,
                                         hip.stream_ptr()), 'ym_mask_iou')
     return out.cpu() if to_cpu else out
+

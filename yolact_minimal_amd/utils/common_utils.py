@@ -14,6 +14,7 @@ import torch
 
 from .. import hip
 from .box_utils import box_iou, mask_iou
+from .packed_masks import PackedMasks
 
 
 class APDataObject:
@@ -86,8 +87,10 @@ def prep_metrics(ap_data, ids_p, classes_p, boxes_p, masks_p, gt, gt_masks, heig
     gt_boxes[:, 0::2] *= width                 # (columns 0, 2 / 1, 3 as strided views: no index tensors, one launch each)
     gt_boxes[:, 1::2] *= height
     gt_classes = gt[:, 4].int().tolist()
-    gt_masks = gt_masks.reshape(-1, height * width)
-    masks_p = masks_p.reshape(-1, height * width)
+    if not isinstance(gt_masks, PackedMasks):               # (a PackedMasks on either side: mask_iou packs the other one)
+        gt_masks = gt_masks.reshape(-1, height * width)
+    if not isinstance(masks_p, PackedMasks):
+        masks_p = masks_p.reshape(-1, height * width)
     ids_p = [int(i) for i in ids_p]
 
     iou_mask = mask_iou(masks_p, gt_masks, to_cpu=False)
@@ -137,8 +140,14 @@ def rle_encode(masks, cap_runs=4096):
     Only the compressed strings (a few hundred bytes per mask) cross PCIe."""
     if not masks.is_cuda:
         raise RuntimeError('yolact_minimal_amd has no CPU path: rle_encode needs CUDA/HIP tensors')
-    m = masks.to(torch.float32).contiguous()
-    n, h, w = m.shape
+    if isinstance(masks, PackedMasks):                      # the same strings from 1/32 of the bytes (`ym_rle_encode_packed`)
+        n, h, w = masks.shape
+        m = masks.bits.contiguous()
+        encode, src = hip.lib().ym_rle_encode_packed, hip.ptr(m, torch.int64)
+    else:
+        m = masks.to(torch.float32).contiguous()
+        n, h, w = m.shape
+        encode, src = hip.lib().ym_rle_encode, hip.ptr(m)
     dev = m.device
     while True:
         cap_str = cap_runs * 4
@@ -146,10 +155,10 @@ def rle_encode(masks, cap_runs=4096):
         ws = torch.empty(n, cap_runs, dtype=torch.int32, device=dev)
         meta = torch.empty(2, n, dtype=torch.int32, device=dev)
         out = torch.empty(n, cap_str, dtype=torch.uint8, device=dev)
-        hip.check(hip.lib().ym_rle_encode(hip.ptr(m), n, h, w, ctypes.c_void_p(counts.data_ptr()), cap_runs,
-                                          ctypes.c_void_p(meta[0].data_ptr()), ctypes.c_void_p(out.data_ptr()), cap_str,
-                                          ctypes.c_void_p(meta[1].data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 4,
-                                          hip.stream_ptr()), 'ym_rle_encode')
+        hip.check(encode(src, n, h, w, ctypes.c_void_p(counts.data_ptr()), cap_runs,
+                         ctypes.c_void_p(meta[0].data_ptr()), ctypes.c_void_p(out.data_ptr()), cap_str,
+                         ctypes.c_void_p(meta[1].data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 4,
+                         hip.stream_ptr()), 'ym_rle_encode')
         nruns, slen = meta.cpu().tolist()
         if min(slen) >= 0:
             break
@@ -161,7 +170,8 @@ def rle_encode(masks, cap_runs=4096):
 
 class MakeJson:
     """Detection dumps for the COCO API (reference common_utils.py:66-104, eval.py:59-67).  `add_mask` accepts the dense
-    [h, w] mask like the reference (host or device) or an RLE dict from `rle_encode` (batch the image's masks there)."""
+    [h, w] mask like the reference (host or device), one mask of a `PackedMasks`, or an RLE dict from `rle_encode` (batch the
+    image's masks there)."""
 
     def __init__(self, coco_label_map=None):
         from ..config import COCO_LABEL_MAP
@@ -180,7 +190,10 @@ class MakeJson:
                                'score': float(score)})
 
     def add_mask(self, image_id, category_id, segmentation, score):
-        if not isinstance(segmentation, dict):
+        if isinstance(segmentation, PackedMasks):            # one packed [h, w] mask (or [1, h, w])
+            pm = segmentation if segmentation.dim() == 3 else PackedMasks(segmentation.bits[None], segmentation.height, segmentation.width)
+            segmentation = rle_encode(pm)[0]
+        elif not isinstance(segmentation, dict):
             seg = torch.as_tensor(segmentation)
             if not seg.is_cuda:
                 seg = seg.cuda()

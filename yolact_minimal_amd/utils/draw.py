@@ -14,7 +14,8 @@ with cv2 on the host; here the masks, ids, scores and boxes stay where `after_nm
 
 Mask colours, blend, outline / plate geometry, draw order and the score formatting are the reference's, exactly (integer arithmetic
 throughout).  The label PIXELS are this package's own fixed-cell bitmap font (`utils/font.py`), not cv2's anti-aliased Hershey Duplex.
-The detections must be device tensors; there is no CPU path.
+The detections must be device tensors; there is no CPU path.  `mask_p` / the masks of `dets_padded` may be a `PackedMasks`
+(utils/packed_masks.py) instead of the float32 tensor: same frames, byte for byte, from 1/32 of the mask bytes.
 """
 import ctypes
 
@@ -24,6 +25,7 @@ import torch
 from .. import hip
 from ..config import COLORS
 from . import font as _font
+from .packed_masks import PackedMasks
 
 _res_cache = {}
 
@@ -72,14 +74,23 @@ def _launch(imgs, masks, ids, scores, boxes, counts, batch, max_det, cfg, flags,
         if nbytes == 0:
             raise RuntimeError('ym_draw_workspace_bytes: ' + L.ym_last_error().decode())
         ws = _scratch(device, nbytes)
-        hip.check(L.ym_draw_detections_batch(
-            hip.ptr(imgs, torch.uint8), hip.ptr(masks) if masks is not None else None, hip.ptr(ids, torch.int64),
+        # (PackedMasks: the mask term is read from the bit rows, one word serves 64 pixels of a detection; same output bytes)
+        packed = isinstance(masks, PackedMasks)
+        draw = L.ym_draw_detections_batch_packed if packed else L.ym_draw_detections_batch
+        hip.check(draw(
+            hip.ptr(imgs, torch.uint8), _mask_ptr(masks), hip.ptr(ids, torch.int64),
             hip.ptr(scores) if scores is not None else None, hip.ptr(boxes, torch.int32),
             hip.ptr(counts, torch.int32) if counts is not None else None, batch, max_det, h, w,
             hip.ptr(res['palette'], torch.uint8), res['palette_n'], int(cfg.num_classes), hip.ptr(res['names'], torch.uint8),
             res['num_names'], hip.ptr(res['font'], torch.int16), flags, float(visual_thre), fps_text,
             hip.ptr(out, torch.uint8), hip.ptr(cutout_total, torch.uint8) if cutout_total is not None else None,
             ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()), 'ym_draw_detections_batch')
+
+
+def _mask_ptr(masks):
+    if masks is None:
+        return None
+    return hip.ptr(masks.bits, torch.int64) if isinstance(masks, PackedMasks) else hip.ptr(masks)
 
 
 def _device_of(ids_p, what):
@@ -153,8 +164,9 @@ def cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg):
     if n:
         full = torch.empty(n, h, w, 3, dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
-            hip.check(hip.lib().ym_draw_cutout_objects(hip.ptr(frame, torch.uint8), hip.ptr(masks), n, h, w, hip.ptr(full, torch.uint8),
-                                                       hip.stream_ptr()), 'ym_draw_cutout_objects')
+            cut = hip.lib().ym_draw_cutout_objects_packed if isinstance(masks, PackedMasks) else hip.lib().ym_draw_cutout_objects
+            hip.check(cut(hip.ptr(frame, torch.uint8), _mask_ptr(masks), n, h, w, hip.ptr(full, torch.uint8), hip.stream_ptr()),
+                      'ym_draw_cutout_objects')
         for i, (x1, y1, x2, y2) in enumerate(boxes.tolist()):
             objs.append(full[i][y1:y2, x1:x2, :])
     if from_numpy:

@@ -9,7 +9,8 @@ Same call shapes and return conventions:
       score threshold;  batch size 1 only, like the reference (`.squeeze()` at :127-130).
   after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, img_name=None) ->
       (ids, scores, boxes int32[n,4] pixels, masks f32[n,img_h,img_w] in {0,1}) or four Nones;
-      `box_p` is scaled IN PLACE like the reference (:230).
+      `box_p` is scaled IN PLACE like the reference (:230).  `packed=True` (or `cfg.packed_masks`): the fourth result is a
+      `PackedMasks` (utils/packed_masks.py: 1 bit per pixel, written by the mask kernel itself; the float tensor never exists).
 The only host<->device synchronisation is one 4-byte read of the detection count at the end of `nms`
 (the reference's boolean-mask gathers synchronise several times per call).
 
@@ -21,6 +22,7 @@ import os
 import torch
 
 from .. import hip
+from .packed_masks import PackedMasks, pack_reference, unpack_reference  # noqa: F401  (re-exported)
 
 _anchor_cache = {}
 _ws_cache = {}
@@ -94,9 +96,22 @@ def nms(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
     return ids[:n], scores[:n], boxes[:n], coefs[:n], proto_p
 
 
-def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, img_name=None):
+def _want_packed(cfg, packed):
+    return bool(packed) or bool(cfg and getattr(cfg, 'packed_masks', False))
+
+
+def _new_masks(lead, img_h, img_w, device, packed):
+    if packed:
+        return torch.empty(*lead, img_h, (img_w + 63) // 64, dtype=torch.int64, device=device)
+    return torch.empty(*lead, img_h, img_w, dtype=torch.float32, device=device)
+
+
+def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, img_name=None, packed=False):
     if ids_p is None:
         return None, None, None, None
+    packed = _want_packed(cfg, packed)
+    if packed and not proto_p.is_cuda:
+        raise RuntimeError('yolact_minimal_amd.utils.output_utils.after_nms(packed=True) needs CUDA (HIP) tensors; there is no CPU path.')
 
     if cfg and getattr(cfg, 'visual_thre', 0) > 0:
         keep = class_p >= cfg.visual_thre
@@ -112,22 +127,30 @@ def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, im
     hp, wp, k = proto_p.shape
     do_crop = not (cfg and getattr(cfg, 'no_crop', False))
     box_c = box_p if box_p.is_contiguous() else box_p.contiguous()
-    with torch.cuda.device(device):
-        masks = torch.empty(n, img_h, img_w, dtype=torch.float32, device=device)
+    if packed and device.index == torch.cuda.current_device():
+        # (the tensors live on the current device: no device switch around the launch, as in nms_batch)
+        masks = torch.empty(n, img_h, (img_w + 63) >> 6, dtype=torch.int64, device=device)
         box_px = torch.empty(n, 4, dtype=torch.int32, device=device)
         _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, 1, n, hp, wp, k, img_h, img_w, do_crop, masks, box_px)
+    else:
+        with torch.cuda.device(device):
+            masks = _new_masks((n,), img_h, img_w, device, packed)
+            box_px = torch.empty(n, 4, dtype=torch.int32, device=device)
+            _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, 1, n, hp, wp, k, img_h, img_w, do_crop, masks, box_px)
     if box_c is not box_p:
         box_p.copy_(box_c)              # keep the reference's in-place scaling visible to the caller
-    return ids_p, class_p, box_px, masks
+    return ids_p, class_p, box_px, PackedMasks._wrap(masks, img_h, img_w) if packed else masks
 
 
 def _after_nms_launch(proto, coefs, boxes, counts, batch, max_det, hp, wp, k, img_h, img_w, do_crop, masks, box_px):
     L = hip.lib()
     nbytes = L.ym_after_nms_batch_workspace_bytes(max_det, hp, wp, img_h, img_w)
     ws = _scratch(proto.device, nbytes) if nbytes else None
-    hip.check(L.ym_after_nms_batch(hip.ptr(proto), hip.ptr(coefs), hip.ptr(boxes), hip.ptr(counts, torch.int32) if counts is not None else None,
-                                   batch, max_det, hp, wp, k, img_h, img_w, int(do_crop), hip.ptr(masks), hip.ptr(box_px, torch.int32),
-                                   ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes, hip.stream_ptr()),
+    # (int64 masks = the words of PackedMasks: the packed kernel, same arguments otherwise)
+    fn = L.ym_after_nms_batch_packed if masks.dtype == torch.int64 else L.ym_after_nms_batch
+    hip.check(fn(hip.ptr(proto), hip.ptr(coefs), hip.ptr(boxes), hip.ptr(counts, torch.int32) if counts is not None else None,
+                 batch, max_det, hp, wp, k, img_h, img_w, int(do_crop), hip.ptr(masks, masks.dtype), hip.ptr(box_px, torch.int32),
+                 ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes, hip.stream_ptr()),
               'ym_after_nms_batch')
 
 
@@ -213,10 +236,12 @@ def nms_batch(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
     return BatchDetections(counts, ids, scores, boxes, coefs, proto_out)
 
 
-def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True):
+def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
     """`after_nms` for every image of a `BatchDetections` in one launch set (all images resized to the same img_h x img_w, as in a
     bench / fixed-size serving batch).  Returns a list of per-image 4-tuples like `after_nms` — or, with `sync=False`, the padded
-    device tensors (ids, scores, boxes_px, masks, counts) without any host read."""
+    device tensors (ids, scores, boxes_px, masks, counts) without any host read.  `packed=True` (or `cfg.packed_masks`): the masks
+    are `PackedMasks` (padded: `[B, max_det, img_h, ceil(img_w / 64)]` words)."""
+    packed = _want_packed(cfg, packed)
     device = dets.proto.device
     batch, md = dets.ids.shape
     _, hp, wp, k = dets.proto.shape
@@ -224,10 +249,12 @@ def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True):
     if cfg and getattr(cfg, 'save_lincomb', False):
         raise NotImplementedError('draw_lincomb (visualisation, reference output_utils.py:276-324) is out of scope')
     with torch.cuda.device(device):
-        masks = torch.empty(batch, md, img_h, img_w, dtype=torch.float32, device=device)
+        masks = _new_masks((batch, md), img_h, img_w, device, packed)
         box_px = torch.empty(batch, md, 4, dtype=torch.int32, device=device)
         _after_nms_launch(dets.proto.contiguous(), dets.coefs, dets.boxes, dets.counts, batch, md, hp, wp, k, img_h, img_w, do_crop,
                           masks, box_px)
+    if packed:
+        masks = PackedMasks._wrap(masks, img_h, img_w)
     if not sync:
         return dets.ids, dets.scores, box_px, masks, dets.counts
     out = []
@@ -236,7 +263,7 @@ def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True):
         if n == 0:
             out.append((None, None, None, None))
             continue
-        r = (dets.ids[b, :n], dets.scores[b, :n], box_px[b, :n], masks[b, :n])
+        r = (dets.ids[b, :n], dets.scores[b, :n], box_px[b, :n], masks[b][:n])
         if vt > 0:                                               # detect.py's score filter (per detection, so it commutes)
             keep = r[1] >= vt
             r = tuple(t[keep] for t in r) if bool(keep.any()) else (None, None, None, None)
