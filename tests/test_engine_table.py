@@ -152,16 +152,18 @@ def test_tuner_rows_reach_the_table_only_through_the_reference_digest_gate(tmp_p
     base = {'M1156_N256_C1024_k1_s1_seg1_r0': [32, 32, 1, 4, 22, 40, 4]}
     path.write_text(json.dumps(base))
     rows = {'M1156_N256_C1024_k1_s1_seg1_r0_tp': [32, 32, 1, 4, 22, 0, 0]}
-    seen = []
+    seen, narrowed = [], []
 
     def red(candidate):
         seen.append(json.load(open(candidate)))
+        narrowed.append(os.environ.get(G.KEYS_ENV))
         return 1
 
     with pytest.raises(G.GateRefused):
         G.merge_rows(rows, str(path), runner=red)
     assert json.loads(path.read_text()) == base                         # untouched
     assert seen[0] == {**base, **rows}                                  # the tests saw the candidate, not the committed table
+    assert narrowed == [','.join(sorted(rows))] and G.KEYS_ENV not in os.environ      # ... and the per-row test only the merged keys
     assert not list(tmp_path.parent.glob('tuned_candidate_*'))
     merged = G.merge_rows(rows, str(path), runner=lambda candidate: 0)
     assert merged == {**base, **rows} and json.loads(path.read_text()) == merged
@@ -169,9 +171,55 @@ def test_tuner_rows_reach_the_table_only_through_the_reference_digest_gate(tmp_p
     import ast
     src = open(os.path.join(G.REPO, 'tests', 'test_gpu_forward.py')).read()
     names = {n.name for n in ast.walk(ast.parse(src)) if isinstance(n, ast.FunctionDef)}
-    for t in G.GATE_TESTS:
-        assert t.split('::')[1] in names, t
+    rowsrc = open(os.path.join(G.REPO, 'tests', 'test_gpu_forward_fullsize.py')).read()
+    in_file = {'tests/test_gpu_forward.py': names,
+               'tests/test_gpu_forward_fullsize.py': {n.name for n in ast.walk(ast.parse(rowsrc)) if isinstance(n, ast.FunctionDef)}}
+    for t in G.GATE_TESTS:                                              # each in the file its id names
+        assert t.split('::')[1] in in_file[t.split('::')[0]], t
+    assert sum(t.startswith('tests/test_gpu_forward.py::') for t in G.GATE_TESTS) >= 2         # the digests stay in the gate
     assert "'throughput'" in src
+    # every forward row, of any image size, is launched at its own shape against fp64 under the candidate table: the per-row test is
+    # part of the gate, reads the table through the engine (YM_TUNED_PATH) and the gate's key list
+    assert 'tests/test_gpu_forward_fullsize.py::test_every_tuned_forward_launch_at_full_size' in G.GATE_TESTS
+    assert 'tuned_table()' in rowsrc and 'tuned_gfx950.json\'' not in rowsrc and f"KEYS_ENV = '{G.KEYS_ENV}'" in rowsrc
     # and the tuner goes through it
     tool = open(os.path.join(G.REPO, 'tools', 'tune_forward.py')).read()
     assert 'merge_rows' in tool and 'json.dump(table, open(E.TUNED_PATH' not in tool
+
+
+def test_every_forward_key_of_the_committed_table_resolves_to_a_layer():
+    """tests/conv_geometry.py, the geometry rule of tests/test_gpu_forward_fullsize.py: every forward key of the table is a layer of
+    some model at an image size that is a multiple of 32 from 128 to 864 and a batch of 1 / 2 / 4 / 8 / 16; strided keys get a
+    consistent input side, `_L5` keys five levels; and every row names a kernel variant that exists for its shape (no quiet
+    fall-back inside ym_conv2d_fwd).  A new row for a size outside the rule fails here, before anyone needs a GPU."""
+    from tests import conv_geometry as CG
+    from yolact_minimal_amd import engine as E
+    table = json.load(open(E.TUNED_PATH))
+    keys = CG.forward_keys(table)
+    assert len(keys) > 1000 and all(not k.startswith(('T_', 'W_')) for k in keys)
+    assert len(keys) + sum(k.startswith(('T_', 'W_')) for k in table) == len(table)        # nothing is neither
+    pyramids = 0
+    for key in keys:
+        g = CG.resolve(key)
+        assert g is not None, f'{key}: no layer of any model / image size / batch has this shape'
+        if g.levels:
+            pyramids += 1
+            assert len(g.levels) == 5 and g.batch * sum(s * s for s in g.levels) == g.M and g.stride == 1, g.describe()
+            assert list(g.levels) == CG.resnet_chain(g.size)[3:], g.describe()
+        else:
+            assert g.batch * g.ho * g.ho == g.M and (g.h + 2 * g.pad - g.k) // g.stride + 1 == g.ho, g.describe()
+            if g.stride > 1:
+                assert g.h in CG.resnet_chain(g.size) and g.h > g.ho, g.describe()
+            if g.C == 4:
+                assert g.h == g.size and (g.k, g.stride, g.pad) in ((7, 2, 3), (4, 4, 0)), g.describe()
+        assert g.batch in (1, 2, 4, 8, 16) and g.size % 32 == 0 and 128 <= g.size <= 864, g.describe()
+        plan, mma = CG.launch_plan(g, table[key])
+        assert CG.silent_fallback(g, plan, mma) is None, (g.describe(), table[key], CG.silent_fallback(g, plan, mma))
+    assert pyramids >= 30
+    # the rule refuses what it should: a size that is no multiple of 32, a side no chain has, a pyramid of another depth
+    assert CG.resolve('M10201_N256_C256_k3_s1_seg1_r0') is None                 # 101 x 101: a side of 808 px, no multiple of 32
+    assert CG.resolve('M10000_N256_C256_k3_s1_seg1_r0')[-5:] == (1, 800, 100, 100, None)
+    assert CG.resolve('M1156_N256_C256_k3_s2_seg1_r0')[-5:] == (1, 544, 68, 34, None)
+    assert CG._input_side(544, 9, 3, 2, 256) == (17, 1) and CG._input_side(544, 9, 3, 2, 4) is None      # (an odd input side)
+    assert CG.resolve('M1364_N256_C256_k3_s1_seg1_r0_L4') is None
+    assert CG.resolve('T_M1156_N256_C256_k3_s1') is None
