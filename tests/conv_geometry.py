@@ -65,8 +65,8 @@ class Geometry(NamedTuple):
 
 
 def is_forward_key(key):
-    p = plan_transfer.parse(key)
-    return p is not None and p[0][0] == ''
+    f = plan_transfer.parse_key(key)
+    return f is not None and f.prefix == ''
 
 
 def forward_keys(table):
@@ -91,17 +91,15 @@ def _input_side(size, ho, k, stride, cin):
 
 def resolve(key):
     """Geometry of a forward key, or None when no layer of any model / size / batch matches it."""
-    p = plan_transfer.parse(key)
-    if p is None or p[0][0] != '':
+    if not is_forward_key(key):
         return None
-    (_, k, stride, seg, r, lev, suffix, _), M, N, C = p
-    nseg, residual = int(seg or 1), (r == '1')
+    _, M, N, C, k, stride, nseg, residual, lev, suffix = plan_transfer.parse_key(key)
     for batch in BATCHES:
         if M % batch:
             continue
         for size in SIZES:
             if lev:
-                if lev != '_L5' or stride != 1:
+                if lev != 5 or stride != 1:
                     return None
                 levels = tuple(fpn_levels(size))
                 if batch * sum(s * s for s in levels) == M:
@@ -122,16 +120,17 @@ KNOWN_STAGES = (0, 2, 3, 22, 23, 24, 33, 34, 42, 43, 44, 46, 48, 52, 53, 54)
 
 
 def launch_plan(g, row):
-    """(ConvPlan, mma) that reach the descriptor of the launch a row is read for -- what `_Conv.bind` / `_Conv.apply_mma` /
-    `_bind_pyramid` (engine.py) and `_configure_conv` (train_engine.py) do with an exact row."""
-    from yolact_minimal_amd.conv_plan import ConvPlan
-    plan, mma = ConvPlan.from_row(row), 0
-    if g.levels:                                   # the pyramid launch reads tile, K split and tail only
-        plan = ConvPlan(plan.tile_m, plan.tile_n, plan.ksplit, tail_tiles=plan.tail_tiles, tail_ksplit=plan.tail_ksplit)
-    elif g.suffix.startswith('_mma') and not plan.wave:      # (a wave row of this pipe = the f32 wave kernel for a tiny layer)
-        mma = int(g.suffix[4:])
-        plan = plan._replace(stages=3 if plan.stages == 3 else 0)
-    return plan, mma
+    """(ConvPlan, mma) that reach the descriptor of the launch a row is read for: the engines' own resolution (conv_launch.py: the
+    inference policy, for an `_st` row the training one) over a table that holds this row alone."""
+    from yolact_minimal_amd import conv_launch as CL
+    assert plan_transfer.mode() != 'only'                         # (the row itself is meant, not a neighbour's)
+    base, table = g.key[:len(g.key) - len(g.suffix)], {g.key: row}
+    shape = (g.M, g.N, -(-(g.k * g.k * g.C) // 32), g.nseg)
+    eligible = g.C % 32 == 0 and not g.levels
+    if g.suffix == '_st':
+        return CL.train_overrides(CL.train_plan(table, base, shape, stats=True), table, base, 0, eligible)
+    mma = int(g.suffix[4:]) if g.suffix.startswith('_mma') else 0
+    return CL.infer_plan(table, base, shape, 'throughput' if g.suffix == '_tp' else 'latency', mma, eligible, pyramid=bool(g.levels))[:2]
 
 
 def family(g, plan, mma):

@@ -84,24 +84,15 @@ def test_pipeline_checks_the_hardware_queue_count(monkeypatch):
 def _desc_from_key(key, row):
     """A descriptor with the GEMM shape a forward-conv key names (M = B Ho Wo: any factorisation gives the same plan) and the
     row's tiling; pointers are placeholders (the planner never dereferences them)."""
-    import re
+    from yolact_minimal_amd import conv_launch, plan_transfer
     from yolact_minimal_amd.conv_plan import ConvPlan
-    from yolact_minimal_amd.hip import ConvDesc
-    m = re.match(r'M(\d+)_N(\d+)_C(\d+)_k(\d+)_s(\d+)_seg(\d+)_r(\d+)', key)
-    M, N, C, k, s, nseg, res = map(int, m.groups())
+    _, M, N, C, k, s, nseg, res, _, _ = plan_transfer.parse_key(key)
     ho = max(h for h in range(1, 1200) if M % (h * h) == 0)
-    d = ConvDesc()
+    cuts = [0, N] if nseg == 1 else [0, N - N // 3 - 12, N - N // 3, N][:nseg + 1]
+    segs = [(n0, n1, 0x2000, ho * ho * (n1 - n0), n1 - n0, 0) for n0, n1 in zip(cuts, cuts[1:])]
+    d = conv_launch.conv_desc(M // (ho * ho), ho * s, ho * s, C, N, k, k, s, k // 2, ho, ho, -(-(k * k * C) // 32) * 32, segs)
     d.inp = d.weight = 0x1000
     d.residual = 0x1000 if res else None
-    d.B, d.H, d.W, d.Cin, d.Cout = M // (ho * ho), ho * s, ho * s, C, N
-    d.KH = d.KW = k
-    d.stride, d.pad, d.Ho, d.Wo = s, k // 2, ho, ho
-    d.k_pad = -(-(k * k * C) // 32) * 32
-    cuts = [0, N] if nseg == 1 else [0, N - N // 3 - 12, N - N // 3, N][:nseg + 1]
-    d.nseg = nseg
-    for i in range(nseg):
-        d.seg[i].n_begin, d.seg[i].n_end = cuts[i], cuts[i + 1]
-        d.seg[i].out, d.seg[i].pitch, d.seg[i].batch_stride = 0x2000, cuts[i + 1] - cuts[i], ho * ho * (cuts[i + 1] - cuts[i])
     ConvPlan.from_row(row).apply(d)
     d.tile_counters = 0x3000
     return d
@@ -113,15 +104,14 @@ def test_planner_accepts_every_forward_row_of_the_committed_table():
     Rows for the segmented head (3 outputs) and the pyramid launch (`_L<n>`) are planned by the engine with their real segment
     tables and are covered by the GPU forward tests."""
     import ctypes
-    import re
-    from yolact_minimal_amd import engine as E, hip
+    from yolact_minimal_amd import engine as E, hip, plan_transfer
     from yolact_minimal_amd.conv_plan import ConvPlan
     lib = hip.lib()
     table = json.load(open(E.TUNED_PATH))
-    pat = re.compile(r'^M\d+_N\d+_C\d+_k\d+_s\d+_seg1_r[01](_tp)?$')
     checked = wave = split = 0
     for key, row in table.items():
-        if not pat.match(key) or '_C4_' in key:                                   # (the 7x7 stem on the 4-channel image: its own mode)
+        f = plan_transfer.parse_key(key)
+        if f.prefix or f.nseg != 1 or f.levels or f.suffix not in ('', '_tp') or f.C == 4:     # (the stem on the 4-channel image: its own mode)
             continue
         d = _desc_from_key(key, row)
         lib.ym_conv2d_workspace_bytes(None)                                        # plants a known message in ym_last_error()
@@ -223,3 +213,91 @@ def test_every_forward_key_of_the_committed_table_resolves_to_a_layer():
     assert CG._input_side(544, 9, 3, 2, 256) == (17, 1) and CG._input_side(544, 9, 3, 2, 4) is None      # (an odd input side)
     assert CG.resolve('M1364_N256_C256_k3_s1_seg1_r0_L4') is None
     assert CG.resolve('T_M1156_N256_C256_k3_s1') is None
+
+
+SIDES = (8, 10, 13, 16, 20, 23, 26, 32, 40, 46, 50, 64, 80, 92, 100, 128, 160, 184, 200)    # as in test_plan_transfer.py
+POLICY = {      # configuration -> (cases, sha256 of the canonical result list), recorded at the commit before conv_launch.py existed
+    'infer latency mma0 nearest=1': (2214, '2a20ec2c7ed65fa824cdbdc2573632d254d0eedd5630daa31a7c9f50aafa68d6'),
+    'infer latency mma0 nearest=only': (2214, '971d267760c8cfdc3093cccd3732cfa70f099967137fa0beeeb81788e5e3c6c8'),
+    'infer latency mma0 nearest=0': (2214, 'e2bf2fd0e223229345a81e66c1b70e115a1d62477305949c0b584c22eaea0a8e'),
+    'infer latency mma3 nearest=1': (2214, '1342834748066fdbb083b62327d978fd875b0c65121d62761d1cf0e134e63695'),
+    'infer latency mma3 nearest=only': (2214, 'a6c7c80b1d143766ff6faee289ddc478693e26505476926e054b7b91272e957a'),
+    'infer latency mma3 nearest=0': (2214, 'b10a54f175c372a2696238d70778520b1e98bfd749228ff86caddbc0d036d752'),
+    'infer latency mma6 nearest=1': (2214, 'bd03dead7e4191f431875a71c301987b1814f5cf5b84a1f59ed658c67fa9409f'),
+    'infer latency mma6 nearest=only': (2214, 'e6852a2666dc5c55e67fc6a0b856b0e82980ba545002195bec671d5b265ddec7'),
+    'infer latency mma6 nearest=0': (2214, '45f0f7c5eeb63f26fb9238a979bc3baee0a74e54b5dcc6162f98fd1f44f981ef'),
+    'infer throughput mma0 nearest=1': (2214, 'f59c6a11c74b8f9c5bccde3725f6ef6dda21d4c578bdd6013e63f60de6c32d18'),
+    'infer throughput mma0 nearest=only': (2214, '971d267760c8cfdc3093cccd3732cfa70f099967137fa0beeeb81788e5e3c6c8'),
+    'infer throughput mma0 nearest=0': (2214, '6150a061bf1c34fa84a057bea8267cedaa2ce70eeda63a6256649e217c81e656'),
+    'infer throughput mma3 nearest=1': (2214, '1342834748066fdbb083b62327d978fd875b0c65121d62761d1cf0e134e63695'),
+    'infer throughput mma3 nearest=only': (2214, 'a6c7c80b1d143766ff6faee289ddc478693e26505476926e054b7b91272e957a'),
+    'infer throughput mma3 nearest=0': (2214, 'b10a54f175c372a2696238d70778520b1e98bfd749228ff86caddbc0d036d752'),
+    'infer throughput mma6 nearest=1': (2214, '02039c8ec571aa7926fd3200999231f016566b3f1b7511c87d60378037a3af3c'),
+    'infer throughput mma6 nearest=only': (2214, 'e6852a2666dc5c55e67fc6a0b856b0e82980ba545002195bec671d5b265ddec7'),
+    'infer throughput mma6 nearest=0': (2214, '3a777ef16996e01870119a81ec97dfd879409c189aea3c51ab027d65b8fadae3'),
+    'infer latency mma3 nearest=1 no_tuned': (2214, 'a350180249fa5ddbd8c65f25412be03559ac38d268ae90d7c2e6064065dfd828'),
+    'train mma0 nearest=1': (6226, 'd926dc18df4c5772cbc5295f1185a82ead41dfe66dc6a1d076bb82f249017004'),
+    'train mma0 nearest=only': (6226, '1e120195359da1c5d8958fa97ea223b47be527f4cb34af87f90970985dd07bb6'),
+    'train mma0 nearest=0': (6226, '2065c0bd4973668142cbf8d6dfd158553c76769324861a212cb9e648dccbbc63'),
+    'train mma3 nearest=1': (6226, '49a5f5ef8f05cd6c0336e8139db55067df465c2fc9db574f09de26c814324892'),
+    'train mma3 nearest=only': (6226, '6a88a180a9fe0e88b86fff77c37c25ddeb28382cd7c652c1ea72fac8c7a54b07'),
+    'train mma3 nearest=0': (6226, 'ebeb7ccc1e3b9780bdba7a884c21f0d9f2a958ef9bef9c5bcd2f46d118207777'),
+    'train mma0 nearest=1 force=43': (6226, '6ae48d0058a1e1236bbfef52f0987c67a52a7c0e260bd442253af70c1fc35a88'),
+}
+
+
+def test_plan_policy_is_what_the_engines_did_before_it_moved(monkeypatch):
+    """conv_launch.py over every shape of the committed table and the same shapes at M = side^2 (shapes without a row), per build
+    mode, matrix pipe, transfer mode, YM_NO_TUNED and YM_FORCE_STAGES: count and SHA-256 of [key, the eight plan fields, mma,
+    source] (training: [key, stats, plan fields, mma]; weight gradient: [key, msplit, lds_buffers]).  POLICY was recorded by walking
+    the same cases through _Conv.bind / apply_mma / _bind_pyramid (fake tensors) and _configure_conv / _configure_wgrad (bare
+    descriptors built from the key) of the commit before this module existed, reading the plan back from the descriptor."""
+    import hashlib
+    from yolact_minimal_amd import conv_launch as CL, engine as E, plan_transfer as PT
+    from yolact_minimal_amd.conv_plan import ConvPlan
+    for v in ('YM_FORCE_STAGES', 'YM_FORCE_GRID'):
+        monkeypatch.delenv(v, raising=False)
+    table = json.load(open(E.TUNED_PATH))
+    keys = [PT.parse_key(k) for k in table]
+
+    def shifted(shapes):
+        return sorted(set(shapes) | {(side * side,) + sh[1:] for sh in shapes for side in SIDES})
+
+    def nkt(C, k):
+        return -(-(k * k * C) // 32)
+
+    def digest(rows):
+        return len(rows), hashlib.sha256(json.dumps(rows, separators=(',', ':')).encode()).hexdigest()
+
+    got = {}
+    cases = shifted({f[1:9] for f in keys if f.prefix == ''})
+    for mode, mma, near, no_tuned in [(m, p, n, False) for m in ('latency', 'throughput') for p in (0, 3, 6) for n in ('1', 'only', '0')] + \
+            [('latency', 3, '1', True)]:
+        monkeypatch.setenv('YM_TUNED_NEAREST', near)
+        rows = []
+        for M, N, C, k, s, nseg, r, lev in cases:
+            key = PT.forward_key(M, N, C, k, s, nseg, r, lev)
+            plan, pipe, source, _ = CL.infer_plan(table, key, (M, N, nkt(C, k), nseg), mode, mma, C % 32 == 0 and not lev,
+                                                  no_tuned=no_tuned, pyramid=bool(lev))
+            rows.append([key, *plan, pipe, source])
+        got[f'infer {mode} mma{mma} nearest={near}' + (' no_tuned' if no_tuned else '')] = digest(rows)
+    fwd = shifted({f[1:6] + (f.residual,) for f in keys if f.prefix == '' and f.nseg == 1 and not f.levels})
+    dgrad, wgrad = (shifted({f[1:6] for f in keys if f.prefix == pre}) for pre in ('T_', 'W_'))
+    for mma, near, force in [(p, n, '') for p in (0, 3) for n in ('1', 'only', '0')] + [(0, '1', '43')]:
+        monkeypatch.setenv('YM_TUNED_NEAREST', near)
+        monkeypatch.setenv('YM_FORCE_STAGES', force)
+        rows = []
+        for key, M, N, C, k, dg in [(PT.forward_key(M, N, C, k, s, 1, r), M, N, C, k, False) for M, N, C, k, s, r in fwd] + \
+                [(PT.dgrad_key(*c), *c[:4], True) for c in dgrad]:
+            for stats in ((False,) if dg else (False, True)):
+                plan = CL.train_plan(table, key, (M, N, nkt(C, k), 1), stats)
+                plan, pipe = CL.train_overrides(plan or ConvPlan(), table, key, mma, C % 32 == 0)
+                rows.append([key, stats, *plan, pipe])
+        rows += [[key, *(CL.wgrad_plan(table, key) or (0, 0))] for key in (PT.wgrad_key(*c) for c in wgrad)]
+        got[f'train mma{mma} nearest={near}' + (f' force={force}' if force else '')] = digest(rows)
+    assert got == POLICY, {k: v for k, v in got.items() if v != POLICY.get(k)}
+    # the configurations tell the policy's branches apart
+    assert all(n > 1000 for n, _ in POLICY.values())
+    for a, b in (('infer latency mma0 nearest=1', 'infer throughput mma0 nearest=1'), ('infer latency mma0 nearest=1', 'infer latency mma3 nearest=1'),
+                 ('infer latency mma0 nearest=1', 'infer latency mma0 nearest=only'), ('train mma0 nearest=1', 'train mma3 nearest=1')):
+        assert POLICY[a][1] != POLICY[b][1], (a, b)

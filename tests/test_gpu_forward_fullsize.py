@@ -67,7 +67,7 @@ class Launch:
     """Operands, output buffers with guard bands, descriptor and fp64 reference of one row's launch."""
 
     def __init__(self, g, plan, mma, gen, counters):
-        from yolact_minimal_amd import hip
+        from yolact_minimal_amd import conv_launch, hip
         self.g, self.plan = g, plan
         b, N, C, k = g.batch, g.N, g.C, g.k
         cin = 3 if C == 4 else C
@@ -116,23 +116,14 @@ class Launch:
                 self.bufs.append(t)
                 self.regions.append(t[:, ANCHORS_BEFORE:ANCHORS_BEFORE + n])
                 segs.append((self.cuts[i], self.cuts[i + 1], t.data_ptr() + ANCHORS_BEFORE * c * 4, n_total * c, na * c, self.acts[i]))
-        # ---- descriptor (what engine._Conv.bind / _bind_pyramid / train_engine._conv_forward set) ----
-        d = self.desc = hip.ConvDesc()
+        # ---- descriptor: the engines' own builder ----
+        hi, ho = self.sides[0]
+        d = self.desc = conv_launch.conv_desc(b, hi, hi, C, N, k, k, g.stride, g.pad, ho, ho, k_pad, segs,
+                                              levels=self.sides if g.levels else None)
         d.inp, d.weight = self.x_all.data_ptr(), self.wp.data_ptr()
         d.scale = self.scale.data_ptr() if self.scale is not None else None
         d.shift = self.shift.data_ptr() if self.shift is not None else None
         d.residual = self.residual.data_ptr() if self.residual is not None else None
-        hi, ho = self.sides[0]
-        d.B, d.H, d.W, d.Cin, d.Cout = b, hi, hi, C, N
-        d.KH, d.KW, d.stride, d.pad, d.Ho, d.Wo, d.k_pad = k, k, g.stride, g.pad, ho, ho, k_pad
-        if g.levels:
-            d.nlevels = len(g.levels)
-            for l, s in enumerate(g.levels):
-                d.level_h[l], d.level_w[l] = s, s
-        d.nseg = len(segs)
-        for i, (n0, n1, ptr, bstride, pitch, act) in enumerate(segs):
-            d.seg[i].n_begin, d.seg[i].n_end, d.seg[i].out = n0, n1, ptr
-            d.seg[i].batch_stride, d.seg[i].pitch, d.seg[i].act = bstride, pitch, act
         plan.apply(d)
         d.mma = mma
         d.tile_counters = counters.data_ptr()

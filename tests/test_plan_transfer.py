@@ -10,6 +10,7 @@ import os
 import pytest
 
 from yolact_minimal_amd import plan_transfer as PT
+from yolact_minimal_amd.conv_plan import ConvPlan
 
 TABLE = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'yolact_minimal_amd',
                                     'tuned_gfx950.json')))
@@ -18,6 +19,13 @@ TABLE = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.absp
 def test_every_table_key_parses():
     bad = [k for k in TABLE if PT.parse(k) is None]
     assert not bad, bad[:5]
+    build = {'': PT.forward_key, 'T_': lambda *a: PT.dgrad_key(*a[:5], a[8]), 'W_': lambda *a: PT.wgrad_key(*a[:5])}
+    for key in TABLE:                 # the builders and the parser are inverses of each other
+        f = PT.parse_key(key)
+        made = build[f.prefix](*f[1:])
+        assert made == key and PT.parse_key(made) == f, key
+    assert PT.parse_key(PT.dgrad_key(9, 8, 32, 3, 2)) == ('T_', 9, 8, 32, 3, 2, None, False, 0, '')
+    assert PT.parse_key(PT.wgrad_key(9, 8, 32, 3, 2)) == ('W_', 9, 8, 32, 3, 2, None, False, 0, '')
 
 
 def test_exact_row_wins(monkeypatch):
@@ -101,25 +109,15 @@ def _lib():
 
 
 def _desc(hip, M_side, N, C, k, s, nseg, residual, transposed=False):
-    d = hip.ConvDesc()
+    from yolact_minimal_amd import conv_launch
+    pad = k // 2
+    # data gradient: (Ho, Wo) = dx, (H, W) = dy
+    side_in = (M_side + 2 * pad - k) // s + 1 if transposed else (M_side - 1) * s + k - 2 * pad
+    step = -(-N // nseg)
+    segs = [(i * step, min(N, (i + 1) * step), 0x10000, M_side * M_side * N, N, 0) for i in range(nseg)]
+    d = conv_launch.conv_desc(1, side_in, side_in, C, N, k, k, s, pad, M_side, M_side, -(-(k * k * C) // 32) * 32, segs, transposed=transposed)
     d.inp = d.weight = 0x10000
     d.residual = 0x10000 if residual else None
-    pad = k // 2
-    if transposed:         # data gradient: (Ho, Wo) = dx, (H, W) = dy
-        d.Ho = d.Wo = M_side
-        d.H = d.W = (M_side + 2 * pad - k) // s + 1
-    else:
-        d.Ho = d.Wo = M_side
-        d.H = d.W = (M_side - 1) * s + k - 2 * pad
-    d.B, d.Cin, d.Cout, d.KH, d.KW, d.stride, d.pad = 1, C, N, k, k, s, pad
-    d.k_pad = -(-(k * k * C) // 32) * 32
-    d.nseg = nseg
-    step = -(-N // nseg)
-    for i in range(nseg):
-        d.seg[i].n_begin, d.seg[i].n_end = i * step, min(N, (i + 1) * step)
-        d.seg[i].out = 0x10000
-        d.seg[i].batch_stride, d.seg[i].pitch = M_side * M_side * N, N
-    d.transposed = int(transposed)
     d.tile_counters = 0x10000
     return d
 
@@ -167,16 +165,14 @@ def test_transferred_rows_are_plans_the_library_accepts(monkeypatch):
         pre, k, s, seg, r, lev, suf, stem = fam
         for side in (8, 10, 13, 16, 20, 23, 26, 32, 40, 46, 50, 64, 80, 92, 100, 128, 160, 184, 200):
             M = side * side
-            sig = f'{pre}M{M}_N{N}_C{C}_k{k}_s{s}' + (f'_seg{seg}_r{r}' if seg else '') + suf
             nseg = int(seg) if seg else 1
+            sig = PT.dgrad_key(M, N, C, k, s, suf) if pre else PT.forward_key(M, N, C, k, s, nseg, r == '1', suffix=suf)
             d = _desc(hip, side, N, C, k, s, nseg, r == '1', transposed=(pre == 'T_'))
             row, src = PT.lookup(TABLE, sig, M, N, d.k_pad // 32, nseg)
             if row is None:
                 continue
             assert src.startswith('nearest:')
-            d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = row[0], row[1], row[2], row[3], row[4]
-            d.tail_tiles, d.tail_ksplit = row[5], row[6]
-            d.grid_wgs = row[7] if len(row) > 7 else 0
+            ConvPlan.from_row(row).apply(d)
             if d.kwaves and pre == 'T_':
                 continue
             assert _launchable(row, d.k_pad // 32), (sig, src, row)

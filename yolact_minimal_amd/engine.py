@@ -23,9 +23,9 @@ import sys
 import torch
 import torch.nn as nn
 
-from . import hip, plan_transfer
-from .conv_plan import ConvPlan, from_entry
-from .hip import ConvDesc, ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU
+from . import conv_launch, hip, plan_transfer
+from .conv_plan import ConvPlan
+from .hip import ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU
 
 
 def _round_up(x, m):
@@ -39,6 +39,10 @@ _tuned = None
 def conv_mma():
     """YM_CONV_MMA = 0 (default: f32 MFMA, the parity mode) | 3 (bf16x3) | 6 (bf16x6): see ym_conv_desc.mma."""
     return int(os.environ.get('YM_CONV_MMA', '0') or 0)
+
+
+def no_tuned():
+    return os.environ.get('YM_NO_TUNED', '0') == '1'
 
 
 def autotune_on():
@@ -59,7 +63,7 @@ def tuned_table():
     global _tuned
     if _tuned is None:
         _tuned = {}
-        if os.path.exists(TUNED_PATH) and os.environ.get('YM_NO_TUNED', '0') != '1':
+        if os.path.exists(TUNED_PATH) and not no_tuned():
             with open(TUNED_PATH) as f:
                 _tuned = json.load(f)
             if autotune_on() and os.path.exists(user_cache_path()):
@@ -89,28 +93,25 @@ def _store_user_rows(rows):
     os.replace(tmp, path)
 
 
+def record_rows(rows):
+    """Rows measured in this process (InferEngine.autotune, the training sweeps): added to the process table and, with
+    YM_AUTOTUNE=1, written through to the per-user cache that later processes overlay on the shipped table."""
+    tuned_table().update(rows)
+    plan_transfer._index_cache.clear()
+    if autotune_on():
+        try:
+            _store_user_rows(rows)
+        except OSError as e:
+            print(f'yolact_minimal_amd: could not write {user_cache_path()}: {e}', file=sys.stderr)
+
+
 _build_mode = ['latency']
 
 
 def _entry(sig, M=0, N=0, nkt=0, nseg=1, with_source=False):
-    """Tuned entry of a conv shape for the engine being built.  'latency' (one request at a time: the default) reads `sig`;
-    'throughput' (the slots of a RequestPipeline with several requests in flight) reads `sig + '_tp'` first: choices that spread a
-    launch over every CU (tail splits, one-wave workgroups) shorten a lone request and cost throughput when other requests want
-    those CUs -- tools/tune_forward.py --inflight N measures them on the pipeline's own img/s.
-    A shape without a row (another --img_size / batch) takes the row of the nearest tuned shape of its family, re-derived for its
-    M (plan_transfer.py); `with_source` also returns where the row came from ('table' / 'nearest:<key>' / 'heuristic')."""
-    t = tuned_table()
-    hit, src = None, 'heuristic'
-    if _build_mode[0] == 'throughput' and plan_transfer.mode() != 'only':
-        hit = t.get(sig + '_tp')
-        src = 'table'
-    if hit is None:
-        if M > 0:
-            hit, src = plan_transfer.lookup(t, sig, M, N, nkt, nseg)
-        else:
-            hit, src = t.get(sig), 'table'
-            if hit is None:
-                src = 'heuristic'
+    """Tuned entry of a conv shape for the engine being built (conv_launch.entry with the process table and build mode);
+    `with_source` also returns where the row came from ('table' / 'nearest:<key>' / 'heuristic')."""
+    hit, src = conv_launch.entry(tuned_table(), sig, (M, N, nkt, nseg), _build_mode[0])
     return (hit, src) if with_source else hit
 
 
@@ -188,57 +189,30 @@ class _Conv:
         assert cin == self.cin_pad, (self.name, cin, self.cin_pad)
         ho = (h + 2 * self.pad - self.kh) // self.stride + 1
         wo = (w + 2 * self.pad - self.kw) // self.stride + 1
-        d = ConvDesc()
+        d = self.desc = conv_launch.conv_desc(b, h, w, cin, self.cout, self.kh, self.kw, self.stride, self.pad, ho, wo, self.k_pad, segs)
         d.inp = x.data_ptr()
         d.residual = residual.data_ptr() if residual is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout = b, h, w, cin, self.cout
-        d.KH, d.KW, d.stride, d.pad, d.Ho, d.Wo, d.k_pad = self.kh, self.kw, self.stride, self.pad, ho, wo, self.k_pad
-        d.nseg = len(segs)
-        for i, (n0, n1, base_ptr, bstride, pitch, act) in enumerate(segs):
-            d.seg[i].n_begin, d.seg[i].n_end = n0, n1
-            d.seg[i].out = base_ptr
-            d.seg[i].batch_stride, d.seg[i].pitch, d.seg[i].act = bstride, pitch, act
-        self.desc = d
         self._bind_params()
         self.out_hw = (ho, wo)
         self.flops = 2.0 * b * ho * wo * self.cout * self.kh * self.kw * self.cin
-        self.sig = f'M{b * ho * wo}_N{self.cout}_C{cin}_k{self.kh}_s{self.stride}_seg{len(segs)}_r{int(residual is not None)}'
+        self.sig = plan_transfer.forward_key(b * ho * wo, self.cout, cin, self.kh, self.stride, len(segs), residual is not None)
         self._shape = (b * ho * wo, self.cout, self.k_pad // 32, len(segs))
-        row, self.plan_source = _entry(self.sig, *self._shape, with_source=True)
-        self._hit = hit = from_entry(row)
-        p = self.plan
-        if hit is not None and p.tile_m == p.tile_n == p.ksplit == p.kwaves == 0:
-            self.plan = hit
-        self.apply_mma(conv_mma())                  # (writes the plan into the descriptor)
+        self._resolve(conv_mma())
         return ho, wo
 
-    def tuned_key(self):
-        return self.sig + (f'_mma{self.mma}' if self.mma else '')
+    def _resolve(self, mma, bound=None, pyramid=False):
+        """Resolve the plan from the tuned table (conv_launch.infer_plan) and write it into the descriptor."""
+        d = self.desc
+        self.plan, self.mma, self.plan_source, self._hit = conv_launch.infer_plan(
+            tuned_table(), self.sig, self._shape, _build_mode[0], mma, not self.stem and d.Cin % 32 == 0 and d.nlevels == 0, self.plan,
+            no_tuned(), pyramid, bound)
+        self.plan.apply(d)
+        d.mma = self.mma
 
     def apply_mma(self, mma):
         """Select the matrix pipe of this conv (ym_conv_desc.mma) where the split-bf16 kernel applies: Cin % 32 == 0, workgroup
-        kernel.  Tile / split-K / tail choices are kept; the operand staging falls back to the register double buffer."""
-        d = self.desc
-        ok = mma in (3, 6) and not self.stem and d.Cin % 32 == 0 and d.nlevels == 0
-        self.mma = mma if ok else 0
-        plan = None
-        if self.mma and os.environ.get('YM_NO_TUNED', '0') != '1':      # this pipe's own row: exact, or the nearest tuned shape's
-            plan = from_entry(plan_transfer.lookup(tuned_table(), self.tuned_key(), *self._shape)[0])
-        if plan is None:
-            plan = self._hit                # (no entry for this pipe: the f32 choice, incl. its wave kernel for tiny layers)
-            # (not the weight-stationary kernel, whose tiles this pipe lacks; nor a TRANSFERRED wave-kernel row: not measured on it)
-            if self.mma and plan is not None and (plan.weight_stationary or (self.plan_source != 'table' and plan.wave)):
-                plan = ConvPlan()
-        if plan is not None and os.environ.get('YM_NO_TUNED', '0') != '1':     # each matrix pipe has its own measured choice
-            self.plan = plan
-            if plan.wave:                                           # the tuner may prefer the f32 wave kernel for a tiny layer
-                self.mma = 0
-        if self.mma:
-            # split modes stage through registers: 0/2 = one register set (fewer VGPRs: two workgroups per CU on the big tiles),
-            # 3 = two sets (the tile being converted arrived an iteration earlier: wins where occupancy is one wave per SIMD anyway)
-            self.plan = self.plan._replace(stages=3 if self.plan.stages == 3 else 0)
-        self.plan.apply(d)
-        d.mma = self.mma
+        kernel.  The table hit of the bind is kept; this pipe's own row, if any, is read."""
+        self._resolve(mma, (self._hit, self.plan_source))
 
 
 def _bind_pyramid(layer, pyr, batch, shapes, segs):
@@ -246,29 +220,15 @@ def _bind_pyramid(layer, pyr, batch, shapes, segs):
     rows, cin = pyr.shape
     assert cin == layer.cin_pad and layer.stride == 1 and layer.pad == layer.kh // 2 and len(shapes) <= 5
     assert rows == sum(batch * h * w for h, w in shapes)
-    d = ConvDesc()
+    d = layer.desc = conv_launch.conv_desc(batch, shapes[0][0], shapes[0][1], cin, layer.cout, layer.kh, layer.kw, 1, layer.pad,
+                                           shapes[0][0], shapes[0][1], layer.k_pad, segs, levels=shapes)
     d.inp = pyr.data_ptr()
-    d.B, d.H, d.W, d.Cin, d.Cout = batch, shapes[0][0], shapes[0][1], cin, layer.cout
-    d.KH, d.KW, d.stride, d.pad, d.Ho, d.Wo, d.k_pad = layer.kh, layer.kw, 1, layer.pad, shapes[0][0], shapes[0][1], layer.k_pad
-    d.nlevels = len(shapes)
-    for l, (h, w) in enumerate(shapes):
-        d.level_h[l], d.level_w[l] = h, w
-    d.nseg = len(segs)
-    for i, (n0, n1, base_ptr, bstride, pitch, act) in enumerate(segs):
-        d.seg[i].n_begin, d.seg[i].n_end = n0, n1
-        d.seg[i].out = base_ptr
-        d.seg[i].batch_stride, d.seg[i].pitch, d.seg[i].act = bstride, pitch, act
-    layer.desc = d
     layer._bind_params()
     layer.out_hw = shapes[0]
     layer.flops = 2.0 * rows * layer.cout * layer.kh * layer.kw * layer.cin
-    layer.sig = f'M{rows}_N{layer.cout}_C{cin}_k{layer.kh}_s1_seg{len(segs)}_r0_L{len(shapes)}'
+    layer.sig = plan_transfer.forward_key(rows, layer.cout, cin, layer.kh, 1, len(segs), levels=len(shapes))
     layer._shape = (rows, layer.cout, layer.k_pad // 32, len(segs))
-    row, layer.plan_source = _entry(layer.sig, *layer._shape, with_source=True)
-    layer._hit = hit = from_entry(row)
-    if hit is not None:                # (tile, K split and tail; set_mma writes the whole row, whose stages the pyramid launch ignores)
-        layer.plan = ConvPlan(hit.tile_m, hit.tile_n, hit.ksplit, tail_tiles=hit.tail_tiles, tail_ksplit=hit.tail_ksplit)
-    layer.plan.apply(d)
+    layer._resolve(0, pyramid=True)        # (set_mma later writes the whole row, whose stages the pyramid launch ignores)
 
 
 class InferEngine:
@@ -302,7 +262,7 @@ class InferEngine:
         try:
             with torch.cuda.device(device):
                 self._build()
-                if autotune_on() and os.environ.get('YM_NO_TUNED', '0') != '1':
+                if autotune_on() and not no_tuned():
                     self._autotune_missing()
         finally:
             _build_mode[0] = prev
@@ -314,15 +274,10 @@ class InferEngine:
         if not todo:
             return
         rows = self.autotune(iters=10, skip=have)
-        tuned_table().update(rows)
-        plan_transfer._index_cache.clear()
         for c in self.convs:
             if c.sig in rows:
                 c.plan_source, c._hit = 'autotuned', ConvPlan.from_row(rows[c.sig])
-        try:
-            _store_user_rows(rows)
-        except OSError as e:
-            print(f'yolact_minimal_amd: could not write {user_cache_path()}: {e}', file=sys.stderr)
+        record_rows(rows)
 
     # ---- construction ------------------------------------------------------------------------
     def _buf(self, *shape):

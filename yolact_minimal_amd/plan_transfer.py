@@ -22,6 +22,7 @@ transfer itself: tools/size_bench.py)."""
 import math
 import os
 import re
+from collections import namedtuple
 
 from .conv_plan import ConvPlan, WgradPlan
 
@@ -38,6 +39,32 @@ _index_cache = {}
 def mode():
     v = os.environ.get('YM_TUNED_NEAREST', '1')
     return 'off' if v in ('0', 'off') else ('only' if v == 'only' else 'on')
+
+
+# the fields of a key: prefix '' forward / 'T_' data gradient / 'W_' weight gradient; nseg and residual of forward keys only; levels of a
+# pyramid launch; suffix '' / '_st' / '_tp' / '_mma<n>'
+Key = namedtuple('Key', 'prefix M N C k stride nseg residual levels suffix', defaults=(None, False, 0, ''))
+
+
+def forward_key(M, N, C, k, stride, nseg=1, residual=False, levels=0, suffix=''):
+    return f'M{M}_N{N}_C{C}_k{k}_s{stride}_seg{nseg}_r{int(residual)}' + (f'_L{levels}' if levels else '') + suffix
+
+
+def dgrad_key(M, N, C, k, stride, suffix=''):
+    return f'T_M{M}_N{N}_C{C}_k{k}_s{stride}{suffix}'
+
+
+def wgrad_key(M, N, C, k, stride):
+    return f'W_M{M}_N{N}_C{C}_k{k}_s{stride}'
+
+
+def parse_key(sig):
+    """The `Key` of a table key, or None."""
+    m = _SIG.match(sig)
+    if not m:
+        return None
+    pre, M, N, C, k, s, seg, r, lev, suf = m.groups()
+    return Key(pre or '', int(M), int(N), int(C), int(k), int(s), int(seg) if seg else None, r == '1', int(lev[2:]) if lev else 0, suf or '')
 
 
 def parse(sig):

@@ -11,16 +11,15 @@ RCCL) — no ATen convolution, batch-norm or pooling kernel is ever called.  The
 head outputs (matching, OHEM ranking, cross-entropy, smooth-L1, mask BCE) is `yolact_minimal_amd/loss.py`.
 """
 import ctypes
-import math
 import os
 import weakref
 
 import torch
 import torch.nn.functional as F
 
-from . import hip, plan_transfer
-from .conv_plan import ConvPlan, WgradPlan, from_entry
-from .hip import ConvDesc, WgradDesc, ACT_NONE, ACT_RELU, ACT_TANH
+from . import conv_launch, hip, plan_transfer
+from .conv_plan import ConvPlan, WgradPlan
+from .hip import WgradDesc, ACT_NONE, ACT_RELU, ACT_TANH
 
 _scratch = {}
 _desc_cache = {}      # shape key -> (descriptor with every shape-dependent field set, ...): see _conv_forward
@@ -45,15 +44,9 @@ def _tuning():
 def _remember(key, hit):
     """A row the inline sweep measured: kept for tools/autotune_train.py (dump_new_entries) and, with YM_AUTOTUNE=1, written through
     to the per-user cache that later processes overlay on the shipped table (engine.tuned_table)."""
-    _table()[key] = hit
+    from .engine import record_rows
     _new_entries[key] = hit
-    from .engine import autotune_on, _store_user_rows, user_cache_path
-    if autotune_on():
-        try:
-            _store_user_rows({key: hit})
-        except OSError as e:
-            import sys
-            print(f'yolact_minimal_amd: could not write {user_cache_path()}: {e}', file=sys.stderr)
+    record_rows({key: hit})
 
 
 def train_mma():
@@ -86,24 +79,9 @@ def _time_launch(fn, iters=5):
 
 
 def _configure_conv(d, key, stats=False):
-    """Set tile/ksplit/kwaves of a ConvDesc from the tuned table (or sweep it when YM_TUNE_TRAIN=1).  `stats`: the launch carries
-    fused BatchNorm sums, which the persistent kernel does not do: `<key>_st` holds the per-item choice measured for such launches
-    where the plain entry (shared with inference) selects the persistent kernel."""
-    M_rows = d.B * d.Ho * d.Wo
-    plan = None
-    if plan_transfer.mode() != 'only':
-        plan = from_entry((_table().get(key + '_st') if stats else None) or _table().get(key))
-    if plan is None and not _tuning() and plan_transfer.mode() != 'off':
-        # another --img_size / batch: the row of the nearest tuned shape of the family, re-derived for this M (plan_transfer.py);
-        # with fused statistics the `_st` family competes with the plain one, the donor nearer in M wins
-        only = plan_transfer.mode() == 'only'
-        donors = [(abs(math.log2(nb[1] / M_rows)), i, k) for i, k in enumerate(([key + '_st'] if stats else []) + [key])
-                  for nb in [plan_transfer.nearest(_table(), k, only)] if nb is not None]
-        if donors:
-            k = min(donors)[2]
-            plan = from_entry(plan_transfer.lookup(_table(), k, M_rows, d.Cout, d.k_pad // 32, d.nseg)[0])
-            if plan is not None and stats and k == key:
-                plan = plan.with_bn_sums()
+    """Set the plan of a forward / data-gradient ConvDesc: the tuned table's (conv_launch.train_plan), else a sweep where those are
+    on (YM_TUNE_TRAIN=1 / YM_AUTOTUNE=1), then the overrides (conv_launch.train_overrides).  `stats`: fused BatchNorm sums."""
+    plan = conv_launch.train_plan(_table(), key, (d.B * d.Ho * d.Wo, d.Cout, d.k_pad // 32, d.nseg), stats, _tuning())
     if plan is None and _tuning():
         M, nkt = d.B * d.Ho * d.Wo, d.k_pad // 32
         big = scratch(torch.device('cuda', torch.cuda.current_device()), 1 << 28)
@@ -137,31 +115,12 @@ def _configure_conv(d, key, stats=False):
             if t < best * 0.98:
                 best, plan = t, cand
         _remember(key, plan.to_row())
-    if plan is not None:
-        plan.apply(d)
-    force = os.environ.get('YM_FORCE_STAGES')        # experiments / tests: e.g. 43 = every conv the persistent kernel covers runs on it
-    if force:
-        d.tile_m, d.tile_n, d.kwaves, d.stages, d.grid_wgs = 64, 64, 0, int(force), int(os.environ.get('YM_FORCE_GRID', '0'))
-        if d.tail_tiles and d.ksplit > 1:
-            d.tail_tiles = d.tail_ksplit = 0
-    mma = train_mma()
-    if mma and d.Cin % 32 == 0 and d.nlevels == 0:
-        # opt-in FAST training mode (YM_TRAIN_MMA=3): forward and data-gradient convs on the bf16 MFMA (split-bf16 products, see
-        # ym_conv_desc.mma).  NOT the parity mode: per-product error ~2^-17 instead of 2^-24, which the ill-conditioned backward of
-        # a random-init net amplifies beyond the fp32 reference's own noise (tests keep the default, f32).
-        plan = from_entry(_table().get(key + f'_mma{mma}'))
-        if plan is not None:            # (tile, K split, K waves and tail: the staging and grid of the f32 choice stay)
-            plan._replace(stages=d.stages, grid_wgs=d.grid_wgs).apply(d)
-        if d.kwaves == 0:
-            d.mma, d.stages = mma, 0
+    plan, d.mma = conv_launch.train_overrides(plan or ConvPlan.of(d), _table(), key, train_mma(), d.Cin % 32 == 0 and d.nlevels == 0)
+    plan.apply(d)
 
 
 def _configure_wgrad(d, key):
-    plan = from_entry(_table().get(key), WgradPlan) if plan_transfer.mode() != 'only' else None
-    if plan is None and not _tuning():
-        p = plan_transfer.parse(key)
-        if p:
-            plan = from_entry(plan_transfer.lookup(_table(), key, p[1], p[2], 0)[0], WgradPlan)
+    plan = conv_launch.wgrad_plan(_table(), key, _tuning())
     if plan is None and _tuning():
         big = scratch(torch.device('cuda', torch.cuda.current_device()), 1 << 28)
         best, plan = 1e30, WgradPlan(0, 2)
@@ -391,45 +350,29 @@ def _conv_forward(x, wp, k_pad, cout_pad, kh, kw, stride, pad, shift, act, resid
            None if segs is None else tuple((n0, n1, bs, pt, a) for n0, n1, _, bs, pt, a in segs), train_mma())
     ent = _desc_cache.get(key)
     if ent is None:
-        d = ConvDesc()
-        d.B, d.H, d.W, d.Cin, d.Cout, d.KH, d.KW = b, h, w, cin, cout_pad, kh, kw
-        d.stride, d.pad, d.Ho, d.Wo, d.k_pad = stride, pad, ho, wo, k_pad
-        if segs is None:
-            d.nseg = 1
-            d.seg[0].n_begin, d.seg[0].n_end = 0, cout_pad
-            d.seg[0].batch_stride, d.seg[0].pitch, d.seg[0].act = ho * wo * cout_pad, cout_pad, act
-        else:
-            d.nseg = len(segs)
-            for i, (n0, n1, ptr, bstride, pitch, a) in enumerate(segs):
-                d.seg[i].n_begin, d.seg[i].n_end = n0, n1
-                d.seg[i].batch_stride, d.seg[i].pitch, d.seg[i].act = bstride, pitch, a
-        # pointers of this first call: the inline sweep (YM_TUNE_TRAIN=1) launches with them, and the two queries below look at
-        # their alignment (torch allocations are 256-byte aligned, so every later call answers the same)
-        d.inp, d.weight = x.data_ptr(), wp.data_ptr()
-        d.shift = shift.data_ptr() if shift is not None else None
-        d.residual = residual.data_ptr() if residual is not None else None
-        if segs is None:
-            y = out if out is not None else torch.empty(b, ho, wo, cout_pad, device=x.device, dtype=torch.float32)
-            d.seg[0].out = y.data_ptr()
-        else:
-            for i, sg in enumerate(segs):
-                d.seg[i].out = sg[2]
-        if cin != 4:
-            _configure_conv(d, f'M{b * ho * wo}_N{cout_pad}_C{cin}_k{kh}_s{stride}_seg{d.nseg}_r{int(residual is not None)}', stats=bn_stats is not None)
-        d.tile_counters = _tile_counters(x.device)
-        fuses = bn_stats is not None and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
-        ent = _desc_cache[key] = (d, fuses, hip.conv_workspace_bytes(d))
-    d, fused, ws_bytes = ent
+        d = conv_launch.conv_desc(b, h, w, cin, cout_pad, kh, kw, stride, pad, ho, wo, k_pad,
+                                  [(0, cout_pad, None, ho * wo * cout_pad, cout_pad, act)] if segs is None else segs)
+    else:
+        d, fused, ws_bytes = ent
     d.inp, d.weight, d.k_pad = x.data_ptr(), wp.data_ptr(), k_pad
     d.shift = shift.data_ptr() if shift is not None else None
     d.residual = residual.data_ptr() if residual is not None else None
     if segs is None:
-        if y is None:
-            y = out if out is not None else torch.empty(b, ho, wo, cout_pad, device=x.device, dtype=torch.float32)
+        y = out if out is not None else torch.empty(b, ho, wo, cout_pad, device=x.device, dtype=torch.float32)
         d.seg[0].out = y.data_ptr()
     else:
         for i, sg in enumerate(segs):
             d.seg[i].out = sg[2]
+    if ent is None:
+        # first use of the shape: the inline sweep (YM_TUNE_TRAIN=1) launches with this call's pointers, and the two queries below
+        # look at their alignment (torch allocations are 256-byte aligned, so every later call answers the same)
+        if cin != 4:
+            _configure_conv(d, plan_transfer.forward_key(b * ho * wo, cout_pad, cin, kh, stride, d.nseg, residual is not None),
+                            stats=bn_stats is not None)
+        d.tile_counters = _tile_counters(x.device)
+        fused = bn_stats is not None and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
+        ws_bytes = hip.conv_workspace_bytes(d)
+        _desc_cache[key] = (d, fused, ws_bytes)
     if fused:
         d.bn_sum, d.bn_sumsq = bn_stats.data_ptr(), bn_stats.data_ptr() + cout_pad * 8
     ws = scratch(x.device, ws_bytes)
@@ -454,15 +397,11 @@ def _conv_dgrad(dz, weight, cout_pad, x_shape, stride, pad, add=None, out=None, 
            bn_bwd is not None)
     ent = _desc_cache.get(key)
     if ent is None:
-        d = ConvDesc()
-        d.B, d.H, d.W, d.Cin, d.Cout, d.KH, d.KW = b, dz.shape[1], dz.shape[2], cout_pad, cin, kh, kw
-        d.stride, d.pad, d.Ho, d.Wo, d.k_pad, d.nseg = stride, pad, h, w, kh * kw * cout_pad, 1
-        d.seg[0].n_begin, d.seg[0].n_end = 0, cin
-        d.seg[0].batch_stride, d.seg[0].pitch, d.seg[0].act = h * w * cin, cin, ACT_NONE
-        d.transposed = 1
-        d.inp, d.weight, d.seg[0].out = dz.data_ptr(), wd.data_ptr(), dx.data_ptr()
+        d = conv_launch.conv_desc(b, dz.shape[1], dz.shape[2], cout_pad, cin, kh, kw, stride, pad, h, w, kh * kw * cout_pad,
+                                  [(0, cin, dx.data_ptr(), h * w * cin, cin, ACT_NONE)], transposed=True)
+        d.inp, d.weight = dz.data_ptr(), wd.data_ptr()
         d.residual = add.data_ptr() if add is not None else None
-        _configure_conv(d, f'T_M{b * h * w}_N{cin}_C{cout_pad}_k{kh}_s{stride}')
+        _configure_conv(d, plan_transfer.dgrad_key(b * h * w, cin, cout_pad, kh, stride))
         d.tile_counters = _tile_counters(dz.device)
         fuses = bn_bwd is not None and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
         ent = _desc_cache[key] = (d, hip.conv_workspace_bytes(d), fuses)
@@ -763,7 +702,7 @@ def _conv_wgrad_now(x, dz, weight_shape, stride, pad, weight_param=None, dw=None
         if segments is not None:
             d.row_end[0], d.row_end[1] = segments[0], segments[1]
             d.dw_seg[0], d.dw_seg[1] = segments[2].data_ptr(), segments[3].data_ptr()
-        _configure_wgrad(d, f'W_M{b * dz.shape[1] * dz.shape[2]}_N{dz.shape[3]}_C{cin_p}_k{kh}_s{stride}')
+        _configure_wgrad(d, plan_transfer.wgrad_key(b * dz.shape[1] * dz.shape[2], dz.shape[3], cin_p, kh, stride))
         nbytes = hip.lib().ym_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
         if nbytes == 0:
             raise RuntimeError('ym_conv2d_wgrad_workspace_bytes: ' + hip.lib().ym_last_error().decode())
