@@ -123,6 +123,11 @@ typedef struct {
     int32_t grid_wgs;        /* persistent kernel (stages 4x): workgroups to launch; 0 = as many as the CUs hold (LDS-limited, at most  */
                              /* 4 per CU), never more than there are work items.  Wave kernel with DMA rings (kwaves > 0, stages 22-24):  */
                              /* waves per workgroup, 0 = 4 (1 / 2 with kwaves <= that: single tiles are balanced over the CUs)            */
+    int32_t bn_ordered;      /* (in what was the struct's trailing padding: its size is unchanged.)  != 0 with bn_sum: ORDERED statistics.  */
+                             /* bn_sum is then the base of a partial buffer double[ym_conv2d_bn_partial_rows(desc)][2][Cout] (8-byte        */
+                             /* aligned, no zero fill needed) and bn_sumsq is unused: instead of atomics, exactly one workgroup stores its   */
+                             /* column sums to part[row][0][c] (bn_sum term) and part[row][1][c] (bn_sumsq term) for every row and every     */
+                             /* c < Cout; ym_bn_partials_finish then adds the rows in a fixed order.  Forward statistics and bnb_* sums.     */
 } ym_conv_desc;
 
 /* y = act(conv(x, w) * scale + shift + residual), one launch (plus a reduce launch if K is split).
@@ -134,6 +139,19 @@ size_t ym_sizeof_conv_desc(void);                      /* for bindings: must equ
 size_t ym_conv2d_workspace_bytes(const ym_conv_desc* d);
 int ym_conv2d_tile_counters(const ym_conv_desc* d);   /* output tiles of the chosen plan (0 if K is not split) */
 int ym_conv2d_fuses_bn_stats(const ym_conv_desc* d);
+int ym_conv2d_bn_partial_rows(const ym_conv_desc* d); /* rows of the bn_ordered partial buffer the chosen plan writes (M tiles, or   */
+                                                      /* walkers x wave rows of the weight-stationary kernel); 0 if the statistics do  */
+                                                      /* not fuse (ym_conv2d_fuses_bn_stats(desc) == 0)                                */
+/* Ordered sum of per-row partials part[rows][2][C] (fp64) into sums = sum[C] | sumsq[C] (fp64, overwritten), the layout
+ * ym_bn_train_fwd_stats / ym_bn_train_bwd_apply read.  The order is fixed: for each of the two terms and each channel, slice s
+ * (s = 0..15) adds the rows k = s, s + 16, s + 32, ... in ascending k starting from 0.0; then the 16 slice sums are added in
+ * ascending s starting from 0.0.  The result depends on the partials alone, not on how the launch was scheduled. */
+int ym_bn_partials_finish(const void* part, int rows, int C, void* sums, ym_stream_t s);
+/* Launches, since the library was loaded, whose sums on a statistic or gradient path end in floating-point atomics (their result
+ * depends on the order in which workgroups retire): ym_conv2d_fwd with bn_sum and bn_ordered == 0, ym_bn_train_fwd / ym_bn_train_bwd /
+ * ym_act_bias_bwd (dbias) with the small workspace, ym_swin_window_attention_bwd.  Host-side, monotonic; a step that leaves it where
+ * it was is bit-reproducible.  (The reported loss scalars are summed with atomics too; nothing reads them back, they do not count.) */
+int64_t ym_unordered_sum_launches(void);
 int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t workspace_bytes, ym_stream_t s);
 
 /* ---- Swin-T backward + AdamW (row a18 under loss.backward(); reference train.py:62-63,126) ---------------------------
@@ -280,7 +298,10 @@ int ym_wgrad_reduce_batch(const ym_wgrad_reduce_item* items_dev, int n_items, ui
 /* BatchNorm2d forward in TRAIN mode on a conv output y [M][C] (C % 4 == 0): batch mean / biased variance
  * (fp64 accumulation), running stats updated in place with `momentum` (unbiased variance, torch semantics),
  * out = relu?( (y-mean)*invstd*gamma + beta + residual? ).  save_mean/save_invstd [C] feed the backward.
- * workspace >= 16*C bytes. */
+ * workspace >= 16*C bytes; with ym_bn_train_fwd_workspace_bytes(M, C) the statistics pass writes per-workgroup partials to
+ * workspace + 16*C as double[rows][2][C], rows = (ym_bn_train_fwd_workspace_bytes(M, C) - 16*C) / (16*C), and sums them in the
+ * order of ym_bn_partials_finish (no atomics); the first 16*C bytes then hold sum[C] | sumsq[C]. */
+size_t ym_bn_train_fwd_workspace_bytes(int64_t M, int C);
 int ym_bn_train_fwd(const float* y, int64_t M, int C, const float* gamma, const float* beta, float eps, float momentum,
                     float* running_mean, float* running_var, const float* residual, int relu, float* out,
                     float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, ym_stream_t s);

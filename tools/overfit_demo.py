@@ -127,7 +127,21 @@ def serving_agrees(net, cfg, data, device, size, depth=4):
     return same, n_det
 
 
-def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', seed=0, lr=None, log=print, eval_every=0, log_every=100):
+def state_digest(tr):
+    """sha256 over every parameter and BatchNorm buffer (`state_dict` order) and then the optimizer's momentum buffers: two runs of
+    the deterministic mode (`--deterministic`) print the same digest."""
+    import hashlib
+    h = hashlib.sha256()
+    for _, v in tr.net.state_dict().items():
+        h.update(v.detach().cpu().contiguous().numpy().tobytes())
+    for name in ('buf', 'exp_avg_sq'):
+        if hasattr(tr.opt, name):
+            h.update(getattr(tr.opt, name).detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', seed=0, lr=None, log=print, eval_every=0, log_every=100,
+        deterministic=False):
     from yolact_minimal_amd.config import build_cfg
     from yolact_minimal_amd.modules.yolact import Yolact
     from yolact_minimal_amd.trainer import Trainer, init_distributed, shard_batch
@@ -142,7 +156,7 @@ def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', see
         cfg.lr = lr
     torch.manual_seed(seed)
     net = Yolact(cfg)
-    tr = Trainer(net, cfg, device, world, local_rank % torch.cuda.device_count())
+    tr = Trainer(net, cfg, device, world, local_rank % torch.cuda.device_count(), deterministic=True if deterministic else None)
     if rank != 0:
         log = lambda *_: None                                                   # noqa: E731
     data = make_dataset(n_images, size, seed)
@@ -176,6 +190,7 @@ def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', see
         if rank != 0:
             dist.barrier()                       # (rank 0 scores alone, like train.py:162-174)
             return None
+    digest = state_digest(tr) if deterministic else None        # (before the evaluation: the trained state and nothing else)
     table, row_box, row_mask, found = evaluate(net, cfg, data, device, size)
     strong = evaluate.detections_above_0p3
     # the same detector through `--traditional_nms` (greedy per-class NMS, utils/output_utils.py:84-123 + cython_nms.pyx)
@@ -188,7 +203,8 @@ def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', see
     return dict(cfg=cfg_name, size=size, images=n_images, batch=batch, steps=steps, train_s=round(train_s, 1), losses=hist,
                 box_map=row_box[1:], mask_map=row_mask[1:], images_with_detections=found, curve=curve, table=table,
                 serving_path_identical_pictures=same, detections=n_det, detections_above_0p3=strong, world=world, replicas_identical=replicas_identical,
-                box_map_traditional_nms=trad_box[1:], mask_map_traditional_nms=trad_mask[1:])
+                box_map_traditional_nms=trad_box[1:], mask_map_traditional_nms=trad_mask[1:],
+                **({'state_digest': digest} if deterministic else {}))
 
 
 def main():
@@ -202,8 +218,11 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--eval-every', type=int, default=0)
     ap.add_argument('--log-every', type=int, default=100)
+    ap.add_argument('--deterministic', action='store_true', help='ordered BatchNorm sums (train_engine._DETERMINISTIC): the result '
+                    'carries a sha256 `state_digest` of the trained state that is the same from run to run')
     a = ap.parse_args()
-    r = run(a.steps, a.images, a.size, a.batch, a.cfg, seed=a.seed, lr=a.lr, eval_every=a.eval_every, log_every=a.log_every)
+    r = run(a.steps, a.images, a.size, a.batch, a.cfg, seed=a.seed, lr=a.lr, eval_every=a.eval_every, log_every=a.log_every,
+            deterministic=a.deterministic)
     if r is not None:                            # (rank 0)
         print(r.pop('table'))
         print('OVERFIT ' + json.dumps(r) if r['world'] > 1 else json.dumps(r))

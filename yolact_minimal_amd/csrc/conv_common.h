@@ -74,6 +74,7 @@ struct ConvP {
     const float* bnb_gamma;
     const float* bnb_beta;
     int bnb_relu;
+    int bn_ordered;    // 1: no atomics, every workgroup that owns a statistics row stores it to bn_sum = part[row][2][Cout] (ym_conv_desc.bn_ordered)
     int* counters;     // optional per-output-tile arrival counters: fused split-K finish (see ym_conv_desc.tile_counters)
     int B, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo, Kpad;
     int M, HoWo, nkt, ksplit, kt_per_split, tiles_m, tiles_n;
@@ -224,4 +225,6 @@ size_t ym_conv_pers_lds_bytes(int bm, int bn, int ns, bool defer);
 // 256x64: a workgroup keeps `bn` output channels x all of K in LDS and walks M blocks of `bm` rows).  grid_wgs: workgroups (0 = as
 // many as the CUs hold).  YM_EINVAL: no such variant / too much LDS.
 int ym_launch_conv_ws(const ymk::ConvP& p, int bm, int bn, int nstg, int grid_wgs, hipStream_t st);
+// rows of BatchNorm partial sums that launch writes in ordered mode (ConvP::bn_ordered): one per (M walker, wave row)
+int ym_conv_ws_partial_rows(int M, int Cout, int bm, int bn, int nkt, int nstg, int grid_wgs);
 size_t ym_conv_ws_lds_bytes(int bm, int bn, int nkt, int nstg);

@@ -736,7 +736,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(const ConvP p) {
         }
         if (p.bn_sum) {
             // train-mode BatchNorm statistics of THIS conv output, fused: per-workgroup column sums of the tile
-            // (fp64), then one fp64 atomic per channel per workgroup.
+            // (fp64), then one fp64 atomic per channel per workgroup (or, ordered mode, one store).
             __syncthreads();                       // every lane is done reading the staged tile
             double* R = reinterpret_cast<double*>(smem);   // [RPP][BN][2] doubles (<= 16 KB)
 #pragma unroll
@@ -749,8 +749,17 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(const ConvP p) {
                 double S = 0.0, Q = 0.0;
 #pragma unroll
                 for (int r = 0; r < RPP; ++r) { S += R[(r * BN + tid) * 2]; Q += R[(r * BN + tid) * 2 + 1]; }
-                atomicAdd(p.bn_sum + n0 + tid, S);
-                atomicAdd(p.bn_sumsq + n0 + tid, Q);
+                if (p.bn_ordered) {
+                    // ordered mode: this workgroup is the only one that runs the epilogue of output tile (tile_m, tile_n) (with a K
+                    // split: the last arriver), so it owns row tile_m of part[tiles_m][2][Cout] for its channels -- plain stores, and
+                    // ym_bn_partials_finish adds the rows in a fixed order.  A tile without a live row stores zeros.
+                    double* row = p.bn_sum + (size_t)tile_m * 2 * p.Cout;
+                    row[n0 + tid] = S;
+                    row[p.Cout + n0 + tid] = Q;
+                } else {
+                    atomicAdd(p.bn_sum + n0 + tid, S);
+                    atomicAdd(p.bn_sumsq + n0 + tid, Q);
+                }
             }
         }
         YM_STAMP(3);
@@ -1059,6 +1068,14 @@ extern "C" int ym_conv2d_fuses_bn_stats(const ym_conv_desc* d) {
     return (vec_epilogue(d) && (pl.slots() == 1 || d->tile_counters) && d->kwaves == 0) ? 1 : 0;
 }
 
+extern "C" int ym_conv2d_bn_partial_rows(const ym_conv_desc* d) {
+    Plan pl;
+    if (make_plan(d, &pl) != YM_OK) return 0;
+    if (!(vec_epilogue(d) && (pl.slots() == 1 || d->tile_counters) && d->kwaves == 0)) return 0;      // (ym_conv2d_fuses_bn_stats)
+    if (pl.ws) return ym_conv_ws_partial_rows(pl.M, d->Cout, pl.bm, pl.bn, pl.nkt, pl.ws_ring, d->grid_wgs);
+    return pl.tiles_m;                           // one row per M tile (a stride-2 data gradient: the class-padded tiles)
+}
+
 extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t workspace_bytes, ym_stream_t s) {
     Plan pl;
     int rc = make_plan(d, &pl);
@@ -1114,7 +1131,7 @@ extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t work
         YM_REQUIRE(pl.tail_tiles == 0 || ((uintptr_t)workspace & 15) == 0, "conv: tail split needs a 16-byte aligned workspace");
         p.vec = (vec_epilogue(d) && ((uintptr_t)workspace & 15) == 0) ? 1 : 0;
     }
-    p.bn_sum = d->bn_sum; p.bn_sumsq = d->bn_sumsq;
+    p.bn_sum = d->bn_sum; p.bn_sumsq = d->bn_sumsq; p.bn_ordered = (d->bn_sum && d->bn_ordered) ? 1 : 0;
     p.bnb_y = d->bnb_y; p.bnb_out = d->bnb_out; p.bnb_mean = d->bnb_mean; p.bnb_invstd = d->bnb_invstd;
     p.bnb_gamma = d->bnb_gamma; p.bnb_beta = d->bnb_beta; p.bnb_relu = d->bnb_relu;
     p.trace = nullptr; p.trace_epoch = nullptr; p.trace_ring = 0; p.trace_stride = 0; p.trace_rt = 0; p.trace_hw = nullptr;
@@ -1142,7 +1159,7 @@ extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t work
     p.fd_wo = FastDiv::make((unsigned)d->Wo); p.fd_cin = FastDiv::make((unsigned)d->Cin); p.fd_kw = FastDiv::make((unsigned)d->KW);
     p.ws_bytes = (unsigned)(need < 0xFFFFFFF0ull ? need : 0);
     if (d->bn_sum) {
-        YM_REQUIRE(d->bn_sumsq && p.vec && (pl.slots() == 1 || p.counters) && d->kwaves == 0,
+        YM_REQUIRE((d->bn_sumsq || d->bn_ordered) && ((uintptr_t)d->bn_sum & 7) == 0 && p.vec && (pl.slots() == 1 || p.counters) && d->kwaves == 0,
                    "conv: bn_sum given but this configuration cannot fuse the statistics (ask ym_conv2d_fuses_bn_stats)");
     }
     if (d->bnb_y) {
@@ -1151,6 +1168,7 @@ extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t work
         YM_REQUIRE(d->Cout % 4 == 0 && ((uintptr_t)d->bnb_y & 15) == 0 && ((uintptr_t)d->bnb_out & 15) == 0,
                    "conv: bnb_y / bnb_out must be 16-byte aligned [M][Cout] tensors");
     }
+    if (d->bn_sum && !d->bn_ordered) ym_note_unordered_sum();      // (the epilogue ends in fp64 atomics)
     hipStream_t st = (hipStream_t)s;
     if (d->kwaves > 0) {
         const bool dma = d->stages >= 22 && d->stages <= 24;

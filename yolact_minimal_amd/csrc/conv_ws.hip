@@ -17,7 +17,9 @@
 //     no LDS staging, no barrier;
 //   * train-mode BatchNorm statistics (ym_conv_desc.bn_sum): a lane's column sums stay in REGISTERS for the workgroup's whole
 //     life (fp32 over the 32 rows of a block, fp64 across blocks) and are flushed with ONE fp64 atomic per channel and wave at
-//     the end -- the per-tile LDS reduction + 128 atomics per tile of conv_igemm_f32 are gone.
+//     the end -- the per-tile LDS reduction + 128 atomics per tile of conv_igemm_f32 are gone.  Ordered mode (ConvP::bn_ordered):
+//     the wave stores the pair to row j0 * WM + wm of the partial buffer instead (gm * WM rows, each (row, channel) written by
+//     exactly one wave, whatever blocks it walked), and ym_bn_partials_finish adds the rows in a fixed order.
 // The data gradient of such a layer is the same GEMM on the dgrad-packed filter ([Cin][Cout_pad] = [N][K]) and takes this kernel
 // too (with the residual-gradient add); launches that carry BatchNorm-BACKWARD sums (bnb_*) stay on conv_igemm_f32.
 // Same products, fp32 accumulation in K order (lane half h, step s of group g: k = 8g + 4h + s; one accumulator per tile, where the
@@ -233,8 +235,14 @@ __global__ __launch_bounds__(256) void conv1x1_ws(const ConvP p, int nslices, in
             const double a = ds1[jj] + __shfl_xor(ds1[jj], 32), b = ds2[jj] + __shfl_xor(ds2[jj], 32);
             const int col = n0 + wn * 64 + jj * 32 + frag_row;
             if (khalf == 0 && col < N) {
-                atomicAdd(p.bn_sum + col, a);
-                atomicAdd(p.bn_sumsq + col, b);
+                if (p.bn_ordered) {
+                    double* row = p.bn_sum + (size_t)(j0 * WM + wm) * 2 * N;      // part[row][2][N]
+                    row[col] = a;
+                    row[N + col] = b;
+                } else {
+                    atomicAdd(p.bn_sum + col, a);
+                    atomicAdd(p.bn_sumsq + col, b);
+                }
             }
         }
     }
@@ -260,10 +268,11 @@ size_t ym_conv_ws_lds_bytes(int bm, int bn, int nkt, int nstg) {
     return ((size_t)nkt * bn * 32 + (size_t)nstg * bm * 32) * sizeof(float);
 }
 
-int ym_launch_conv_ws(const ConvP& p, int bm, int bn, int nstg, int grid_wgs, hipStream_t st) {
-    const int nslices = ym_cdiv(p.Cout, bn), mblocks = ym_cdiv(p.M, bm);
-    const size_t lds = ym_conv_ws_lds_bytes(bm, bn, p.nkt, nstg);
-    if (lds > (160u << 10)) { ym_set_error("conv(weight-stationary): %zu B of LDS (tile %dx%d, K %d, ring %d)", lds, bm, bn, p.nkt * 32, nstg); return YM_EINVAL; }
+namespace {
+// workgroups that walk the M blocks of one filter slice
+int ws_walkers(int M, int Cout, int bm, int bn, int nkt, int nstg, int grid_wgs) {
+    const int nslices = ym_cdiv(Cout, bn), mblocks = ym_cdiv(M, bm);
+    const size_t lds = ym_conv_ws_lds_bytes(bm, bn, nkt, nstg);
     static int cus = 0;
     if (cus == 0) {
         int dev = 0, n = 0;
@@ -277,6 +286,19 @@ int ym_launch_conv_ws(const ConvP& p, int bm, int bn, int nstg, int grid_wgs, hi
     int gm = total / nslices;
     if (gm < 1) gm = 1;
     if (gm > mblocks) gm = mblocks;
+    return gm;
+}
+}  // namespace
+
+int ym_conv_ws_partial_rows(int M, int Cout, int bm, int bn, int nkt, int nstg, int grid_wgs) {
+    return ws_walkers(M, Cout, bm, bn, nkt, nstg, grid_wgs) * (bm / 64);
+}
+
+int ym_launch_conv_ws(const ConvP& p, int bm, int bn, int nstg, int grid_wgs, hipStream_t st) {
+    const int nslices = ym_cdiv(p.Cout, bn), mblocks = ym_cdiv(p.M, bm);
+    const size_t lds = ym_conv_ws_lds_bytes(bm, bn, p.nkt, nstg);
+    if (lds > (160u << 10)) { ym_set_error("conv(weight-stationary): %zu B of LDS (tile %dx%d, K %d, ring %d)", lds, bm, bn, p.nkt * 32, nstg); return YM_EINVAL; }
+    const int gm = ws_walkers(p.M, p.Cout, bm, bn, p.nkt, nstg, grid_wgs);
 #define YM_WS(WM_, WN_)                                                                       \
     do {                                                                                      \
         if (nstg == 2) return launch_ws<WM_, WN_, 2>(p, nslices, mblocks, gm, lds, st);       \

@@ -15,6 +15,11 @@ void ym_set_error(const char* fmt, ...) {
 extern "C" const char* ym_last_error(void) { return g_err; }
 extern "C" int ym_abi_version(void) { return 1; }
 
+// launches that end in floating-point atomics on a statistic / gradient path (ym_unordered_sum_launches): host side, monotonic
+static unsigned long long g_unordered = 0;
+void ym_note_unordered_sum(void) { __atomic_fetch_add(&g_unordered, 1ull, __ATOMIC_RELAXED); }
+extern "C" int64_t ym_unordered_sum_launches(void) { return (int64_t)__atomic_load_n(&g_unordered, __ATOMIC_RELAXED); }
+
 namespace {
 
 __global__ void k_nchw_to_nhwc4(const float* __restrict__ in, float* __restrict__ out, int B, int C, int HW) {

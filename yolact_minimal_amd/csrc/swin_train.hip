@@ -719,6 +719,7 @@ extern "C" int ym_swin_window_attention_bwd(const float* qkv, const float* qkv_b
     if (nblk > wgs_needed) nblk = wgs_needed;
     p.nblk = (int)nblk;
     const size_t lds = (size_t)slots * 4 * MAT * sizeof(float);      // 72 KB (2 slots: two workgroups per CU) / 144 KB (4 slots)
+    ym_note_unordered_sum();                                   // (dtable / dqkv_bias_pad end in fp32 atomics)
     static YmLdsAttr attr2 = {}, attr4 = {};
     if (slots == 4) {
         if (int rc = ym_ensure_dyn_lds(attr4, reinterpret_cast<const void*>(k_window_attention_bwd<4>), lds, "window_attention_bwd")) return rc;

@@ -603,6 +603,26 @@ inline int ew_grid(size_t total, int cap = 8192) {
 
 }  // namespace
 
+// grid of the statistics passes that write per-workgroup partials (ym_bn_train_fwd / ym_bn_train_bwd with the larger workspace)
+static inline int col_part_grid(int64_t M, int C) {
+    const int CQ = (C / 4) < 256 ? (C / 4) : 256, RL = 256 / CQ;
+    long long grid = (M + (long long)RL * 16 - 1) / ((long long)RL * 16);
+    if (grid < 1) grid = 1;
+    if (grid > 1024) grid = 1024;
+    return (int)grid;
+}
+
+extern "C" int ym_bn_partials_finish(const void* part, int rows, int C, void* sums, ym_stream_t s) {
+    YM_REQUIRE(part && sums && rows > 0 && C > 0, "bn_partials_finish: bad args");
+    double* out = (double*)sums;
+    hipLaunchKernelGGL(k_col_finish, dim3(ym_cdiv(C, 16)), dim3(256), 0, (hipStream_t)s, (const double*)part, rows, C, out, out + C);
+    return ym_check_launch("bn_partials_finish");
+}
+
+extern "C" size_t ym_bn_train_fwd_workspace_bytes(int64_t M, int C) {
+    return (size_t)C * 16 + (size_t)col_part_grid(M, C) * 2 * C * 8;
+}
+
 extern "C" int ym_bn_train_fwd(const float* y, int64_t M, int C, const float* gamma, const float* beta, float eps,
                                float momentum, float* running_mean, float* running_var, const float* residual, int relu,
                                float* out, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,
@@ -613,13 +633,22 @@ extern "C" int ym_bn_train_fwd(const float* y, int64_t M, int C, const float* ga
     hipStream_t st = (hipStream_t)s;
     double* sum = (double*)workspace;
     double* sumsq = sum + C;
-    (void)hipMemsetAsync(sum, 0, (size_t)C * 16, st);
-    const int CQ = (C / 4) < 256 ? (C / 4) : 256, RL = 256 / CQ;
-    int grid = (int)((M + (long long)RL * 16 - 1) / ((long long)RL * 16));
-    if (grid > 512) grid = 512;       // every block ends with 2*C contended fp64 atomics: keep the block count low
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_col_reduce<0>, dim3(grid), dim3(256), 0, st, y, nullptr, nullptr, nullptr, nullptr, (long long)M, C, 0,
-                       0, sum, sumsq);
+    if (workspace_bytes >= ym_bn_train_fwd_workspace_bytes(M, C)) {                 // two-stage: partials, then an ordered sum
+        const int big = col_part_grid(M, C);
+        double* part = sumsq + C;
+        hipLaunchKernelGGL(k_col_reduce<0>, dim3(big), dim3(256), 0, st, y, nullptr, nullptr, nullptr, nullptr, (long long)M, C, 0,
+                           0, sum, sumsq, part);
+        hipLaunchKernelGGL(k_col_finish, dim3(ym_cdiv(C, 16)), dim3(256), 0, st, part, big, C, sum, sumsq);
+    } else {
+        (void)hipMemsetAsync(sum, 0, (size_t)C * 16, st);
+        const int CQ = (C / 4) < 256 ? (C / 4) : 256, RL = 256 / CQ;
+        int grid = (int)((M + (long long)RL * 16 - 1) / ((long long)RL * 16));
+        if (grid > 512) grid = 512;       // every block ends with 2*C contended fp64 atomics: keep the block count low
+        if (grid < 1) grid = 1;
+        ym_note_unordered_sum();
+        hipLaunchKernelGGL(k_col_reduce<0>, dim3(grid), dim3(256), 0, st, y, nullptr, nullptr, nullptr, nullptr, (long long)M, C, 0,
+                           0, sum, sumsq);
+    }
     hipLaunchKernelGGL(k_bn_finalize, dim3(ym_cdiv(C, 256)), dim3(256), 0, st, sum, sumsq, (long long)M, eps, momentum,
                        save_mean, save_invstd, running_mean, running_var, C);
     hipLaunchKernelGGL(k_bn_apply, dim3(ew_grid((size_t)M * (C / 4))), dim3(256), 0, st, y, save_mean, save_invstd, gamma, beta,
@@ -687,6 +716,7 @@ extern "C" int ym_bn_train_bwd(const float* dout, const float* out, const float*
     } else {
         if (grid > 512) grid = 512;
         (void)hipMemsetAsync(db, 0, (size_t)C * 16, st);
+        ym_note_unordered_sum();
         hipLaunchKernelGGL(k_col_reduce<1>, dim3(grid), dim3(256), 0, st, dout, out, y, save_mean, save_invstd, (long long)M, C,
                            relu, 0, db, dg, (double*)nullptr, gamma, beta);
     }
@@ -731,6 +761,7 @@ extern "C" int ym_act_bias_bwd(const float* dy, const float* y, int64_t M, int C
         } else {
             if (grid > 2048) grid = 2048;
             (void)hipMemsetAsync(acc, 0, (size_t)C * 8, st);
+            ym_note_unordered_sum();
             hipLaunchKernelGGL(k_col_reduce<2>, dim3(grid), dim3(256), 0, st, dy, y, nullptr, nullptr, nullptr, (long long)M, C, 0,
                                act, acc, nullptr);
         }

@@ -9,6 +9,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void ym_set_error(const char* fmt, ...);
+void ym_note_unordered_sum(void);      // an entry point enqueued a kernel whose sums end in floating-point atomics (elementwise.hip)
 
 #define YM_REQUIRE(cond, ...)                \
     do {                                     \

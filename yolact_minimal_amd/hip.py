@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     'ym_after_nms_batch_packed', 'ym_pack_masks', 'ym_unpack_masks', 'ym_mask_iou_packed_workspace_bytes', 'ym_mask_iou_packed',
     'ym_rle_encode_packed', 'ym_draw_detections_batch_packed', 'ym_draw_cutout_objects_packed',
     'ym_bn_train_bwd_workspace_bytes', 'ym_bn_train_bwd', 'ym_bn_train_bwd_apply', 'ym_act_bias_bwd', 'ym_conv2d_fuses_bn_stats', 'ym_bn_train_fwd_stats', 'ym_maxpool3x3s2_bwd', 'ym_maxpool3x3s2_fwd_idx', 'ym_maxpool3x3s2_bwd_idx', 'ym_bilinear2x_bwd', 'ym_sgd_step',
+    'ym_conv2d_bn_partial_rows', 'ym_bn_partials_finish', 'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes',
 )
 
 
@@ -60,7 +61,8 @@ class ConvDesc(ctypes.Structure):
                 ('level_w', ctypes.c_int32 * 5), ('tail_tiles', ctypes.c_int32), ('tail_ksplit', ctypes.c_int32), ('mma', ctypes.c_int32),
                 ('bnb_relu', ctypes.c_int32), ('bnb_y', ctypes.c_void_p), ('bnb_out', ctypes.c_void_p),
                 ('bnb_mean', ctypes.c_void_p), ('bnb_invstd', ctypes.c_void_p), ('bnb_gamma', ctypes.c_void_p),
-                ('bnb_beta', ctypes.c_void_p), ('grid_wgs', ctypes.c_int32)]
+                ('bnb_beta', ctypes.c_void_p), ('grid_wgs', ctypes.c_int32),
+                ('bn_ordered', ctypes.c_int32)]       # (the former trailing padding: sizeof is unchanged)
 
 
 class WgradDesc(ctypes.Structure):
@@ -202,6 +204,12 @@ def lib():
         L.ym_class_box_loss.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
         L.ym_semantic_loss.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp]
         L.ym_conv2d_fuses_bn_stats.argtypes = [ctypes.POINTER(ConvDesc)]
+        L.ym_conv2d_bn_partial_rows.argtypes = [ctypes.POINTER(ConvDesc)]
+        L.ym_bn_partials_finish.argtypes = [vp, i32, i32, vp, vp]
+        L.ym_unordered_sum_launches.argtypes = []
+        L.ym_unordered_sum_launches.restype = ctypes.c_int64
+        L.ym_bn_train_fwd_workspace_bytes.argtypes = [i64, i32]
+        L.ym_bn_train_fwd_workspace_bytes.restype = sz
         L.ym_bn_train_fwd_stats.argtypes = [vp, i64, i32, vp, vp, f32, f32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         L.ym_bn_train_bwd_workspace_bytes.argtypes = [i64, i32]
         L.ym_bn_train_bwd_workspace_bytes.restype = sz
@@ -232,7 +240,8 @@ def lib():
             if name not in ('ym_last_error', 'ym_conv2d_workspace_bytes', 'ym_nms_workspace_bytes',
                             'ym_greedy_nms_workspace_bytes', 'ym_conv2d_wgrad_workspace_bytes',
                             'ym_sizeof_conv_desc', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
-                            'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes'):
+                            'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes',
+                            'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

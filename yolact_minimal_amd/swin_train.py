@@ -14,7 +14,7 @@ import ctypes
 
 import torch
 
-from . import hip
+from . import hip, train_engine
 from .hip import ACT_NONE
 from .train_engine import ConvBias, _grad_slot, scratch
 
@@ -120,6 +120,10 @@ class WindowAttentionFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, qkv_bias, table = ctx.saved_tensors
         heads, window, shift = ctx.meta
+        if train_engine._DETERMINISTIC:
+            raise RuntimeError('deterministic training (YM_DETERMINISTIC=1 / Trainer(deterministic=True)) does not cover Swin-T: '
+                               'k_window_attention_bwd (ym_swin_window_attention_bwd) sums the relative-position-bias table '
+                               'gradient and the padded-token qkv bias gradient with fp32 atomics')
         b, h, w, c3 = qkv.shape
         c = c3 // 3
         dqkv = torch.empty_like(qkv)

@@ -167,6 +167,41 @@ def _ru(x, m):
     return (x + m - 1) // m * m
 
 
+# ---- ordered BatchNorm sums (bit-reproducible training) --------------------------------------------------------------------------
+# With the switch on, no launch of a step ends in floating-point atomics on a path that feeds the weights: the conv epilogues that
+# carry BatchNorm sums (forward statistics, bnb_* backward sums) store per-row partials (ym_conv_desc.bn_ordered) and one
+# `ym_bn_partials_finish` launch right behind the conv adds them, in a fixed order, into the same [2][C] fp64 slice every consumer
+# already reads; the unfused statistics passes get the workspace with which they write partials too.  Parameters, optimizer state
+# and running statistics are then bit-identical from run to run (one rank or gloo ranks, same build, same plan table); the reported
+# loss scalars are not part of that.  A runtime switch like the others here (tools/train_ab.py --set ..:_DETERMINISTIC=1), default
+# from YM_DETERMINISTIC=1; it is part of every `_desc_cache` key it affects.
+_DETERMINISTIC = os.environ.get('YM_DETERMINISTIC', '0') == '1'
+_part_scratch = {}
+
+
+def set_deterministic(on):
+    """`Trainer(deterministic=...)`: None keeps the current setting (the environment's default unless someone changed it)."""
+    global _DETERMINISTIC
+    if on is not None:
+        _DETERMINISTIC = bool(on)
+    return bool(_DETERMINISTIC)
+
+
+def _partials(device, rows, c):
+    """Partial-sum buffer of one ordered launch, [rows][2][c] fp64: one per (device, stream), grown on demand, never zeroed (every
+    entry is written); the finish runs right behind the conv on the same stream, so the next launch may reuse it."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    buf = _part_scratch.get(key)
+    if buf is None or buf.numel() < rows * 2 * c:
+        buf = _part_scratch[key] = torch.empty(max(rows * 2 * c, 1 << 16), device=device, dtype=torch.float64)
+    return buf
+
+
+def _finish_partials(part, rows, c, stats):
+    hip.check(hip.lib().ym_bn_partials_finish(ctypes.c_void_p(part.data_ptr()), rows, c, ctypes.c_void_p(stats.data_ptr()),
+                                              hip.stream_ptr()), 'ym_bn_partials_finish')
+
+
 _counters = {}
 
 
@@ -347,13 +382,15 @@ def _conv_forward(x, wp, k_pad, cout_pad, kh, kw, stride, pad, shift, act, resid
     # the BN statistics fuse) is built once per shape and reused: per call only the pointers change.  (The host spends ~35 us per
     # launch in a step of ~1100 launches; with the convs on the bf16 pipe the step is host-bound.)
     key = ('f', x.device.index, b, h, w, cin, cout_pad, kh, kw, stride, pad, act, residual is not None, bn_stats is not None,
-           None if segs is None else tuple((n0, n1, bs, pt, a) for n0, n1, _, bs, pt, a in segs), train_mma())
+           None if segs is None else tuple((n0, n1, bs, pt, a) for n0, n1, _, bs, pt, a in segs), train_mma(),
+           bool(_DETERMINISTIC) and bn_stats is not None)
+    ordered = key[-1]
     ent = _desc_cache.get(key)
     if ent is None:
         d = conv_launch.conv_desc(b, h, w, cin, cout_pad, kh, kw, stride, pad, ho, wo, k_pad,
                                   [(0, cout_pad, None, ho * wo * cout_pad, cout_pad, act)] if segs is None else segs)
     else:
-        d, fused, ws_bytes = ent
+        d, fused, ws_bytes, part_rows = ent
     d.inp, d.weight, d.k_pad = x.data_ptr(), wp.data_ptr(), k_pad
     d.shift = shift.data_ptr() if shift is not None else None
     d.residual = residual.data_ptr() if residual is not None else None
@@ -372,12 +409,20 @@ def _conv_forward(x, wp, k_pad, cout_pad, kh, kw, stride, pad, shift, act, resid
         d.tile_counters = _tile_counters(x.device)
         fused = bn_stats is not None and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
         ws_bytes = hip.conv_workspace_bytes(d)
-        _desc_cache[key] = (d, fused, ws_bytes)
-    if fused:
+        d.bn_ordered = int(fused and ordered)
+        part_rows = hip.lib().ym_conv2d_bn_partial_rows(ctypes.byref(d)) if d.bn_ordered else 0
+        _desc_cache[key] = (d, fused, ws_bytes, part_rows)
+    part = None
+    if fused and part_rows:
+        part = _partials(x.device, part_rows, cout_pad)
+        d.bn_sum, d.bn_sumsq = part.data_ptr(), None
+    elif fused:
         d.bn_sum, d.bn_sumsq = bn_stats.data_ptr(), bn_stats.data_ptr() + cout_pad * 8
     ws = scratch(x.device, ws_bytes)
     _count(key)
     hip.conv2d_fwd(d, ws)
+    if part is not None:
+        _finish_partials(part, part_rows, cout_pad, bn_stats)
     if bn_stats is not None:
         return y, fused
     return y
@@ -394,7 +439,7 @@ def _conv_dgrad(dz, weight, cout_pad, x_shape, stride, pad, add=None, out=None, 
     wd = _pack_dgrad(weight, cout_pad)
     dx = out if out is not None else torch.empty(b, h, w, cin, device=dz.device, dtype=torch.float32)
     key = ('d', dz.device.index, b, dz.shape[1], dz.shape[2], cout_pad, cin, kh, kw, stride, pad, h, w, add is not None, train_mma(),
-           bn_bwd is not None)
+           bn_bwd is not None, bool(_DETERMINISTIC) and bn_bwd is not None)
     ent = _desc_cache.get(key)
     if ent is None:
         d = conv_launch.conv_desc(b, dz.shape[1], dz.shape[2], cout_pad, cin, kh, kw, stride, pad, h, w, kh * kw * cout_pad,
@@ -404,8 +449,12 @@ def _conv_dgrad(dz, weight, cout_pad, x_shape, stride, pad, add=None, out=None, 
         _configure_conv(d, plan_transfer.dgrad_key(b * h * w, cin, cout_pad, kh, stride))
         d.tile_counters = _tile_counters(dz.device)
         fuses = bn_bwd is not None and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
-        ent = _desc_cache[key] = (d, hip.conv_workspace_bytes(d), fuses)
-    d, ws_bytes, fuses = ent
+        d.bn_ordered = int(fuses and key[-1])
+        if d.bn_ordered:                 # (the row query looks at the descriptor as it will be launched: with its bnb_* sums)
+            d.bnb_y = bn_bwd.y
+        part_rows = hip.lib().ym_conv2d_bn_partial_rows(ctypes.byref(d)) if d.bn_ordered else 0
+        ent = _desc_cache[key] = (d, hip.conv_workspace_bytes(d), fuses, part_rows)
+    d, ws_bytes, fuses, part_rows = ent
     d.inp, d.weight, d.seg[0].out = dz.data_ptr(), wd.data_ptr(), dx.data_ptr()
     if add is not None:
         assert tuple(add.shape) == (b, h, w, cin) and add.is_contiguous()
@@ -414,12 +463,18 @@ def _conv_dgrad(dz, weight, cout_pad, x_shape, stride, pad, add=None, out=None, 
         assert bn_bwd.c == cin and bn_bwd.m == b * h * w
         stats = _stats_pool.take(2 * cin, dz.device)                 # zeroed
         d.bn_sum, d.bn_sumsq = stats.data_ptr(), stats.data_ptr() + cin * 8
+        part = None
+        if part_rows:
+            part = _partials(dz.device, part_rows, cin)
+            d.bn_sum, d.bn_sumsq = part.data_ptr(), None
         d.bnb_y, d.bnb_out, d.bnb_mean, d.bnb_invstd = bn_bwd.y, bn_bwd.out, bn_bwd.mean, bn_bwd.invstd
         d.bnb_gamma, d.bnb_beta, d.bnb_relu = bn_bwd.gamma, bn_bwd.beta, bn_bwd.relu
     ws = scratch(dz.device, ws_bytes)
     _count(key)
     hip.conv2d_fwd(d, ws)
     if fuses:
+        if part is not None:
+            _finish_partials(part, part_rows, cin, stats)
         bn_bwd.stats, bn_bwd.dout_ptr = stats, dx.data_ptr()
     return dx
 
@@ -950,6 +1005,16 @@ def check_links_drained():
                            f'consumers of a shared tensor in decreasing creation order (set YM_GRAD_JOIN=0 YM_FUSE_RES_GRAD=0)')
 
 
+def abandon_links():
+    """A backward pass that raised leaves its parked gradients and the armed end-of-backward check behind (the autograd engine
+    drops its callbacks with the failed graph task): forget them, so that the next step starts clean.  Trainer.step calls this
+    before it re-raises."""
+    for l in _live_links:
+        l.grad = None
+    _live_links.clear()
+    _drain_armed[0] = False
+
+
 class ResGradLink:
     """A Bottleneck's input feeds conv1 AND the residual add of conv3 (modules/resnet.py:21,35-37); autograd would sum the two
     gradients with an extra elementwise pass.  conv3's backward parks its residual gradient here (`give`) and conv1's backward,
@@ -1062,10 +1127,14 @@ class ConvBn(torch.autograd.Function):
                                                       hip.ptr(out), hip.ptr(mean), hip.ptr(invstd),
                                                       ctypes.c_void_p(stats.data_ptr()), hip.stream_ptr()), 'ym_bn_train_fwd_stats')
         else:
+            ws_ptr, ws_bytes = stats.data_ptr(), stats.numel() * 8
+            if _DETERMINISTIC:            # the workspace with which the statistics pass writes partials + an ordered sum (no atomics)
+                ws = scratch(x.device, hip.lib().ym_bn_train_fwd_workspace_bytes(m, cout))
+                ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
             hip.check(hip.lib().ym_bn_train_fwd(hip.ptr(y), m, cout, hip.ptr(gamma.detach()), hip.ptr(beta.detach()), eps, momentum,
                                                 hip.ptr(running_mean), hip.ptr(running_var), res_ptr, int(relu),
-                                                hip.ptr(out), hip.ptr(mean), hip.ptr(invstd), ctypes.c_void_p(stats.data_ptr()),
-                                                stats.numel() * 8, hip.stream_ptr()), 'ym_bn_train_fwd')
+                                                hip.ptr(out), hip.ptr(mean), hip.ptr(invstd), ctypes.c_void_p(ws_ptr),
+                                                ws_bytes, hip.stream_ptr()), 'ym_bn_train_fwd')
         # `out` is only needed for the ReLU mask when a residual was added; otherwise backward re-derives the mask from y
         mask_out = out if (relu and (residual is not None or beta is None)) else None
         ctx.save_for_backward(x, weight, gamma, y, mask_out, mean, invstd)

@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from . import hip
-from .train_engine import wgrad_stream_if_used, weights_changed, release_wgrad_scratch
+from .train_engine import wgrad_stream_if_used, weights_changed, release_wgrad_scratch, set_deterministic
 
 
 def init_distributed(backend=None):
@@ -305,8 +305,13 @@ def flatten_buffers(module):
 
 
 class Trainer:
-    def __init__(self, net, cfg, device, world=1, local_rank=0):
+    def __init__(self, net, cfg, device, world=1, local_rank=0, deterministic=None):
+        """`deterministic`: True / False sets train_engine's ordered-sum switch (bit-reproducible parameters, optimizer state and
+        running statistics: see train_engine._DETERMINISTIC) for this trainer's steps; None keeps the process default
+        (YM_DETERMINISTIC=1)."""
         self.net, self.cfg, self.device, self.world = net.train().to(device), cfg, device, world
+        self.deterministic = deterministic
+        set_deterministic(deterministic)
         if getattr(self.net, '_train_state', None) is not None:
             self.net._drop_train_state()             # the module's own plumbing (train_state.py) gives way to this trainer's
         release_wgrad_scratch()                      # (per-layer scratch of a previous trainer in this process)
@@ -419,6 +424,7 @@ class Trainer:
         self.load_state_dict(torch.load(path, map_location=self.device))
 
     def step(self, images, targets, masks):
+        set_deterministic(self.deterministic)         # (another trainer of this process may have chosen otherwise)
         self.opt.lr = lr_at(self.cfg, self.step_idx)
         ev = None
         if self._timing is not None:
@@ -437,12 +443,16 @@ class Trainer:
             dist.all_reduce(all_loss)                 # 16-byte logging collective, train.py:121-122
         total = losses[0] + losses[1] + losses[2] + losses[3]
         from .loss import unit_loss_grads
-        from .train_engine import wgrad_on_side_stream, check_links_drained
+        from .train_engine import wgrad_on_side_stream, check_links_drained, abandon_links
         # weight gradients run on a side stream next to the data-gradient chain; the main stream waits for them at the block's end
         if ev is not None:
             ev[2].record()
-        with unit_loss_grads(), wgrad_on_side_stream(self.device):   # d(total)/d(loss_i) = 1: stored loss gradients pass through unscaled
-            total.backward()
+        try:
+            with unit_loss_grads(), wgrad_on_side_stream(self.device):   # d(total)/d(loss_i) = 1: stored loss gradients pass through unscaled
+                total.backward()
+        except Exception:
+            abandon_links()                           # (e.g. Swin-T's backward refusing the deterministic mode: nothing stays parked)
+            raise
         check_links_drained()                         # every gradient parked for a later consumer was consumed (host-side check)
         if ev is not None:
             ev[3].record()                            # backward done on the device: the weight-gradient stream was joined at the block's end
