@@ -86,10 +86,15 @@ typedef struct {
                                 `weight` comes from ym_pack_conv_weight_dgrad.  Autograd counterpart of every
                                 nn.Conv2d on the path (loss_total.backward(), reference train.py:126). */
     int32_t stages;          /* workgroup kernel operand staging: 0/2 = registers, double buffer; 3 = registers, loads two K tiles
-                                ahead (64-wide tiles); 22/23/24 = direct global->LDS DMA, ring of 2/3/4 (24: 64x64 tile only);
+                                ahead (forward: not the 128x128 tile; data gradient: 64x64 only); 22/23 = direct global->LDS DMA, ring
+                                of 2/3; 24 = ring of 4, 33/34 = ring of 3/4 with software-pipelined fragments (64x64 forward tile only);
                                 42/43/44/46/48 = PERSISTENT direct-to-LDS kernel, ring of 2/3/4/6/8 (64x64 tile, plain NHWC
                                 output, ReLU or no activation, no bn_sum; anything else falls back to 22/23/24): grid_wgs workgroups walk
-                                the (tile, K slice) items and the operand stream runs on across item boundaries */
+                                the (tile, K slice) items and the operand stream runs on across item boundaries;
+                                52/53/54 = WEIGHT-STATIONARY 1x1 / stride-1 kernel, ring of 2/3/4 (tile 64x256, 128x128 or 256x64, plain
+                                NHWC output, ReLU or no activation, no bnb_y, filter slice <= 64 KB and slice + ring <= 160 KB of LDS;
+                                anything else runs as the 64x64 tile with 22).  Any other value, and a value that does not exist for
+                                the tile, runs the register double buffer; ym_conv2d_effective_plan reports what a descriptor resolves to */
     double* bn_sum;          /* optional [Cout] fp64 accumulators (zeroed by the caller): the epilogue adds the */
     double* bn_sumsq;        /* per-channel sum / sum of squares of the conv OUTPUT (train-mode BN statistics).  */
                              /* Only when ym_conv2d_fuses_bn_stats(desc) == 1 (plain NHWC output).               */
@@ -111,7 +116,8 @@ typedef struct {
                              /* parity mode).  3 / 6 = "split bf16": every fp32 operand is split on its way into LDS into two / three  */
                              /* bf16 terms and the 3 / 6 most significant cross products run on v_mfma_f32_32x32x16_bf16 with fp32     */
                              /* accumulation (relative error per product ~2^-17 / ~2^-23; tensors in HBM stay fp32).  Needs Cin % 32   */
-                             /* == 0, kwaves == 0, no pyramid input; stages is ignored (register-staged double buffer).               */
+                             /* == 0, kwaves == 0, no pyramid input; register staging only: stages 3 = two register sets (every tile), */
+                             /* any other value the double buffer.                                                                     */
     int32_t bnb_relu;        /* Train-mode BatchNorm BACKWARD statistics, fused.  A data-gradient launch (transposed = 1) writes the   */
     const float* bnb_y;      /* gradient dout[M][Cout] of the PREVIOUS layer's BN output; with bnb_y != NULL its epilogue also adds    */
     const float* bnb_out;    /* that BN's two backward sums to bn_sum / bn_sumsq (zeroed by the caller): bn_sum[c] += sum_m dz,        */
@@ -139,6 +145,15 @@ size_t ym_sizeof_conv_desc(void);                      /* for bindings: must equ
 size_t ym_conv2d_workspace_bytes(const ym_conv_desc* d);
 int ym_conv2d_tile_counters(const ym_conv_desc* d);   /* output tiles of the chosen plan (0 if K is not split) */
 int ym_conv2d_fuses_bn_stats(const ym_conv_desc* d);
+/* The plan ym_conv2d_fwd would run for this descriptor (16-byte aligned workspace assumed), in the row encoding of the tuned table:
+ * out = [tile_m, tile_n, ksplit, kwaves, stages, tail_tiles, tail_ksplit, grid_wgs].  Host only: needs no device, and looks at the
+ * descriptor's pointers for nullness and alignment only.  `stages` is canonical: 2 = register double buffer (whatever value asked
+ * for it; pyramid and stem always), 3 = register ring where it is built, 22/23/24 = direct-to-LDS ring of 2/3/4 (with kwaves > 0:
+ * the wave kernel's DMA rings), 33/34 = DMA ring with pipelined fragments, 40 + depth = the persistent ring actually launched,
+ * 50 + depth = weight-stationary ring, 0 = wave kernel without DMA.  tail_tiles / tail_ksplit are the plan's after clamping (0 / 0:
+ * the tail was dropped); grid_wgs is the descriptor's where the chosen kernel reads it, else 0.  Returns YM_OK, or the error of an
+ * invalid descriptor. */
+int ym_conv2d_effective_plan(const ym_conv_desc* d, int32_t out[8]);
 int ym_conv2d_bn_partial_rows(const ym_conv_desc* d); /* rows of the bn_ordered partial buffer the chosen plan writes (M tiles, or   */
                                                       /* walkers x wave rows of the weight-stationary kernel); 0 if the statistics do  */
                                                       /* not fuse (ym_conv2d_fuses_bn_stats(desc) == 0)                                */

@@ -1,4 +1,4 @@
-"""Layer geometry of a forward key of the tuned table (host only; no GPU, no library).
+"""Layer geometry of a forward key of the tuned table, and the plan the library runs for its row (host only; no GPU).
 
 A key `M.._N.._C.._k.._s.._seg.._r..(_L5)(_st|_tp|_mma3)` names M = B * Ho * Wo output pixels, not B, Ho, Wo; a 3x3 filter's halo
 addressing depends on them.  The table is measured on real layers, so every key must be a layer of some model at some image size:
@@ -116,9 +116,6 @@ def resolve(key):
     return None
 
 
-KNOWN_STAGES = (0, 2, 3, 22, 23, 24, 33, 34, 42, 43, 44, 46, 48, 52, 53, 54)
-
-
 def launch_plan(g, row):
     """(ConvPlan, mma) that reach the descriptor of the launch a row is read for: the engines' own resolution (conv_launch.py: the
     inference policy, for an `_st` row the training one) over a table that holds this row alone."""
@@ -133,42 +130,62 @@ def launch_plan(g, row):
     return CL.infer_plan(table, base, shape, 'throughput' if g.suffix == '_tp' else 'latency', mma, eligible, pyramid=bool(g.levels))[:2]
 
 
-def family(g, plan, mma):
+def family(g, effective, mma):
+    """Kernel family of the plan that runs (hip.conv_effective_plan)."""
     if g.levels:
         return 'pyramid'
     if mma:
         return 'split-bf16'
-    if plan.wave:
-        return 'wave-DMA' if plan.wave_dma else 'wave'
-    if plan.persistent:
+    if effective.wave:
+        return 'wave-DMA' if effective.wave_dma else 'wave'
+    if effective.persistent:
         return 'persistent'
-    if plan.weight_stationary:
+    if effective.weight_stationary:
         return 'weight-stationary'
-    if plan.tile_m == 0:
-        return 'heuristic'
-    return 'LDS ring' if plan.stages >= 22 else 'register'
+    return 'LDS ring' if effective.stages >= 22 else 'register'
 
 
-def silent_fallback(g, plan, mma):
-    """Why ym_conv2d_fwd would run this launch on ANOTHER kernel than the row names without saying so, or None.  The library has no
-    query for the kernel it picked; these are the conditions include/yolact_hip.h documents for the variants that fall back."""
-    tile = (plan.tile_m, plan.tile_n)
-    plain = g.nseg == 1 and g.N % 4 == 0           # one NHWC tensor the vector epilogue can write
-    if plan.stages not in KNOWN_STAGES:
-        return f'stages {plan.stages} names no kernel'
-    if g.levels or mma or plan.wave:
-        if (plan.tail_tiles or plan.tail_ksplit) and not plain:
-            return 'a tail split needs one plain NHWC output'
-        return None                                # (stages ignored / rejected loudly)
-    if plan.persistent and not (tile == (64, 64) and plain and g.C % 32 == 0 and g.suffix != '_st'):
-        return 'the persistent walker covers 64x64 tiles of a plain NHWC output without BatchNorm sums'
-    if plan.weight_stationary and not (tile in ((64, 256), (128, 128), (256, 64)) and g.k == 1 and g.stride == 1 and plain and
-                                       g.C % 32 == 0 and plan.tile_n * g.C * 4 <= (64 << 10)):
-        return 'the weight-stationary kernel covers 1x1 / 1 filters whose slice fits the LDS, plain NHWC output'
-    if plan.stages in (24, 33, 34) and tile != (64, 64):
-        return f'stages {plan.stages} exists for the 64x64 tile only'
-    if plan.stages == 3 and tile == (128, 128):
-        return 'the register ring of 3 exists for 64-wide tiles only'
-    if (plan.tail_tiles or plan.tail_ksplit) and not plain:
-        return 'a tail split needs one plain NHWC output'
-    return None
+# Rows of the table that ym_conv2d_fwd does NOT run as written: key -> the row it runs instead.  Exact in both directions (a listed
+# row resolves to precisely this, no other row differs from its request); retuning a listed shape removes its entry.
+KNOWN_FALLBACKS = {
+    # 8 * 64 * 32 + 4 * 256 * 32 floats = 192 KB of LDS for the filter slice + ring of 4: over the weight-stationary kernel's 160 KB
+    'M147968_N128_C256_k1_s1_seg1_r0': [64, 64, 1, 0, 22, 0, 0],
+}
+
+
+def canonical_stages(g, plan, mma):
+    """`stages` of a request in ym_conv2d_effective_plan's canonical values (include/yolact_hip.h): 0 and 2 both name the register
+    double buffer, which is all a pyramid or stem launch has and, besides 3, all a split-bf16 one; a wave launch without DMA is 0."""
+    if plan.wave:
+        return plan.stages if plan.wave_dma else 0
+    if g.levels or g.C == 4 or (mma and plan.stages != 3) or plan.stages == 0:
+        return 2
+    return plan.stages
+
+
+def fallback(g, plan, mma, effective):
+    """How the plan the library runs (`effective`) departs from the requested one, or None.  `ksplit` is the planner's to normalise
+    (cdiv(nkt, cdiv(nkt, ksplit))) and is not compared; a tile of 0 leaves the tile to the planner."""
+    diffs = []
+    if plan.tile_m and plan.tile_n and (plan.tile_m, plan.tile_n) != (effective.tile_m, effective.tile_n):
+        diffs.append(f'tile {plan.tile_m}x{plan.tile_n} runs as {effective.tile_m}x{effective.tile_n}')
+    if plan.kwaves != effective.kwaves:
+        diffs.append(f'kwaves {plan.kwaves} runs as {effective.kwaves}')
+    if canonical_stages(g, plan, mma) != effective.stages:
+        diffs.append(f'stages {plan.stages} runs as {effective.stages}')
+    if plan.tail_tiles > 0 and plan.tail_ksplit > 1 and plan.tail_tiles != effective.tail_tiles:
+        diffs.append(f'tail of {plan.tail_tiles} tiles runs as {effective.tail_tiles}')
+    return '; '.join(diffs) or None
+
+
+def check_effective(g, row, plan, mma, desc):
+    """Ask the library which plan it runs for `desc` (the launch of `row`) and hold it to the request, or to KNOWN_FALLBACKS;
+    returns the effective ConvPlan."""
+    from yolact_minimal_amd import hip
+    effective = hip.conv_effective_plan(desc)
+    why = fallback(g, plan, mma, effective)
+    if g.key in KNOWN_FALLBACKS:
+        assert why is not None and effective.to_row() == KNOWN_FALLBACKS[g.key], (g.describe(), row, effective.to_row(), why)
+    else:
+        assert why is None, f'{g.describe()} row {row} runs as {effective.to_row()}: {why}'
+    return effective

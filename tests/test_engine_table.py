@@ -177,11 +177,40 @@ def test_tuner_rows_reach_the_table_only_through_the_reference_digest_gate(tmp_p
     assert 'merge_rows' in tool and 'json.dump(table, open(E.TUNED_PATH' not in tool
 
 
+def _launch_desc(g, plan, mma):
+    """The descriptor tests/test_gpu_forward_fullsize.py (`Launch`) builds for a row, with placeholder pointers (16-byte aligned where
+    its tensors are; the planner looks at nullness and alignment only): folded BatchNorm + ReLU, for an `_st` row the raw output + its
+    BatchNorm sums, for the three-segment head a bias and tanh on the third segment; arrival counters always."""
+    from yolact_minimal_amd import conv_launch
+    b, N, C, k = g.batch, g.N, g.C, g.k
+    sides = [(s, s) for s in g.levels] if g.levels else [(g.h, g.ho)]
+    pix = sum(ho * ho for _, ho in sides)
+    if g.nseg == 1:
+        segs = [(0, N, 0x10000, 0 if g.levels else g.ho * g.ho * N, N, 0 if g.suffix == '_st' else 1)]
+    else:
+        cuts, na, n_total = (0, 243, 255, 351), 3, 37 + pix * 3 + 29
+        segs = [(n0, n1, 0x10000 * (i + 1) + 37 * ((n1 - n0) // na) * 4, n_total * ((n1 - n0) // na), n1 - n0, 2 * (i == 2))
+                for i, (n0, n1) in enumerate(zip(cuts, cuts[1:]))]
+    d = conv_launch.conv_desc(b, sides[0][0], sides[0][0], C, N, k, k, g.stride, g.pad, sides[0][1], sides[0][1], (k * k * C + 31) // 32 * 32,
+                              segs, levels=sides if g.levels else None)
+    d.inp, d.weight, d.tile_counters = 0x1000, 0x2000, 0x3000
+    d.scale = 0x4000 if g.nseg == 1 and g.suffix != '_st' else None
+    d.shift = 0x5000 if g.suffix != '_st' else None
+    d.residual = 0x6000 if g.residual else None
+    if g.suffix == '_st':
+        d.bn_sum, d.bn_sumsq = 0x7000, 0x8000
+    plan.apply(d)
+    d.mma = mma
+    return d
+
+
 def test_every_forward_key_of_the_committed_table_resolves_to_a_layer():
     """tests/conv_geometry.py, the geometry rule of tests/test_gpu_forward_fullsize.py: every forward key of the table is a layer of
     some model at an image size that is a multiple of 32 from 128 to 864 and a batch of 1 / 2 / 4 / 8 / 16; strided keys get a
-    consistent input side, `_L5` keys five levels; and every row names a kernel variant that exists for its shape (no quiet
-    fall-back inside ym_conv2d_fwd).  A new row for a size outside the rule fails here, before anyone needs a GPU."""
+    consistent input side, `_L5` keys five levels; and the library runs every row of the table as the row says -- the plan
+    ym_conv2d_effective_plan reports for the row's launch is the requested one -- but for the rows of conv_geometry.KNOWN_FALLBACKS,
+    which resolve to exactly the plan listed there.  A new row for a size outside the rule, or one that names a kernel variant its
+    shape does not have, fails here, before anyone needs a GPU."""
     from tests import conv_geometry as CG
     from yolact_minimal_amd import engine as E
     table = json.load(open(E.TUNED_PATH))
@@ -204,8 +233,8 @@ def test_every_forward_key_of_the_committed_table_resolves_to_a_layer():
                 assert g.h == g.size and (g.k, g.stride, g.pad) in ((7, 2, 3), (4, 4, 0)), g.describe()
         assert g.batch in (1, 2, 4, 8, 16) and g.size % 32 == 0 and 128 <= g.size <= 864, g.describe()
         plan, mma = CG.launch_plan(g, table[key])
-        assert CG.silent_fallback(g, plan, mma) is None, (g.describe(), table[key], CG.silent_fallback(g, plan, mma))
-    assert pyramids >= 30
+        CG.check_effective(g, table[key], plan, mma, _launch_desc(g, plan, mma))
+    assert pyramids >= 30 and set(CG.KNOWN_FALLBACKS) <= set(keys)
     # the rule refuses what it should: a size that is no multiple of 32, a side no chain has, a pyramid of another depth
     assert CG.resolve('M10201_N256_C256_k3_s1_seg1_r0') is None                 # 101 x 101: a side of 808 px, no multiple of 32
     assert CG.resolve('M10000_N256_C256_k3_s1_seg1_r0')[-5:] == (1, 800, 100, 100, None)

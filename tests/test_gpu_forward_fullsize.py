@@ -6,9 +6,9 @@ end-to-end digests run the 544 px rows only and cannot be tight per layer.
 
 Per row:
 1. the launch is accepted and leaves ym_last_error alone; rows with a K split or a tail split report the row's own tile count through
-   ym_conv2d_tile_counters.  The library has NO query for the kernel family it picked: the variants that fall back quietly
-   (persistent walker, weight-stationary kernel, ring depths of the 64x64 tile) are held to their documented conditions on the
-   host (conv_geometry.silent_fallback), which is as much as the C-ABI lets a test see;
+   ym_conv2d_tile_counters.  The library is asked which plan it runs for the launch's descriptor (ym_conv2d_effective_plan) and
+   that plan is the row's own -- tile, kwaves, kernel family and ring depth, tail -- or, for a row of
+   conv_geometry.KNOWN_FALLBACKS, exactly the plan listed there; the family a row is tallied under is the one that ran;
 2. the output was prefilled with NaN: none is left;
 3. the guard bands around every output segment keep their fill pattern;
 4. EVERY output element is compared with an fp64 evaluation of the same fp32 operands (plain torch ops on the device, one fp64
@@ -206,9 +206,8 @@ def check_row(key, row, gen, counters):
     g = G.resolve(key)
     assert g is not None, f'{key}: no layer of any model / image size / batch has this shape'
     plan, mma = G.launch_plan(g, row)
-    why = G.silent_fallback(g, plan, mma)
-    assert why is None, f'{g.describe()} row {row}: {why}'
     L = Launch(g, plan, mma, gen, counters)
+    effective = G.check_effective(g, row, plan, mma, L.desc)
     where = f'{g.describe()} row {row}'
     if plan.tile_m and plan.ksplit >= 1:                       # the row's own tile count, when slices of K meet in memory
         split = plan.tail_tiles > 0 or (plan.ksplit > 1 and not plan.wave)
@@ -249,7 +248,7 @@ def check_row(key, row, gen, counters):
     L.run()
     assert all(torch.equal(a, t) for a, t in zip(first, L.bufs)), f'{where}: a second launch into the same buffers differs'
     assert bool((counters == 0).all()), where
-    return G.family(g, plan, mma), err
+    return G.family(g, effective, mma), err
 
 
 @pytest.mark.parametrize('shard', range(NSHARDS))

@@ -1076,7 +1076,7 @@ def test_conv_dgrad_staging_variants_agree(cin, cout, k, stride, hw, b):
 
 @pytest.mark.parametrize('cin,cout,k,hw,b', [(64, 128, 3, 69, 1), (128, 256, 1, 23, 2), (64, 64, 3, 40, 2)])
 def test_stride2_dgrad_with_a_k_split_and_no_arrival_counters(cin, cout, k, hw, b, monkeypatch):
-    """Stride-2 data gradients order their GEMM rows by output-pixel parity class (make_plan: `cls`); only the fused split-K
+    """Stride-2 data gradients order their GEMM rows by output-pixel parity class (conv_planner.hip, plan_tiles: `cls`); only the fused split-K
     finish knows how to map such a row back to its dx pixel.  Without arrival counters (`tile_counters` = NULL: the header calls
     them optional; hip.conv2d_fwd drops them above 16384 tiles) a K split ends in `conv_splitk_reduce`, which reads plain
     [M][Cout] slabs -- the planner must then fall back to the gather over all taps.  Odd sizes (69, 23: the four classes have

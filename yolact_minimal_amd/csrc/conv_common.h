@@ -212,10 +212,42 @@ __device__ __forceinline__ void epilogue_store(const ConvP& p, int m, int n, flo
 }
 
 
+// What ym_conv2d_fwd decides before it launches (conv_planner.hip); the queries of the C ABI read the same fields.
+enum ConvFamily { CONV_IGEMM, CONV_WAVE, CONV_WAVE_DMA, CONV_WS, CONV_PERS };
+struct Plan {
+    int bm, bn, ksplit, kt_per_split, tiles_m, tiles_n, nkt, M;
+    int tail_tiles, tail_split, tail_ktps;     // 0 = no tail
+    // stride-2 data gradient by output-pixel parity class (ConvP::cls): M is then the class-padded row count
+    int cls, M_pix, cls_tile0[5], cls_rows[4], cls_w[4], cls_hw[4], cls_kh0[4], cls_kw0[4], cls_nkw[4], cls_nkt[4];
+    int kwaves;                                // ym_conv_desc.kwaves (wave kernels)
+    int family;                                // ConvFamily: conv_igemm_f32, conv_wave_f32, conv_wdma_f32, conv1x1_ws, conv_igemm_pers
+    int ring = 2;                              // depth of the operand ring (0: the wave kernel without DMA)
+    int mode = 0, spl = 0;                     // conv_igemm_f32 / conv_igemm_pers: MODE; conv_igemm_f32: split-bf16 planes (0: f32 MFMA)
+    bool dl = false, pf = false, pyramid = false;   // conv_igemm_f32: direct-to-LDS ring, pipelined fragments, pyramid input
+    int grid_wgs;                              // ym_conv_desc.grid_wgs where the chosen kernel reads it, else 0
+    int pers_grid;                             // persistent walker: workgroups
+    bool pers_defer;
+    bool vec, counters, fuses_bn;              // vector epilogue; arrival counters used; the launch can carry BatchNorm sums
+    int bn_rows;                               // rows of ordered BatchNorm partials (0: !fuses_bn)
+    int slots() const { return tail_tiles > 0 && tail_split > ksplit ? tail_split : ksplit; }
+    size_t ws_bytes(int cout) const {          // uniform split: [ksplit][M][Cout]; tail: [tail_tiles][tail_split][bm][bn]
+        const size_t u = ksplit > 1 ? (size_t)ksplit * M * cout * sizeof(float) : 0;
+        const size_t t = tail_tiles > 0 ? (size_t)tail_tiles * tail_split * bm * bn * sizeof(float) : 0;
+        return u > t ? u : t;
+    }
+    int grid() const { return (tiles_m * tiles_n - tail_tiles) * ksplit + tail_tiles * (tail_tiles > 0 ? tail_split : 0); }
+    int stages() const {                       // the canonical ym_conv_desc.stages of what runs (include/yolact_hip.h)
+        return ring + (family == CONV_PERS ? 40 : family == CONV_WS ? 50 : family == CONV_WAVE_DMA ? 20 : dl ? (pf ? 30 : 20) : 0);
+    }
+};
+
 }  // namespace ymk
 
-// conv_wave.hip: wave-private kernels (stages 22 / 23 / 24: the DMA-ring variant); returns YM_OK / YM_EINVAL (unsupported variant)
-int ym_launch_conv_wave(const ymk::ConvP& p, int tm, int tn, int kwaves, int stages, int waves_per_block, hipStream_t st);
+// conv_planner.hip.  ws_aligned: the workspace is 16-byte aligned (the one input the descriptor does not hold).  Needs no device.
+int ym_conv_plan(const ym_conv_desc* d, bool ws_aligned, ymk::Plan* pl);
+int ym_cu_count();   // of the current device; 256 where there is none
+// conv_wave.hip: wave-private kernels (ring 2 / 3 / 4: the DMA-ring variant, 0: without); returns YM_OK / YM_EINVAL (unsupported variant)
+int ym_launch_conv_wave(const ymk::ConvP& p, int tm, int tn, int kwaves, int ring, int waves_per_block, hipStream_t st);
 // conv_persist.hip: persistent direct-to-LDS kernel (ring of `ns` K tiles, `grid` workgroups walk p.total_items work items);
 // mode 0 = convolution, 2 = data gradient; launches with fused BatchNorm sums are not covered.  YM_EINVAL: no such variant.
 // defer: the un-split item's stores are issued under the next item's MFMAs (costs a dedicated 16 KB accumulator tile in LDS).

@@ -850,178 +850,6 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce(const ConvP p) {
     }
 }
 
-// Can the output be written by the vectorised row-major epilogue (one plain NHWC tensor, 16-byte aligned operands)?  The K-slice
-// exchange of the fused split-K finish / tail split lives in that epilogue.
-bool vec_epilogue(const ym_conv_desc* d) {
-    const ym_conv_seg& g = d->seg[0];
-    const bool aligned = (((uintptr_t)g.out | (uintptr_t)d->residual | (uintptr_t)d->scale | (uintptr_t)d->shift) & 15) == 0;
-    const bool rows_in_order = d->nlevels ? g.batch_stride == 0      // pyramid: the plain output keeps the input's row order
-                                          : g.batch_stride == (int64_t)d->Ho * d->Wo * d->Cout;
-    return d->nseg == 1 && g.n_begin == 0 && g.n_end == d->Cout && g.pitch == d->Cout && rows_in_order && d->Cout % 4 == 0 && aligned;
-}
-
-struct Plan {
-    int bm, bn, ksplit, kt_per_split, tiles_m, tiles_n, nkt, M;
-    int ws = 0;                                  // 1: the weight-stationary 1x1 kernel (conv_ws.hip) with a ring of `ws_ring` stages
-    int ws_ring = 0;
-    int tail_tiles, tail_split, tail_ktps;     // 0 = no tail
-    // stride-2 data gradient by output-pixel parity class (ConvP::cls): M is then the class-padded row count
-    int cls, M_pix, cls_tile0[5], cls_rows[4], cls_w[4], cls_hw[4], cls_kh0[4], cls_kw0[4], cls_nkw[4], cls_nkt[4];
-    int slots() const { return tail_tiles > 0 && tail_split > ksplit ? tail_split : ksplit; }
-    size_t ws_bytes(int cout) const {          // uniform split: [ksplit][M][Cout]; tail: [tail_tiles][tail_split][bm][bn]
-        const size_t u = ksplit > 1 ? (size_t)ksplit * M * cout * sizeof(float) : 0;
-        const size_t t = tail_tiles > 0 ? (size_t)tail_tiles * tail_split * bm * bn * sizeof(float) : 0;
-        return u > t ? u : t;
-    }
-    int grid() const { return (tiles_m * tiles_n - tail_tiles) * ksplit + tail_tiles * (tail_tiles > 0 ? tail_split : 0); }
-};
-
-int make_plan(const ym_conv_desc* d, Plan* pl, bool allow_cls = true) {
-    YM_REQUIRE(d && d->in && d->weight, "conv: null descriptor / pointer");
-    YM_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cout > 0, "conv: bad shape");
-    YM_REQUIRE(d->Cin == 4 || d->Cin % 32 == 0, "conv: Cin must be 4 (stem) or a multiple of 32, got %d", d->Cin);
-    YM_REQUIRE(d->k_pad % BK == 0 && d->k_pad >= d->KH * d->KW * d->Cin, "conv: k_pad %d invalid", d->k_pad);
-    if (d->transposed) {
-        YM_REQUIRE(d->stride == 1 || d->stride == 2, "conv(dgrad): stride must be 1 or 2");
-        YM_REQUIRE(d->Cin % 32 == 0 && d->kwaves == 0, "conv(dgrad): dy channels must be padded to a multiple of 32; workgroup kernel only");
-        YM_REQUIRE(d->H == (d->Ho + 2 * d->pad - d->KH) / d->stride + 1 && d->W == (d->Wo + 2 * d->pad - d->KW) / d->stride + 1,
-                   "conv(dgrad): H/W (dy) inconsistent with Ho/Wo (dx)");
-    } else if (d->nlevels == 0) {
-        YM_REQUIRE(d->Ho == (d->H + 2 * d->pad - d->KH) / d->stride + 1 && d->Wo == (d->W + 2 * d->pad - d->KW) / d->stride + 1,
-                   "conv: Ho/Wo inconsistent with H/W/K/stride/pad");
-    }
-    long long M_levels = 0;
-    if (d->nlevels != 0) {
-        YM_REQUIRE(d->nlevels >= 1 && d->nlevels <= 5, "conv: nlevels must be 0..5");
-        YM_REQUIRE(!d->transposed && d->kwaves == 0 && d->Cin % 32 == 0 && d->stride == 1 && d->KH == d->KW && (d->KH & 1) &&
-                   d->pad == d->KH / 2, "conv(pyramid): stride 1, odd square filter, pad = K/2, Cin %% 32 == 0, workgroup kernel");
-        for (int l = 0; l < d->nlevels; ++l) {
-            YM_REQUIRE(d->level_h[l] > 0 && d->level_w[l] > 0, "conv(pyramid): bad level %d", l);
-            M_levels += (long long)d->B * d->level_h[l] * d->level_w[l];
-        }
-    }
-    YM_REQUIRE(d->nseg >= 1 && d->nseg <= 3, "conv: nseg must be 1..3");
-    for (int s = 0; s < d->nseg; ++s)
-        YM_REQUIRE(d->seg[s].out && d->seg[s].n_end > d->seg[s].n_begin && d->seg[s].n_end <= d->Cout,
-                   "conv: bad segment %d", s);
-    const long long M = d->nlevels ? M_levels : (long long)d->B * d->Ho * d->Wo;
-    YM_REQUIRE(M * (long long)d->Cout < (1ll << 31) && (d->nlevels ? M : (long long)d->B * d->H * d->W) * d->Cin < (1ll << 31) * 1ll,
-               "conv: tensor too large for 32-bit indexing");
-    pl->M = (int)M;
-    pl->M_pix = (int)M;
-    pl->cls = 0;
-    pl->nkt = d->k_pad / BK;
-    pl->tail_tiles = 0; pl->tail_split = 0; pl->tail_ktps = 0;
-    int bm = d->tile_m, bn = d->tile_n;
-    if (bm == 0 || bn == 0) {
-        // largest tile that still gives every CU at least ~2 workgroups
-        const int cand[3][2] = {{128, 128}, {128, 64}, {64, 64}};
-        bm = 64; bn = 64;
-        for (int c = 0; c < 3; ++c) {
-            const long long wgs = (long long)ym_cdiv(pl->M, cand[c][0]) * ym_cdiv(d->Cout, cand[c][1]);
-            if (wgs >= 512) { bm = cand[c][0]; bn = cand[c][1]; break; }
-        }
-        if (d->Cin == 4) { bm = 128; bn = 64; }
-    }
-    pl->ws = 0; pl->ws_ring = 0;
-    if (d->stages >= 52 && d->stages <= 54) {
-        // weight-stationary 1x1 kernel (conv_ws.hip): a plain GEMM with the filter slice resident in LDS.  What it does not cover
-        // (a filter with taps, a stride, BatchNorm-backward sums, too much filter for the LDS) runs as a 64x64 direct-to-LDS launch.
-        const bool shape_ok = (bm == 64 && bn == 256) || (bm == 128 && bn == 128) || (bm == 256 && bn == 64);
-        const int act = d->seg[0].act;
-        const bool ok = shape_ok && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cin % 32 == 0 && d->k_pad == d->Cin &&
-                        d->nlevels == 0 && d->kwaves == 0 && d->mma == 0 && d->bnb_y == nullptr && vec_epilogue(d) &&
-                        (act == YM_ACT_NONE || act == YM_ACT_RELU) && (size_t)bn * d->Cin * 4 <= (64u << 10) &&
-                        ym_conv_ws_lds_bytes(bm, bn, pl->nkt, d->stages - 50) <= (160u << 10) && (unsigned long long)M * d->Cout * 4ull < 0xFFFFFFF0ull &&
-                        (unsigned long long)M * d->Cin * 4ull < 0xFFFFFFF0ull;      // (conv_ws.hip forms A and C offsets in 32 bits)
-        if (ok) {
-            pl->bm = bm; pl->bn = bn; pl->tiles_m = ym_cdiv(pl->M, bm); pl->tiles_n = ym_cdiv(d->Cout, bn);
-            pl->ksplit = 1; pl->kt_per_split = pl->nkt;
-            pl->ws = 1; pl->ws_ring = d->stages - 50;
-            return YM_OK;
-        }
-        bm = 64; bn = 64;
-    }
-    if (d->kwaves > 0) {
-        YM_REQUIRE(d->Cin != 4, "conv: the wave-private kernel does not support the stem (Cin == 4)");
-        YM_REQUIRE((bm == 32 || bm == 64) && (bn == 32 || bn == 64), "conv(wave): tile must be 32/64, got %dx%d", bm, bn);
-        pl->bm = bm; pl->bn = bn; pl->tiles_m = ym_cdiv(pl->M, bm); pl->tiles_n = ym_cdiv(d->Cout, bn);
-        pl->ksplit = 1; pl->kt_per_split = pl->nkt;
-        // tail split of the wave-private DMA-ring kernel (conv_wave.hip): 32x32 tile with four K waves, plain NHWC output, counters
-        if (d->tail_tiles > 0 && d->tail_ksplit > 1 && d->stages >= 22 && d->stages <= 24 && bm == 32 && bn == 32 && d->kwaves == 4 &&
-            (d->grid_wgs == 0 || d->grid_wgs == 4) && d->tile_counters && vec_epilogue(d)) {
-            YM_REQUIRE(d->tail_tiles <= pl->tiles_m * pl->tiles_n, "conv(wave): tail_tiles %d > %d output tiles", d->tail_tiles, pl->tiles_m * pl->tiles_n);
-            int ts = d->tail_ksplit > pl->nkt ? pl->nkt : d->tail_ksplit;
-            if (ts > 8) ts = 8;                                    // (the last arriver gathers up to 8 slices at once)
-            pl->tail_ktps = ym_cdiv(pl->nkt, ts);
-            pl->tail_split = ym_cdiv(pl->nkt, pl->tail_ktps);
-            pl->tail_tiles = pl->tail_split > 1 ? d->tail_tiles : 0;
-        }
-        return YM_OK;
-    }
-    YM_REQUIRE((bm == 128 || bm == 64) && (bn == 128 || bn == 64), "conv: tile must be 64/128");
-    YM_REQUIRE(d->Cin != 4 || (bm == 128 && bn == 64), "conv: stem mode supports the 128x64 tile only");
-    pl->bm = bm; pl->bn = bn;
-    {
-        // Stride-2 data gradient: rows ordered by output-pixel parity class, every class padded to whole M tiles, and only the
-        // class's filter taps in its K range (ConvP::cls).  YM_DGRAD_CLASSES=0: the gather over all taps of rounds 1-3 (A/B).
-        static int on = -1;
-        if (on < 0) { const char* e = getenv("YM_DGRAD_CLASSES"); on = e ? atoi(e) : 1; }
-        if (on && allow_cls && d->transposed && d->stride == 2 && d->nlevels == 0 && vec_epilogue(d)) {
-            int t0 = 0, nkt_max = 0, nt_max = 0;
-            for (int c = 0; c < 4; ++c) {
-                const int ph = c >> 1, pw = c & 1;
-                const int hc = (d->Ho - ph + 1) / 2, wc = (d->Wo - pw + 1) / 2;          // dx rows / columns of this parity
-                const int kh0 = (ph + d->pad) & 1, kw0 = (pw + d->pad) & 1;
-                const int nkh = kh0 < d->KH ? (d->KH - kh0 + 1) / 2 : 0, nkw = kw0 < d->KW ? (d->KW - kw0 + 1) / 2 : 0;
-                pl->cls_tile0[c] = t0;
-                pl->cls_rows[c] = d->B * hc * wc;
-                pl->cls_w[c] = wc > 0 ? wc : 1;
-                pl->cls_hw[c] = hc * wc > 0 ? hc * wc : 1;
-                pl->cls_kh0[c] = kh0; pl->cls_kw0[c] = kw0; pl->cls_nkw[c] = nkw > 0 ? nkw : 1;
-                pl->cls_nkt[c] = nkh * nkw * (d->Cin / BK);
-                if (pl->cls_nkt[c] > nkt_max) nkt_max = pl->cls_nkt[c];
-                t0 += ym_cdiv(pl->cls_rows[c], bm);
-                if (ym_cdiv(pl->cls_rows[c], bm) > nt_max) nt_max = ym_cdiv(pl->cls_rows[c], bm);
-            }
-            pl->cls_tile0[4] = t0;
-            pl->cls = 1;
-            pl->M = 4 * nt_max * bm;                       // M tile t belongs to class t & 3 (its tile t >> 2): see the kernel
-            pl->nkt = nkt_max > 0 ? nkt_max : 1;
-        }
-    }
-    pl->tiles_m = ym_cdiv(pl->M, bm);
-    pl->tiles_n = ym_cdiv(d->Cout, bn);
-    int ks = d->ksplit;
-    if (ks <= 0) {
-        ks = 1;
-        const int wgs = pl->tiles_m * pl->tiles_n;
-        if (wgs < 256) {
-            ks = ym_cdiv(512, wgs);
-            const int max_ks = pl->nkt / 4 > 0 ? pl->nkt / 4 : 1;   // keep >= 4 K tiles per slice
-            if (ks > max_ks) ks = max_ks;
-            if (ks > 16) ks = 16;
-        }
-    }
-    if (ks > pl->nkt) ks = pl->nkt;
-    if (ks < 1) ks = 1;
-    pl->kt_per_split = ym_cdiv(pl->nkt, ks);
-    pl->ksplit = ym_cdiv(pl->nkt, pl->kt_per_split);
-    if (d->tail_tiles > 0 && d->tail_ksplit > 1 && vec_epilogue(d)) {   // (a segmented / unaligned output ignores the tail knobs)
-        YM_REQUIRE(d->tile_counters && pl->ksplit == 1 && d->Cin != 4, "conv: tail_tiles needs tile_counters, ksplit <= 1 and Cin %% 32 == 0");
-        YM_REQUIRE(d->tail_tiles <= pl->tiles_m * pl->tiles_n, "conv: tail_tiles %d > %d output tiles", d->tail_tiles, pl->tiles_m * pl->tiles_n);
-        int ts = d->tail_ksplit > pl->nkt ? pl->nkt : d->tail_ksplit;
-        pl->tail_ktps = ym_cdiv(pl->nkt, ts);
-        pl->tail_split = ym_cdiv(pl->nkt, pl->tail_ktps);
-        pl->tail_tiles = pl->tail_split > 1 ? d->tail_tiles : 0;
-    }
-    // The class-ordered rows exist only inside the launch: K slices of such a plan must meet in the fused finish (arrival counters),
-    // which maps a tile row back to its dx pixel.  `conv_splitk_reduce` reads the slabs as plain [M][Cout] rows, so without counters
-    // (none given, or a workspace past the 32-bit exchange offsets) the plan falls back to the gather over all taps.
-    if (pl->cls && pl->slots() > 1 && (!d->tile_counters || pl->ws_bytes(d->Cout) >= 0xFFFFFFF0ull)) return make_plan(d, pl, false);
-    return YM_OK;
-}
-
 template <int BM, int BN, int MODE, int NS = 2, bool DL = false, bool PF = false, bool RG = false, int SPL = 0>
 void launch(const ConvP& p, int grid, hipStream_t st) {
     size_t lds = SPL ? (size_t)2 * (BM + BN) * SPL * 80 : (size_t)NS * (BM + BN) * (DL ? 32 : PITCH) * sizeof(float);
@@ -1032,60 +860,87 @@ void launch(const ConvP& p, int grid, hipStream_t st) {
     hipLaunchKernelGGL((conv_igemm_f32<BM, BN, MODE, NS, DL, PF, RG, SPL>), dim3(grid), dim3(256), lds, st, p);
 }
 
-template <int MODE, int SPL, int NS>
-void launch_split_ns(const ConvP& p, int bm, int bn, int grid, hipStream_t st) {
-    if (bm == 128 && bn == 128) launch<128, 128, MODE, NS, false, false, false, SPL>(p, grid, st);
-    else if (bm == 128 && bn == 64) launch<128, 64, MODE, NS, false, false, false, SPL>(p, grid, st);
-    else if (bm == 64 && bn == 128) launch<64, 128, MODE, NS, false, false, false, SPL>(p, grid, st);
-    else launch<64, 64, MODE, NS, false, false, false, SPL>(p, grid, st);
+// Every conv_igemm_f32 instantiation the library builds, one per line: <BM, BN, MODE, NS, DL, PF, RG, SPL>.  The planner
+// (conv_planner.hip: plan_variant) resolves a descriptor to one of them; a combination outside the list is a planner bug.
+bool launch_igemm(const ConvP& p, const Plan& pl, int grid, hipStream_t st) {
+#define YM_V(BM_, BN_, MODE_, NS_, DL_, PF_, RG_, SPL_)                                                                               \
+    if (pl.bm == BM_ && pl.bn == BN_ && pl.mode == MODE_ && pl.ring == NS_ && pl.dl == DL_ && pl.pf == PF_ && pl.pyramid == RG_ && \
+        pl.spl == SPL_) { launch<BM_, BN_, MODE_, NS_, DL_, PF_, RG_, SPL_>(p, grid, st); return true; }
+    YM_V(128, 128, 0, 2, 0, 0, 0, 0)
+    YM_V(128, 128, 0, 2, 1, 0, 0, 0)
+    YM_V(128, 128, 0, 3, 1, 0, 0, 0)
+    YM_V(128,  64, 0, 2, 0, 0, 0, 0)
+    YM_V(128,  64, 0, 3, 0, 0, 0, 0)
+    YM_V(128,  64, 0, 2, 1, 0, 0, 0)
+    YM_V(128,  64, 0, 3, 1, 0, 0, 0)
+    YM_V( 64, 128, 0, 2, 0, 0, 0, 0)
+    YM_V( 64, 128, 0, 3, 0, 0, 0, 0)
+    YM_V( 64, 128, 0, 2, 1, 0, 0, 0)
+    YM_V( 64, 128, 0, 3, 1, 0, 0, 0)
+    YM_V( 64,  64, 0, 2, 0, 0, 0, 0)
+    YM_V( 64,  64, 0, 3, 0, 0, 0, 0)
+    YM_V( 64,  64, 0, 2, 1, 0, 0, 0)
+    YM_V( 64,  64, 0, 3, 1, 0, 0, 0)
+    YM_V( 64,  64, 0, 4, 1, 0, 0, 0)
+    YM_V( 64,  64, 0, 3, 1, 1, 0, 0)
+    YM_V( 64,  64, 0, 4, 1, 1, 0, 0)
+    YM_V(128, 128, 2, 2, 0, 0, 0, 0)
+    YM_V(128, 128, 2, 2, 1, 0, 0, 0)
+    YM_V(128, 128, 2, 3, 1, 0, 0, 0)
+    YM_V(128,  64, 2, 2, 0, 0, 0, 0)
+    YM_V(128,  64, 2, 2, 1, 0, 0, 0)
+    YM_V(128,  64, 2, 3, 1, 0, 0, 0)
+    YM_V( 64, 128, 2, 2, 0, 0, 0, 0)
+    YM_V( 64, 128, 2, 2, 1, 0, 0, 0)
+    YM_V( 64, 128, 2, 3, 1, 0, 0, 0)
+    YM_V( 64,  64, 2, 2, 0, 0, 0, 0)
+    YM_V( 64,  64, 2, 3, 0, 0, 0, 0)
+    YM_V( 64,  64, 2, 2, 1, 0, 0, 0)
+    YM_V( 64,  64, 2, 3, 1, 0, 0, 0)
+    YM_V(128,  64, 1, 2, 0, 0, 0, 0)
+    YM_V(128, 128, 0, 2, 0, 0, 1, 0)
+    YM_V(128,  64, 0, 2, 0, 0, 1, 0)
+    YM_V( 64, 128, 0, 2, 0, 0, 1, 0)
+    YM_V( 64,  64, 0, 2, 0, 0, 1, 0)
+    YM_V(128, 128, 0, 2, 0, 0, 0, 2)
+    YM_V(128, 128, 0, 3, 0, 0, 0, 2)
+    YM_V(128,  64, 0, 2, 0, 0, 0, 2)
+    YM_V(128,  64, 0, 3, 0, 0, 0, 2)
+    YM_V( 64, 128, 0, 2, 0, 0, 0, 2)
+    YM_V( 64, 128, 0, 3, 0, 0, 0, 2)
+    YM_V( 64,  64, 0, 2, 0, 0, 0, 2)
+    YM_V( 64,  64, 0, 3, 0, 0, 0, 2)
+    YM_V(128, 128, 0, 2, 0, 0, 0, 3)
+    YM_V(128, 128, 0, 3, 0, 0, 0, 3)
+    YM_V(128,  64, 0, 2, 0, 0, 0, 3)
+    YM_V(128,  64, 0, 3, 0, 0, 0, 3)
+    YM_V( 64, 128, 0, 2, 0, 0, 0, 3)
+    YM_V( 64, 128, 0, 3, 0, 0, 0, 3)
+    YM_V( 64,  64, 0, 2, 0, 0, 0, 3)
+    YM_V( 64,  64, 0, 3, 0, 0, 0, 3)
+    YM_V(128, 128, 2, 2, 0, 0, 0, 2)
+    YM_V(128, 128, 2, 3, 0, 0, 0, 2)
+    YM_V(128,  64, 2, 2, 0, 0, 0, 2)
+    YM_V(128,  64, 2, 3, 0, 0, 0, 2)
+    YM_V( 64, 128, 2, 2, 0, 0, 0, 2)
+    YM_V( 64, 128, 2, 3, 0, 0, 0, 2)
+    YM_V( 64,  64, 2, 2, 0, 0, 0, 2)
+    YM_V( 64,  64, 2, 3, 0, 0, 0, 2)
+    YM_V(128, 128, 2, 2, 0, 0, 0, 3)
+    YM_V(128, 128, 2, 3, 0, 0, 0, 3)
+    YM_V(128,  64, 2, 2, 0, 0, 0, 3)
+    YM_V(128,  64, 2, 3, 0, 0, 0, 3)
+    YM_V( 64, 128, 2, 2, 0, 0, 0, 3)
+    YM_V( 64, 128, 2, 3, 0, 0, 0, 3)
+    YM_V( 64,  64, 2, 2, 0, 0, 0, 3)
+    YM_V( 64,  64, 2, 3, 0, 0, 0, 3)
+#undef YM_V
+    return false;
 }
-template <int MODE, int SPL>
-void launch_split(const ConvP& p, int bm, int bn, int stages, int grid, hipStream_t st) {
-    // stages 3: two register sets (the tile converted into LDS during an iteration was loaded a whole iteration earlier)
-    if (stages == 3) launch_split_ns<MODE, SPL, 3>(p, bm, bn, grid, st);
-    else launch_split_ns<MODE, SPL, 2>(p, bm, bn, grid, st);
-}
 
-}  // namespace
-
-extern "C" size_t ym_sizeof_conv_desc(void) { return sizeof(ym_conv_desc); }
-
-extern "C" size_t ym_conv2d_workspace_bytes(const ym_conv_desc* d) {
-    Plan pl;
-    if (make_plan(d, &pl) != YM_OK) return 0;
-    return pl.ws_bytes(d->Cout);
-}
-
-extern "C" int ym_conv2d_tile_counters(const ym_conv_desc* d) {
-    Plan pl;
-    if (make_plan(d, &pl) != YM_OK) return 0;
-    return pl.slots() > 1 ? pl.tiles_m * pl.tiles_n : 0;
-}
-
-extern "C" int ym_conv2d_fuses_bn_stats(const ym_conv_desc* d) {
-    Plan pl;
-    if (make_plan(d, &pl) != YM_OK) return 0;
-    return (vec_epilogue(d) && (pl.slots() == 1 || d->tile_counters) && d->kwaves == 0) ? 1 : 0;
-}
-
-extern "C" int ym_conv2d_bn_partial_rows(const ym_conv_desc* d) {
-    Plan pl;
-    if (make_plan(d, &pl) != YM_OK) return 0;
-    if (!(vec_epilogue(d) && (pl.slots() == 1 || d->tile_counters) && d->kwaves == 0)) return 0;      // (ym_conv2d_fuses_bn_stats)
-    if (pl.ws) return ym_conv_ws_partial_rows(pl.M, d->Cout, pl.bm, pl.bn, pl.nkt, pl.ws_ring, d->grid_wgs);
-    return pl.tiles_m;                           // one row per M tile (a stride-2 data gradient: the class-padded tiles)
-}
-
-extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    Plan pl;
-    int rc = make_plan(d, &pl);
-    if (rc != YM_OK) return rc;
+// Everything the kernels read: the descriptor's operands and shape, the plan's tiling, and what only a launch can check.
+int fill_params(const ym_conv_desc* d, const Plan& pl, void* workspace, ConvP& p) {
     const size_t need = pl.ws_bytes(d->Cout);
-    if (need > workspace_bytes || (need && !workspace)) {
-        ym_set_error("conv: workspace %zu B < %zu B needed (ksplit %d)", workspace_bytes, need, pl.ksplit);
-        return YM_ENOSPC;
-    }
-    ConvP p;
     p.in = d->in; p.w = d->weight; p.scale = d->scale; p.shift = d->shift; p.residual = d->residual;
     p.ws = (float*)workspace;
     p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW;
@@ -1127,10 +982,8 @@ extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t work
             p.seg[i] = SegDev{nullptr, 0, 0, 0, 0, 0};
         }
     }
-    {
-        YM_REQUIRE(pl.tail_tiles == 0 || ((uintptr_t)workspace & 15) == 0, "conv: tail split needs a 16-byte aligned workspace");
-        p.vec = (vec_epilogue(d) && ((uintptr_t)workspace & 15) == 0) ? 1 : 0;
-    }
+    YM_REQUIRE(pl.tail_tiles == 0 || ((uintptr_t)workspace & 15) == 0, "conv: tail split needs a 16-byte aligned workspace");
+    p.vec = pl.vec;
     p.bn_sum = d->bn_sum; p.bn_sumsq = d->bn_sumsq; p.bn_ordered = (d->bn_sum && d->bn_ordered) ? 1 : 0;
     p.bnb_y = d->bnb_y; p.bnb_out = d->bnb_out; p.bnb_mean = d->bnb_mean; p.bnb_invstd = d->bnb_invstd;
     p.bnb_gamma = d->bnb_gamma; p.bnb_beta = d->bnb_beta; p.bnb_relu = d->bnb_relu;
@@ -1145,7 +998,7 @@ extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t work
     if (p.trace_ring <= 0) p.trace_epoch = nullptr;
     if (const char* e = getenv("YM_PERS_ABL")) { if (!d->bn_sum) p.bnb_relu = atoi(e); }      // conv_persist.hip ablations (trace build only)
 #endif
-    p.counters = (p.vec && pl.slots() > 1 && (d->kwaves == 0 || pl.tail_tiles > 0) && need < 0xFFFFFFF0ull) ? d->tile_counters : nullptr;
+    p.counters = pl.counters ? d->tile_counters : nullptr;
     YM_REQUIRE(!pl.cls || (p.vec && (pl.slots() == 1 || p.counters)), "conv(dgrad, stride 2): the class-ordered plan needs a 16-byte aligned workspace");
     YM_REQUIRE(pl.tail_tiles == 0 || p.counters, "conv: tail_tiles needs a plain NHWC output (vector epilogue) and a workspace < 4 GiB");
     p.main_tiles = pl.tiles_m * pl.tiles_n - pl.tail_tiles;
@@ -1158,8 +1011,9 @@ extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t work
     p.fd_howo = FastDiv::make((unsigned)(d->Ho * d->Wo));
     p.fd_wo = FastDiv::make((unsigned)d->Wo); p.fd_cin = FastDiv::make((unsigned)d->Cin); p.fd_kw = FastDiv::make((unsigned)d->KW);
     p.ws_bytes = (unsigned)(need < 0xFFFFFFF0ull ? need : 0);
+    p.total_items = pl.grid();
     if (d->bn_sum) {
-        YM_REQUIRE((d->bn_sumsq || d->bn_ordered) && ((uintptr_t)d->bn_sum & 7) == 0 && p.vec && (pl.slots() == 1 || p.counters) && d->kwaves == 0,
+        YM_REQUIRE((d->bn_sumsq || d->bn_ordered) && ((uintptr_t)d->bn_sum & 7) == 0 && pl.fuses_bn,
                    "conv: bn_sum given but this configuration cannot fuse the statistics (ask ym_conv2d_fuses_bn_stats)");
     }
     if (d->bnb_y) {
@@ -1168,86 +1022,80 @@ extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t work
         YM_REQUIRE(d->Cout % 4 == 0 && ((uintptr_t)d->bnb_y & 15) == 0 && ((uintptr_t)d->bnb_out & 15) == 0,
                    "conv: bnb_y / bnb_out must be 16-byte aligned [M][Cout] tensors");
     }
-    if (d->bn_sum && !d->bn_ordered) ym_note_unordered_sum();      // (the epilogue ends in fp64 atomics)
-    hipStream_t st = (hipStream_t)s;
-    if (d->kwaves > 0) {
-        const bool dma = d->stages >= 22 && d->stages <= 24;
-        YM_REQUIRE(!dma || (d->Cin % 32 == 0 && d->nlevels == 0 && !d->transposed && (size_t)pl.M * d->Cout * 4 < 0xFFFFFFF0ull),
-                   "conv(wave, DMA ring): needs Cin %% 32 == 0, one input size, a forward convolution");
-        return ym_launch_conv_wave(p, pl.bm, pl.bn, d->kwaves, d->stages, d->grid_wgs, st);
-    }
-    if (pl.ws) return ym_launch_conv_ws(p, pl.bm, pl.bn, pl.ws_ring, d->grid_wgs, st);
-    const int grid = pl.grid();
-    p.total_items = grid;
-    int stages = d->stages;
-    if (stages >= 52 && stages <= 54) stages = 22;       // (a weight-stationary request the kernel does not cover: see make_plan)
-    if (stages >= 42 && stages <= 48) {
-        // persistent direct-to-LDS kernel (conv_persist.hip); what it does not cover runs on the non-persistent ring of the same depth
-        const int ns = stages - 40;
-        const int act = d->seg[0].act;
-        const bool ok = p.vec && pl.bm == 64 && pl.bn == 64 && d->Cin % 32 == 0 && d->nlevels == 0 && d->mma == 0 && !pl.cls &&
-                        (act == YM_ACT_NONE || act == YM_ACT_RELU) && (pl.slots() == 1 || p.counters) && d->bn_sum == nullptr &&
-                        (ns == 2 || ns == 3 || ns == 4 || ns == 6 || ns == 8);
-        if (ok) {
-            static int cus = 0;
-            if (cus == 0) {
-                int dev = 0, n = 0;
-                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-                cus = n;
-            }
-            static int defer = -1;                            // YM_PERS_DEFER=0: the synchronous epilogue (A/B experiments)
-            if (defer < 0) { const char* e = getenv("YM_PERS_DEFER"); defer = e ? atoi(e) : 1; }
-            int per_cu = (int)((160u << 10) / ym_conv_pers_lds_bytes(64, 64, ns, defer != 0));
-            if (per_cu > 4) per_cu = 4;                       // 128 VGPRs: four waves per SIMD
-            if (per_cu < 1) per_cu = 1;
-            int g = d->grid_wgs > 0 ? d->grid_wgs : cus * per_cu;
-            if (g > grid) g = grid;
-            if (g >= 8 && g < grid) g &= ~7;                  // a workgroup's items then all lie in its own XCD's chunk of the tile space
-            return ym_launch_conv_pers(p, 64, 64, d->transposed ? 2 : 0, ns, defer != 0, g, st);
-        }
-        stages = ns >= 4 && pl.bm == 64 && pl.bn == 64 && !d->transposed ? 24 : (ns == 2 ? 22 : 23);
-    }
-    // stages: 0/2 register-staged double buffer, 3 register-staged ring of 3 (64-wide tiles), 22/23/24 direct-to-LDS ring of 2/3/4,
-    // 33/34 direct-to-LDS ring of 3/4 with software-pipelined fragments (64x64 forward tile)
-#define YM_TILE_CASE(BM_, BN_, MODE_, HAS3_)                                                          \
-    do {                                                                                              \
-        if (stages == 23) launch<BM_, BN_, MODE_, 3, true>(p, grid, st);                           \
-        else if (stages == 22) launch<BM_, BN_, MODE_, 2, true>(p, grid, st);                      \
-        else if (stages == 3 && HAS3_) launch<BM_, BN_, MODE_, HAS3_ ? 3 : 2>(p, grid, st);        \
-        else launch<BM_, BN_, MODE_, 2>(p, grid, st);                                                 \
-    } while (0)
-    if (d->mma != 0) {                                  // split-bf16 products (see SPL above); tensors stay fp32
+    YM_REQUIRE(pl.family != CONV_WAVE_DMA || (size_t)pl.M * d->Cout * 4 < 0xFFFFFFF0ull, "conv(wave, DMA ring): the output must be < 4 GiB");
+    if (pl.family == CONV_IGEMM && d->mma != 0) {
         YM_REQUIRE(d->mma == 3 || d->mma == 6, "conv: mma must be 0 (f32 MFMA), 3 (bf16x3) or 6 (bf16x6), got %d", d->mma);
         YM_REQUIRE(d->nlevels == 0 && d->Cin % 32 == 0, "conv: split-bf16 mode needs Cin %% 32 == 0 and a single-size input");
-        if (d->transposed) { if (d->mma == 3) launch_split<2, 2>(p, pl.bm, pl.bn, stages, grid, st); else launch_split<2, 3>(p, pl.bm, pl.bn, stages, grid, st); }
-        else { if (d->mma == 3) launch_split<0, 2>(p, pl.bm, pl.bn, stages, grid, st); else launch_split<0, 3>(p, pl.bm, pl.bn, stages, grid, st); }
-    } else if (d->nlevels > 0) {                        // pyramid input: register-staged double buffer
-        if (pl.bm == 128 && pl.bn == 128) launch<128, 128, 0, 2, false, false, true>(p, grid, st);
-        else if (pl.bm == 128 && pl.bn == 64) launch<128, 64, 0, 2, false, false, true>(p, grid, st);
-        else if (pl.bm == 64 && pl.bn == 128) launch<64, 128, 0, 2, false, false, true>(p, grid, st);
-        else launch<64, 64, 0, 2, false, false, true>(p, grid, st);
-    } else if (d->transposed) {
-        if (pl.bm == 128 && pl.bn == 128) YM_TILE_CASE(128, 128, 2, false);
-        else if (pl.bm == 128 && pl.bn == 64) YM_TILE_CASE(128, 64, 2, false);
-        else if (pl.bm == 64 && pl.bn == 128) YM_TILE_CASE(64, 128, 2, false);
-        else YM_TILE_CASE(64, 64, 2, true);
-    } else if (d->Cin == 4) launch<128, 64, 1>(p, grid, st);
-    else if (pl.bm == 128 && pl.bn == 128) YM_TILE_CASE(128, 128, 0, false);
-    else if (pl.bm == 128 && pl.bn == 64) YM_TILE_CASE(128, 64, 0, true);
-    else if (pl.bm == 64 && pl.bn == 128) YM_TILE_CASE(64, 128, 0, true);
-    else if (stages == 24) launch<64, 64, 0, 4, true>(p, grid, st);
-    else if (stages == 33) launch<64, 64, 0, 3, true, true>(p, grid, st);
-    else if (stages == 34) launch<64, 64, 0, 4, true, true>(p, grid, st);
-    else YM_TILE_CASE(64, 64, 0, true);
-#undef YM_TILE_CASE
-    rc = ym_check_launch("conv_igemm_f32");
-    if (rc != YM_OK) return rc;
-    if (pl.ksplit > 1 && !p.counters) {
-        const size_t total = (size_t)pl.M * d->Cout;
+    }
+    return YM_OK;
+}
+
+int launch_plan(const ConvP& p, const Plan& pl, hipStream_t st) {
+    switch (pl.family) {
+        case CONV_WAVE: case CONV_WAVE_DMA: return ym_launch_conv_wave(p, pl.bm, pl.bn, pl.kwaves, pl.ring, pl.grid_wgs, st);
+        case CONV_WS: return ym_launch_conv_ws(p, pl.bm, pl.bn, pl.ring, pl.grid_wgs, st);
+        case CONV_PERS: return ym_launch_conv_pers(p, pl.bm, pl.bn, pl.mode, pl.ring, pl.pers_defer, pl.pers_grid, st);
+    }
+    if (!launch_igemm(p, pl, pl.grid(), st)) {
+        ym_set_error("conv: no conv_igemm_f32<%d, %d, %d, %d, %d, %d, %d, %d> is built (planner bug)", pl.bm, pl.bn, pl.mode, pl.ring, pl.dl, pl.pf, pl.pyramid, pl.spl);
+        return YM_EINVAL;
+    }
+    int rc = ym_check_launch("conv_igemm_f32");
+    if (rc == YM_OK && pl.ksplit > 1 && !p.counters) {
+        const size_t total = (size_t)p.M * p.Cout;
         int rgrid = (int)((total / (p.vec ? 4 : 1) + 255) / 256);
         if (rgrid > 2048) rgrid = 2048;
         hipLaunchKernelGGL(conv_splitk_reduce, dim3(rgrid), dim3(256), 0, st, p);
         rc = ym_check_launch("conv_splitk_reduce");
     }
     return rc;
+}
+
+}  // namespace
+
+extern "C" size_t ym_sizeof_conv_desc(void) { return sizeof(ym_conv_desc); }
+
+// (the queries assume a 16-byte aligned workspace)
+extern "C" size_t ym_conv2d_workspace_bytes(const ym_conv_desc* d) {
+    Plan pl;
+    return ym_conv_plan(d, true, &pl) == YM_OK ? pl.ws_bytes(d->Cout) : 0;
+}
+
+extern "C" int ym_conv2d_tile_counters(const ym_conv_desc* d) {
+    Plan pl;
+    return ym_conv_plan(d, true, &pl) == YM_OK && pl.slots() > 1 ? pl.tiles_m * pl.tiles_n : 0;
+}
+
+extern "C" int ym_conv2d_fuses_bn_stats(const ym_conv_desc* d) {
+    Plan pl;
+    return ym_conv_plan(d, true, &pl) == YM_OK && pl.fuses_bn ? 1 : 0;
+}
+
+extern "C" int ym_conv2d_bn_partial_rows(const ym_conv_desc* d) {
+    Plan pl;
+    return ym_conv_plan(d, true, &pl) == YM_OK ? pl.bn_rows : 0;
+}
+
+extern "C" int ym_conv2d_effective_plan(const ym_conv_desc* d, int32_t out[8]) {
+    Plan pl;
+    YM_REQUIRE(out, "conv: effective_plan needs an output row");
+    if (int rc = ym_conv_plan(d, true, &pl)) return rc;
+    const bool tail = pl.tail_tiles > 0;
+    const int32_t row[8] = {pl.bm, pl.bn, pl.ksplit, d->kwaves, pl.stages(), tail ? pl.tail_tiles : 0, tail ? pl.tail_split : 0, pl.grid_wgs};
+    for (int i = 0; i < 8; ++i) out[i] = row[i];
+    return YM_OK;
+}
+
+extern "C" int ym_conv2d_fwd(const ym_conv_desc* d, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    Plan pl;
+    if (int rc = ym_conv_plan(d, ((uintptr_t)workspace & 15) == 0, &pl)) return rc;
+    const size_t need = pl.ws_bytes(d->Cout);
+    if (need > workspace_bytes || (need && !workspace)) {
+        ym_set_error("conv: workspace %zu B < %zu B needed (ksplit %d)", workspace_bytes, need, pl.ksplit);
+        return YM_ENOSPC;
+    }
+    ConvP p;
+    if (int rc = fill_params(d, pl, workspace, p)) return rc;
+    if (d->bn_sum && !d->bn_ordered) ym_note_unordered_sum();      // (the epilogue ends in fp64 atomics)
+    return launch_plan(p, pl, (hipStream_t)s);
 }

@@ -581,11 +581,11 @@ int dispatch_dma(const ConvP& p, int kwaves, int ns, int wpb, hipStream_t st) {
 
 }  // namespace
 
-int ym_launch_conv_wave(const ConvP& p, int tm, int tn, int kwaves, int stages, int wpb, hipStream_t st) {
-    if (stages >= 22 && stages <= 24) {          // wave-private DMA rings of 2 / 3 / 4 K tiles (Cin % 32 == 0, one input size)
-        if (tm == 32 && tn == 32) return dispatch_dma<1, 1>(p, kwaves, stages - 20, wpb, st);
-        if (tm == 64 && tn == 32) return dispatch_dma<2, 1>(p, kwaves, stages - 20, wpb, st);
-        if (tm == 32 && tn == 64) return dispatch_dma<1, 2>(p, kwaves, stages - 20, wpb, st);
+int ym_launch_conv_wave(const ConvP& p, int tm, int tn, int kwaves, int ring, int wpb, hipStream_t st) {
+    if (ring > 0) {                              // wave-private DMA rings of 2 / 3 / 4 K tiles (Cin % 32 == 0, one input size)
+        if (tm == 32 && tn == 32) return dispatch_dma<1, 1>(p, kwaves, ring, wpb, st);
+        if (tm == 64 && tn == 32) return dispatch_dma<2, 1>(p, kwaves, ring, wpb, st);
+        if (tm == 32 && tn == 64) return dispatch_dma<1, 2>(p, kwaves, ring, wpb, st);
         ym_set_error("conv(wave, DMA ring): tile must be 32x32, 64x32 or 32x64, got %dx%d", tm, tn);
         return YM_EINVAL;
     }

@@ -273,16 +273,10 @@ namespace {
 int ws_walkers(int M, int Cout, int bm, int bn, int nkt, int nstg, int grid_wgs) {
     const int nslices = ym_cdiv(Cout, bn), mblocks = ym_cdiv(M, bm);
     const size_t lds = ym_conv_ws_lds_bytes(bm, bn, nkt, nstg);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n;
-    }
     int per_cu = (int)((160u << 10) / lds);
     if (per_cu > 2) per_cu = 2;                          // ~190 VGPRs: two waves per SIMD
     if (per_cu < 1) per_cu = 1;
-    int total = grid_wgs > 0 ? grid_wgs : cus * per_cu;
+    int total = grid_wgs > 0 ? grid_wgs : ym_cu_count() * per_cu;
     int gm = total / nslices;
     if (gm < 1) gm = 1;
     if (gm > mblocks) gm = mblocks;

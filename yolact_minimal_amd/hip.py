@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     'ym_after_nms_batch_packed', 'ym_pack_masks', 'ym_unpack_masks', 'ym_mask_iou_packed_workspace_bytes', 'ym_mask_iou_packed',
     'ym_rle_encode_packed', 'ym_draw_detections_batch_packed', 'ym_draw_cutout_objects_packed',
     'ym_bn_train_bwd_workspace_bytes', 'ym_bn_train_bwd', 'ym_bn_train_bwd_apply', 'ym_act_bias_bwd', 'ym_conv2d_fuses_bn_stats', 'ym_bn_train_fwd_stats', 'ym_maxpool3x3s2_bwd', 'ym_maxpool3x3s2_fwd_idx', 'ym_maxpool3x3s2_bwd_idx', 'ym_bilinear2x_bwd', 'ym_sgd_step',
-    'ym_conv2d_bn_partial_rows', 'ym_bn_partials_finish', 'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes',
+    'ym_conv2d_bn_partial_rows', 'ym_conv2d_effective_plan', 'ym_bn_partials_finish', 'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes',
 )
 
 
@@ -205,6 +205,7 @@ def lib():
         L.ym_semantic_loss.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp]
         L.ym_conv2d_fuses_bn_stats.argtypes = [ctypes.POINTER(ConvDesc)]
         L.ym_conv2d_bn_partial_rows.argtypes = [ctypes.POINTER(ConvDesc)]
+        L.ym_conv2d_effective_plan.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int32 * 8)]
         L.ym_bn_partials_finish.argtypes = [vp, i32, i32, vp, vp]
         L.ym_unordered_sum_launches.argtypes = []
         L.ym_unordered_sum_launches.restype = ctypes.c_int64
@@ -296,6 +297,14 @@ def conv_workspace_bytes(desc):
         if err and 'conv' in err and desc.tail_tiles > 0:
             raise RuntimeError(f'ym_conv2d_workspace_bytes: {err}')
     return n
+
+
+def conv_effective_plan(desc):
+    """The ConvPlan ym_conv2d_fwd would run for this descriptor (ym_conv2d_effective_plan: canonical `stages`); host only."""
+    from .conv_plan import ConvPlan
+    row = (ctypes.c_int32 * 8)()
+    check(lib().ym_conv2d_effective_plan(ctypes.byref(desc), ctypes.byref(row)), 'ym_conv2d_effective_plan')
+    return ConvPlan(*row)
 
 
 TILE_COUNTERS = 16384     # int32 entries the engines allocate for ym_conv_desc.tile_counters
