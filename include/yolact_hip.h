@@ -115,9 +115,10 @@ typedef struct {
     int32_t mma;             /* matrix pipe of the workgroup kernel.  0 = f32 MFMA (v_mfma_f32_32x32x2_f32: exact fp32 products, the    */
                              /* parity mode).  3 / 6 = "split bf16": every fp32 operand is split on its way into LDS into two / three  */
                              /* bf16 terms and the 3 / 6 most significant cross products run on v_mfma_f32_32x32x16_bf16 with fp32     */
-                             /* accumulation (relative error per product ~2^-17 / ~2^-23; tensors in HBM stay fp32).  Needs Cin % 32   */
-                             /* == 0, kwaves == 0, no pyramid input; register staging only: stages 3 = two register sets (every tile), */
-                             /* any other value the double buffer.                                                                     */
+                             /* accumulation (relative error per product typically ~2^-17 / ~2^-23, at most 3 * 2^-16 / 5 * 2^-24: the */
+                             /* dropped cross terms and the residual after two / three bf16 roundings of 2^-8 each; tensors in HBM     */
+                             /* stay fp32).  Needs Cin % 32 == 0, kwaves == 0, no pyramid input; register staging only: stages 3 = two */
+                             /* register sets (every tile), any other value the double buffer.                                         */
     int32_t bnb_relu;        /* Train-mode BatchNorm BACKWARD statistics, fused.  A data-gradient launch (transposed = 1) writes the   */
     const float* bnb_y;      /* gradient dout[M][Cout] of the PREVIOUS layer's BN output; with bnb_y != NULL its epilogue also adds    */
     const float* bnb_out;    /* that BN's two backward sums to bn_sum / bn_sumsq (zeroed by the caller): bn_sum[c] += sum_m dz,        */

@@ -503,6 +503,33 @@ def _grad_sample(g):
     return f[:: max(1, f.numel() // 64)][:64]
 
 
+_wc256 = {}
+
+
+def _well_conditioned_256(golden_dir):
+    """Set-up of the 256 px well-conditioned step, shared by the tests that run it (the two CPU oracle passes are computed once per
+    process and left unchanged): (golden, cfg, initial state, image, boxes, masks, fp32 and fp64 oracle losses and gradients)."""
+    if not _wc256:
+        g = np.load(os.path.join(golden_dir, 'train_res50_coco_256_b4.npz'))
+        seed, size, batch = int(g['seed']), 256, 4
+        cfg = build_cfg('res50_coco', 'train', size)
+        torch.manual_seed(seed)
+        net = Yolact(cfg).train()
+        sd = net.state_dict()
+        R.damp_residual_branches_(sd, seed + 400)
+        net.load_state_dict(sd)
+        sd0 = {k: v.clone() for k, v in net.state_dict().items()}
+        img = torch.randn(batch, 3, size, size, generator=torch.Generator().manual_seed(seed + 300))
+        boxes, masks = R.synth_targets(batch, size, seed=seed)
+        l32, g32, _ = _oracle_grads(net, sd0, img, boxes, masks, torch.float32)
+        l64, g64, _ = _oracle_grads(net, sd0, img, boxes, masks, torch.float64)
+        _wc256['v'] = (g, cfg, sd0, img, boxes, masks, l32, g32, l64, g64)
+    g, cfg, sd0, img, boxes, masks, l32, g32, l64, g64 = _wc256['v']
+    net = Yolact(cfg).train()
+    net.load_state_dict({k: v.clone() for k, v in sd0.items()})
+    return g, net, img, boxes, masks, l32, g32, l64, g64
+
+
 def test_train_step_256_well_conditioned_golden(golden_dir):
     """The tight end-to-end gradient check: res50_coco, 256 px, batch 4 (layer4's BatchNorms see 256 samples), residual
     branches damped (`R.damp_residual_branches_`) so that backward is as well conditioned as a random-init net gets.
@@ -515,19 +542,7 @@ def test_train_step_256_well_conditioned_golden(golden_dir):
     DISTRIBUTION of the per-tensor errors is held to the fp32 CPU reference's (median x1.5, p90 x2, max x2), every tensor after
     the backbone to 3x the reference's own distance from fp64 (the larger of the frozen build-container run and the oracle run
     live on this host; floor 1e-4 of max|g|), and the losses to 1e-5."""
-    g = np.load(os.path.join(golden_dir, 'train_res50_coco_256_b4.npz'))
-    seed, size, batch = int(g['seed']), 256, 4
-    cfg = build_cfg('res50_coco', 'train', size)
-    torch.manual_seed(seed)
-    net = Yolact(cfg).train()
-    sd = net.state_dict()
-    R.damp_residual_branches_(sd, seed + 400)
-    net.load_state_dict(sd)
-    sd0 = {k: v.clone() for k, v in net.state_dict().items()}
-    img = torch.randn(batch, 3, size, size, generator=torch.Generator().manual_seed(seed + 300))
-    boxes, masks = R.synth_targets(batch, size, seed=seed)
-    l32, g32, _ = _oracle_grads(net, sd0, img, boxes, masks, torch.float32)
-    l64, g64, _ = _oracle_grads(net, sd0, img, boxes, masks, torch.float64)
+    g, net, img, boxes, masks, l32, g32, l64, g64 = _well_conditioned_256(golden_dir)
     net = net.to(DEV)
     losses = net(img.to(DEV), [b.to(DEV) for b in boxes], [m.to(DEV) for m in masks])
     sum(losses).backward()
@@ -561,6 +576,45 @@ def test_train_step_256_well_conditioned_golden(golden_dir):
     assert worst[0] <= 1.0, sorted(tail, reverse=True)[:5]
     np.testing.assert_allclose(net.backbone.bn1.running_mean.cpu().numpy(), g['run_mean_stem'], rtol=1e-5, atol=1e-7)
     np.testing.assert_allclose(net.backbone.bn1.running_var.cpu().numpy(), g['run_var_stem'], rtol=1e-5, atol=1e-7)
+
+
+def test_train_step_256_well_conditioned_under_split_bf16(golden_dir, monkeypatch):
+    """The same step with YM_TRAIN_MMA=3 (forward and data-gradient convs on the bf16 matrix pipe, split-bf16 products): a check of
+    the plumbing -- the per-launch arithmetic is held tight by tests/test_gpu_split_bf16.py and test_gpu_train_fullsize.py.  Bars:
+    2^8 x the f32 test's (the ratio of the two product roundings, 2^-16 / 2^-24: an upper bound, loose on purpose): losses within
+    2.56e-3 of the fp64 oracle's, every tensor after the backbone within 2^8 x max(3 e_cpu, 1e-4) of max|g|.
+    Measured on MI355X: losses 1.4e-6 of the oracle's at worst (0.001 of the bar); the worst tensor after the backbone
+    (proto_net.proto1.0.weight) 7.7e-3 of max|g| = 0.13 of its bar = 33x the f32 test's bar for it."""
+    from yolact_minimal_amd import train_engine as T
+    monkeypatch.setenv('YM_TRAIN_MMA', '3')
+    g, net, img, boxes, masks, l32, g32, l64, g64 = _well_conditioned_256(golden_dir)
+    net = net.to(DEV)
+    losses = net(img.to(DEV), [b.to(DEV) for b in boxes], [m.to(DEV) for m in masks])
+    sum(losses).backward()
+    torch.cuda.synchronize()
+    got = np.array([float(l.detach()) for l in losses])
+    loss_err = np.abs(got / np.array(l64) - 1).max()
+    rows = []
+    for i, (k, p) in enumerate(net.named_parameters()):
+        e_gpu = _rel_err(p.grad.detach().cpu().double(), g64[k])
+        e_cpu = max(_rel_err(g32[k], g64[k]), float(g['grad_err_vs_fp64'][i]))
+        rows.append((e_gpu / (256.0 * max(3.0 * e_cpu, 1e-4)), k, e_gpu, e_cpu))
+    e_gpu = np.array([r[2] for r in rows])
+    tail = [r for r in rows if not r[1].startswith('backbone.')]
+    worst = max(tail)
+    print(f'256 px bs=4, YM_TRAIN_MMA=3: losses {loss_err:.2e} of the fp64 oracle\'s ({loss_err / 2.56e-3:.3f} of the bar); gradient error vs '
+          f'fp64 / max|g|: median {np.median(e_gpu):.2e} p90 {np.quantile(e_gpu, 0.9):.2e} max {e_gpu.max():.2e}; after the backbone the '
+          f'worst tensor {worst[1]} at {worst[2]:.2e} = {worst[0]:.3f} of its bar ({worst[2] / max(3.0 * worst[3], 1e-4):.2f} of the f32 bar)')
+    np.testing.assert_allclose(got, np.array(l64), rtol=256 * 1e-5)
+    assert worst[0] <= 1.0, sorted(tail, reverse=True)[:5]
+    # the mode under test did run: descriptors of this mode (the cache key carries it), split-bf16 where eligible and nowhere else
+    fwd = [v[0] for k, v in T._desc_cache.items() if k[0] == 'f' and k[-2] == 3]
+    dgrad = [v[0] for k, v in T._desc_cache.items() if k[0] == 'd' and k[14] == 3]
+    assert any(d.mma == 3 for d in fwd) and any(d.mma == 3 and d.transposed for d in dgrad)
+    stem = [d for d in fwd if d.Cin == 4]
+    assert stem and all(d.mma == 0 for d in stem)
+    assert all(d.mma == 0 for d in fwd + dgrad if d.nlevels > 0 or d.Cin % 32 != 0)
+    assert all(d.mma in (0, 3) for d in fwd + dgrad)
 
 
 @pytest.mark.parametrize('cfg_name', ['res101_coco', 'res50_coco'])

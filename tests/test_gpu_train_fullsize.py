@@ -46,11 +46,19 @@ def _shards(items, n=4):
     return [items[i::n] for i in range(n)]
 
 
-@pytest.mark.parametrize('shard', range(4))
-def test_every_tuned_data_gradient_launch_at_full_size(shard):
+# (the f32 cases keep the ids they had before the split-bf16 ones joined them)
+@pytest.mark.parametrize('shard,train_mma', [(s, m) for m in (0, 3) for s in range(4)],
+                         ids=[str(s) if m == 0 else f'{s}-mma{m}' for m in (0, 3) for s in range(4)])
+def test_every_tuned_data_gradient_launch_at_full_size(shard, train_mma, monkeypatch):
     """`T_M{b h w}_N{cin}_C{cout_pad}_k_s` = dx [b,h,w,cin] from dz [b,ho,wo,cout_pad]: 2048 sampled outputs vs fp64, and the two
-    BatchNorm-backward column sums of the epilogue (sum dz, sum dz * xhat under the ReLU mask) vs fp64 over the WHOLE dx."""
+    BatchNorm-backward column sums of the epilogue (sum dz, sum dz * xhat under the ReLU mask) vs fp64 over the WHOLE dx.
+
+    `train_mma` 3: the same launches as YM_TRAIN_MMA=3 plans them (conv_launch.train_overrides: the `_mma3` row's tile and split
+    where there is one, split-bf16 products on every launch whose dz channels are a multiple of 32 and that is no wave-kernel row),
+    held to the same bar and the same sums check, every key: the four shards together take under 0.3 s on one MI355X, far from the
+    10 s above which only every fourth key would run (the whole file: 4.0 s, 3.7 s before).  Measured: worst 6.8e-6 of max|ref|."""
     from yolact_minimal_amd import train_engine as T
+    monkeypatch.setenv('YM_TRAIN_MMA', str(train_mma))       # (part of the descriptor cache's key)
     keys = _shards(_keys('T'))[shard]
     assert keys
     g = torch.Generator(device=DEV).manual_seed(100 + shard)
@@ -74,6 +82,10 @@ def test_every_tuned_data_gradient_launch_at_full_size(shard):
         link.gamma, link.beta, link.relu, link.c, link.m = gamma.data_ptr(), beta.data_ptr(), 1, cin, b * h * h
         T._stats_pool.begin(torch.device(DEV))
         dx = T._conv_dgrad(dz, w, cout_pad, (b, h, h, cin), stride, pad, bn_bwd=link)
+        cached = [v[0] for ck, v in T._desc_cache.items()
+                  if ck[0] == 'd' and ck[2:] == (b, ho, ho, cout_pad, cin, k, k, stride, pad, h, h, False, train_mma, True, bool(T._DETERMINISTIC))]
+        assert len(cached) == 1, key
+        assert cached[0].mma == (train_mma if cached[0].Cin % 32 == 0 and cached[0].kwaves == 0 else 0), (key, cached[0].mma)
         # ---- sampled fp64 reference of dx ----
         n = 2048
         sb = torch.randint(0, b, (n,), device=DEV, generator=g)
@@ -108,7 +120,7 @@ def test_every_tuned_data_gradient_launch_at_full_size(shard):
             e1 = float((stats[cin:2 * cin] - s1).abs().max() / s1.abs().max())
             assert e0 <= 1e-4 and e1 <= 1e-4, (key, e0, e1)
         del dz, w, y, dx
-    print(f'data gradients, shard {shard}: {len(keys)} launches, worst sampled error {worst:.2e} of max|ref|')
+    print(f'data gradients (YM_TRAIN_MMA={train_mma}), shard {shard}: {len(keys)} launches, worst sampled error {worst:.2e} of max|ref|')
 
 
 @pytest.mark.parametrize('shard', range(4))

@@ -97,8 +97,8 @@ def train_plan(table, key, shape, stats=False, tuning=False):
 def train_overrides(plan, table, key, mma, eligible):
     """(plan, mma) after YM_FORCE_STAGES / YM_FORCE_GRID (experiments / tests: e.g. 43 = every conv the persistent kernel covers
     runs on it) and the opt-in fast mode `mma` (YM_TRAIN_MMA=3): forward and data-gradient convs on the bf16 MFMA (split-bf16
-    products, ym_conv_desc.mma) where `eligible` (Cin % 32 == 0, no pyramid).  NOT the parity mode: per-product error ~2^-17 instead
-    of 2^-24, which the ill-conditioned backward of a random-init net amplifies beyond the fp32 reference's own noise."""
+    products, ym_conv_desc.mma) where `eligible` (Cin % 32 == 0, no pyramid).  NOT the parity mode: per-product error ~2^-17 (at most
+    3 * 2^-16) instead of 2^-24, which the ill-conditioned backward of a random-init net amplifies beyond the fp32 reference's own noise."""
     force = os.environ.get('YM_FORCE_STAGES')
     if force:
         plan = plan._replace(tile_m=64, tile_n=64, kwaves=0, stages=int(force), grid_wgs=int(os.environ.get('YM_FORCE_GRID', '0')))
