@@ -535,6 +535,29 @@ int ym_detect_greedy_nms(const float* class_pred, const float* box_pred, const f
                          float* out_scores, float* out_boxes, float* out_coefs, void* workspace,
                          size_t workspace_bytes, ym_stream_t s);
 
+/* The greedy path for a batch of B images in ONE launch set (grid row = image), with the argument order, layouts and checks of
+ * ym_detect_fast_nms_batch: 1 <= B <= 65535, YM_ENOSPC before any launch when the workspace is too small, out_count int32[B],
+ * outputs padded to max_det rows per image (rows past an image's count are unspecified; an image without an anchor over the
+ * score threshold gets out_count 0 and nothing else of it is written).
+ *   Per class: candidates = kept anchors with score > score_thre; order = score descending, equal scores by HIGHER candidate
+ *   index first (oracle/greedy_nms.c); a candidate is dropped iff an earlier KEPT candidate of its class has ovr >= iou_thre on
+ *   the boxes multiplied by img_size ("+ 1" widths, heights and areas, IEEE division).  The kernel settles 64 sorted candidates
+ *   at a time inside one wave and then tests all later ones against that chunk's survivors: two workgroup barriers per 64
+ *   candidates, the sequential result exactly.  The order is a counting rank, O(n^2) per class of n candidates.
+ *   Per image: the max_det highest scores over all kept (class, candidate) pairs, equal scores in class-major, ascending anchor
+ *   order; boxes = (b * img_size) / img_size; coefficients gathered from coef_pred.
+ * B = 1 gives the values of ym_detect_greedy_nms bit for bit.
+ * Workspace per image (every term rounded up to 256 bytes), with S = ym_nms_batch_workspace_bytes(cfg, 1), n = (C-1) * N:
+ *   S + 4 n (candidate lists) + 4 (C-1) (their lengths) + n (kept flags)          when N <= 4096
+ *   ... + 4 n (candidate by rank)                                                 when N >  4096
+ * A class of up to 4096 candidates keeps its sorted boxes, scores, order and alive flags in LDS (25 bytes per candidate); a larger
+ * one reads its boxes through the order in global memory.  N = 18525, C = 81: 19.8 MB against the 45.0 MB of
+ * ym_nms_workspace_bytes.  ym_greedy_nms_batch_workspace_bytes is host only, linear in B, 0 on a bad cfg or B < 1. */
+size_t ym_greedy_nms_batch_workspace_bytes(const ym_nms_cfg* cfg, int B);
+int ym_detect_greedy_nms_batch(const float* class_pred, const float* box_pred, const float* coef_pred, const float* anchors,
+                               const ym_nms_cfg* cfg, int B, int32_t* out_count, int64_t* out_ids, float* out_scores,
+                               float* out_boxes, float* out_coefs, void* workspace, size_t workspace_bytes, ym_stream_t s);
+
 /* y[i] = exp(x[i]) rounded to nearest float — the exp of the box decode (utils/output_utils.py:150, `torch.exp`), exposed so
  * that the parity suite can compare it with oracle/expf_cr.c on arbitrary inputs (bit-identical by construction: same IEEE
  * double operation sequence).  The reference's own torch.exp is MKL VML (1 ulp off this value in 1.1 % of inputs). */

@@ -877,6 +877,263 @@ __global__ __launch_bounds__(NT) void k_greedy_final(const NmsWs w, const Greedy
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// batched greedy NMS (ym_detect_greedy_nms_batch): grid row = image, suppression in chunks of 64 sorted candidates
+// ---------------------------------------------------------------------------------------------------
+// The sequential definition (a candidate is dropped iff an earlier KEPT candidate overlaps it) needs one step per candidate only
+// INSIDE a window where keeps are still undecided.  So: one wave settles 64 consecutive sorted candidates among themselves (the
+// alive bits are a ballot, the current box a readlane: no barrier), then the whole workgroup tests every later candidate against
+// that chunk's survivors.  Two workgroup barriers per 64 candidates instead of 64; the kept set is the sequential one exactly.
+struct GreedyBatchWs {
+    int* cand;          // [C-1][N] compacted-list indices of the class candidates (ascending)
+    int* cand_cnt;      // [C-1]
+    uint8_t* kept;      // [C-1][N] kept flag by candidate position (ascending index order)
+    int* sorted_id;     // [C-1][N] candidate position by rank; only carved when N > greedy_lds_cap(N), else null
+};
+constexpr int GREEDY_CHUNK = 64;        // = one wave
+constexpr int GREEDY_LDS_CAP = 4096;    // candidates of one class whose sorted boxes are staged in LDS (25 bytes each: ~100 KB)
+constexpr int GREEDY_LDS_HEAD = 256;    // bytes in front of the staged arrays: the workgroup's counters
+
+inline int greedy_lds_cap(int N) { return ((N < GREEDY_LDS_CAP ? N : GREEDY_LDS_CAP) + 63) & ~63; }
+inline size_t greedy_lds_bytes(int N) { return (size_t)GREEDY_LDS_HEAD + (size_t)greedy_lds_cap(N) * 25; }
+
+size_t carve_greedy_batch(void* base, int N, int C, GreedyBatchWs* g) {
+    size_t off = 0;
+    const size_t cn = (size_t)(C - 1) * N;
+    auto take = [&](size_t bytes) { char* p = (char*)base + off; off += align_up(bytes); return (void*)p; };
+    GreedyBatchWs t;
+    t.cand = (int*)take(cn * 4);
+    t.cand_cnt = (int*)take((size_t)(C - 1) * 4);
+    t.kept = (uint8_t*)take(cn);
+    t.sorted_id = N > greedy_lds_cap(N) ? (int*)take(cn * 4) : nullptr;
+    if (g) *g = t;
+    return off;
+}
+
+__device__ __forceinline__ GreedyBatchWs image_gws(const GreedyBatchWs& g, size_t stride, int b) {
+    GreedyBatchWs o = g;
+    const size_t sh = stride * (size_t)b;
+    o.cand = (int*)((char*)g.cand + sh);
+    o.cand_cnt = (int*)((char*)g.cand_cnt + sh);
+    o.kept = g.kept + sh;
+    if (g.sorted_id) o.sorted_id = (int*)((char*)g.sorted_id + sh);
+    return o;
+}
+
+// block_greedy_nms's overlap test, operation for operation (bi = the earlier, kept box; iarea its "+1" area)
+__device__ __forceinline__ bool greedy_overlaps(const f32x4 bi, float iarea, const f32x4 bj, float thresh) {
+    const float xx1 = fmaxf(bi[0], bj[0]), yy1 = fmaxf(bi[1], bj[1]);
+    const float xx2 = fminf(bi[2], bj[2]), yy2 = fminf(bi[3], bj[3]);
+    float ww = xx2 - xx1 + 1.f, hh = yy2 - yy1 + 1.f;
+    ww = ww >= 0.f ? ww : 0.f;
+    hh = hh >= 0.f ? hh : 0.f;
+    const float inter = ww * hh;
+    const float jarea = (bj[2] - bj[0] + 1.f) * (bj[3] - bj[1] + 1.f);
+    const float ovr = __fdiv_rn(inter, (iarea + jarea) - inter);
+    return ovr >= thresh;
+}
+
+// rank of candidate i of n in (score descending, higher index first); scores readable 4 at a time, padded with -inf to n4
+__device__ __forceinline__ int greedy_rank_lds(const float* s_score, int n4, float s, int i) {
+    int rank = 0;
+    for (int j = 0; j < n4; j += 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(s_score + j);      // (same address in every lane: a broadcast read)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rank += greedy_before(q[e], j + e, s, i) ? 1 : 0;
+    }
+    return rank;
+}
+
+// The chunked suppression over sorted ranks 0..n-1.  box_at(r): the scaled box of rank r; alive_at(r) / kill(r): its flag, visible
+// to the workgroup after a barrier.  s_surv: one 64-bit word in LDS.
+template <typename BoxAt, typename AliveAt, typename Kill>
+__device__ __forceinline__ void greedy_suppress_chunks(BoxAt box_at, AliveAt alive_at, Kill kill, int n, float thresh,
+                                                       unsigned long long* s_surv) {
+    const int tid = threadIdx.x;
+    for (int base = 0; base < n; base += GREEDY_CHUNK) {
+        if (tid < GREEDY_CHUNK) {                                      // wave 0, all 64 lanes
+            const int r = base + tid, m = min(GREEDY_CHUNK, n - base);
+            const bool valid = tid < m;
+            const f32x4 bj = box_at(valid ? r : base);
+            bool alive = valid && alive_at(valid ? r : base);
+            for (int i = 0; i + 1 < m; ++i) {
+                const unsigned long long bal = __ballot(alive);
+                if (!((bal >> i) & 1ull)) continue;                    // wave-uniform: a suppressed candidate suppresses nobody
+                f32x4 bi;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bi[e] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bj[e]), i));
+                const float iarea = (bi[2] - bi[0] + 1.f) * (bi[3] - bi[1] + 1.f);
+                if (alive && tid > i && greedy_overlaps(bi, iarea, bj, thresh)) alive = false;
+            }
+            const unsigned long long surv = __ballot(alive);
+            if (valid && !alive) kill(r);
+            if (tid == 0) *s_surv = surv;
+        }
+        __syncthreads();
+        const unsigned long long surv = *s_surv;
+        for (int b = base + GREEDY_CHUNK + tid; b < n; b += NT) {
+            if (!alive_at(b)) continue;
+            const f32x4 bj = box_at(b);
+            for (unsigned long long left = surv; left; left &= left - 1ull) {
+                const f32x4 bi = box_at(base + __ffsll((long long)left) - 1);
+                const float iarea = (bi[2] - bi[0] + 1.f) * (bi[3] - bi[1] + 1.f);
+                if (greedy_overlaps(bi, iarea, bj, thresh)) { kill(b); break; }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// grid (C-1, B).  lds_cap = greedy_lds_cap(N) candidates fit the staged form; dynamic LDS = greedy_lds_bytes(N).
+__global__ __launch_bounds__(NT) void k_greedy_per_class_batch(const NmsWs w0, const GreedyBatchWs g0, int N, float score_thre,
+                                                                float iou_thre, float img_size, size_t ws_stride, int lds_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char greedy_lds[];
+    const NmsWs w = image_ws(w0, ws_stride, blockIdx.y);
+    const GreedyBatchWs g = image_gws(g0, ws_stride, blockIdx.y);
+    int* wave_tot = reinterpret_cast<int*>(greedy_lds);                               // [NT / 64]
+    int* running = wave_tot + NT / 64;
+    unsigned long long* s_surv = reinterpret_cast<unsigned long long*>(greedy_lds + 128);
+    unsigned char* body = greedy_lds + GREEDY_LDS_HEAD;
+    const int K = w.counters[0];
+    if (K == 0) return;
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* srow = w.scores_t + (size_t)c * N;
+    int* cand = g.cand + (size_t)c * N;
+    if (tid == 0) *running = 0;
+    __syncthreads();
+    for (int base = 0; base < K; base += NT) {
+        const int i = base + tid;
+        const bool f = i < K && srow[i] > score_thre;
+        const unsigned long long bal = __ballot(f);
+        const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_tot[wv] = __popcll(bal);
+        __syncthreads();
+        int off = *running;
+        for (int x = 0; x < wv; ++x) off += wave_tot[x];
+        if (f) cand[off + pre] = i;
+        __syncthreads();
+        if (tid == 0) { int t = 0; for (int x = 0; x < NT / 64; ++x) t += wave_tot[x]; *running += t; }
+        __syncthreads();
+    }
+    const int n = *running;
+    if (tid == 0) g.cand_cnt[c] = n;
+    if (n == 0) return;
+    const int n4 = (n + 3) & ~3;
+    uint8_t* kept = g.kept + (size_t)c * N;
+    auto scaled_box = [&](int i) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(w.boxes_k + (size_t)cand[i] * 4);
+        return f32x4{b[0] * img_size, b[1] * img_size, b[2] * img_size, b[3] * img_size};
+    };
+    if (n <= lds_cap) {
+        // everything staged: sorted boxes, scores, candidate position by rank, alive flags
+        f32x4* s_box = reinterpret_cast<f32x4*>(body);
+        float* s_score = reinterpret_cast<float*>(body + (size_t)lds_cap * 16);
+        int* s_id = reinterpret_cast<int*>(body + (size_t)lds_cap * 20);
+        uint8_t* s_alive = body + (size_t)lds_cap * 24;
+        for (int i = tid; i < n4; i += NT) s_score[i] = i < n ? srow[cand[i]] : -INFINITY;
+        __syncthreads();
+        for (int i = tid; i < n; i += NT) {
+            const int rank = greedy_rank_lds(s_score, n4, s_score[i], i);
+            s_box[rank] = scaled_box(i);
+            s_id[rank] = i;
+            s_alive[rank] = 1;
+        }
+        __syncthreads();
+        greedy_suppress_chunks([&](int r) { return s_box[r]; }, [&](int r) { return s_alive[r] != 0; }, [&](int r) { s_alive[r] = 0; },
+                               n, iou_thre, s_surv);
+        for (int r = tid; r < n; r += NT) kept[s_id[r]] = s_alive[r];
+        return;
+    }
+    // more candidates than the staged form holds (few-class heads reach n ~ N): the order lives in global memory, the boxes are read
+    // through it, and `kept` itself is the alive flag.  The scores still come from LDS while 4 n bytes fit the same allocation.
+    int* sid = g.sorted_id + (size_t)c * N;
+    const int score_cap = lds_cap * 25 / 4;
+    if (n4 <= score_cap) {
+        float* s_score = reinterpret_cast<float*>(body);
+        for (int i = tid; i < n4; i += NT) s_score[i] = i < n ? srow[cand[i]] : -INFINITY;
+        __syncthreads();
+        for (int i = tid; i < n; i += NT) {
+            sid[greedy_rank_lds(s_score, n4, s_score[i], i)] = i;
+            kept[i] = 1;
+        }
+    } else {
+        for (int i = tid; i < n; i += NT) {
+            const float s = srow[cand[i]];
+            int rank = 0;
+            for (int j = 0; j < n; ++j) rank += greedy_before(srow[cand[j]], j, s, i) ? 1 : 0;
+            sid[rank] = i;
+            kept[i] = 1;
+        }
+    }
+    __syncthreads();
+    greedy_suppress_chunks([&](int r) { return scaled_box(sid[r]); }, [&](int r) { return kept[sid[r]] != 0; }, [&](int r) { kept[sid[r]] = 0; },
+                           n, iou_thre, s_surv);
+}
+
+// grid (1, B): global top max_det over the kept (class, candidate) pairs of one image, k_greedy_final's order (score descending,
+// ties in flat class-major, ascending-index order).  The flat list is the classes' candidate lists back to back (their counts'
+// prefix sums in LDS), not (C-1) x N slots: the select reads what exists.
+__global__ __launch_bounds__(NT) void k_greedy_final_batch(const NmsWs w0, const GreedyBatchWs g0, int N, int ncls, int max_det,
+                                                           float img_size, const FinalOut o0, size_t ws_stride) {
+    const NmsWs w = image_ws(w0, ws_stride, blockIdx.y);
+    const GreedyBatchWs g = image_gws(g0, ws_stride, blockIdx.y);
+    const FinalOut o = image_out(o0, blockIdx.y, max_det, N);
+    __shared__ TopkShared<DET_CAP> sh;
+    __shared__ int s_pre[257];          // s_pre[c] = candidates of the classes before c; s_pre[256] = all
+    __shared__ int wtot[4];
+    __shared__ int n_valid;
+    __shared__ int s_anchor[DET_CAP];   // anchor of output row j: the coefficient gather looks nothing up again
+    const int tid = threadIdx.x;
+    if (w.counters[0] == 0) {
+        if (tid == 0) o.out_count[0] = 0;
+        return;
+    }
+    const int mine = tid < ncls ? g.cand_cnt[tid] : 0;
+    const int excl = block256_excl_scan(mine, wtot);
+    if (tid < 256) s_pre[tid] = excl;
+    if (tid == 255) s_pre[256] = excl + mine;
+    if (tid == 0) n_valid = 0;
+    __syncthreads();
+    const int L = s_pre[256];
+    auto class_of = [&](int f) {            // the class whose list holds flat entry f < L (empty classes share their successor's start)
+        int lo = 0, hi = ncls;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_pre[mid] <= f) lo = mid; else hi = mid;
+        }
+        return lo;
+    };
+    auto key_at = [&](int f) -> uint32_t {
+        const int c = class_of(f);
+        const size_t e = (size_t)c * N + (f - s_pre[c]);
+        return g.kept[e] ? f2key(w.scores_t[(size_t)c * N + g.cand[e]]) : 0u;
+    };
+    block_topk_sorted<DET_CAP>(key_at, L, max_det, sh);
+    if (tid < max_det && sh.keys[tid] != 0u) atomicAdd(&n_valid, 1);
+    __syncthreads();
+    const int n = n_valid;
+    if (tid == 0) o.out_count[0] = n;
+    for (int j = tid; j < n; j += NT) {
+        const int f = sh.idx[j];
+        const int c = class_of(f);
+        const int k = g.cand[(size_t)c * N + (f - s_pre[c])];
+        s_anchor[j] = w.keep_idx[k];
+        o.out_ids[j] = c;
+        o.out_scores[j] = key2f(sh.keys[j]);
+        // boxes[idx] / img_size of boxes * img_size (utils/output_utils.py:90,123)
+        const f32x4 b = *reinterpret_cast<const f32x4*>(w.boxes_k + (size_t)k * 4);
+        f32x4 ob;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ob[e] = __fdiv_rn(b[e] * img_size, img_size);
+        *reinterpret_cast<f32x4*>(o.out_boxes + j * 4) = ob;
+    }
+    __syncthreads();
+    for (int e = tid; e < n * o.coef_dim; e += NT) {
+        const int j = e / o.coef_dim, d = e - j * o.coef_dim;
+        o.out_coefs[e] = o.coef[(size_t)s_anchor[j] * o.coef_dim + d];
+    }
+}
+
 size_t greedy_extra_bytes(int N, int C) {
     const size_t cn = (size_t)(C - 1) * N;
     return align_up(cn * 4) + align_up((size_t)(C - 1) * 4) + align_up(cn * 16) + align_up(cn * 4) + align_up(cn) + align_up(cn);
@@ -992,6 +1249,48 @@ extern "C" int ym_detect_greedy_nms(const float* class_pred, const float* box_pr
     hipLaunchKernelGGL(k_greedy_final, dim3(1), dim3(NT), 0, st, w, g, N, C - 1, cfg->max_det, cfg->img_size, coef_pred,
                        cfg->coef_dim, out_count, out_ids, out_scores, out_boxes, out_coefs);
     return ym_check_launch("greedy_nms");
+}
+
+// per image: the stage-A workspace, then cand / cand_cnt / kept (+ sorted_id when a class can outgrow the staged form)
+static size_t greedy_batch_stride(int N, int C) {
+    return align_up(carve(nullptr, N, C).bytes) + carve_greedy_batch(nullptr, N, C, nullptr);
+}
+
+extern "C" size_t ym_greedy_nms_batch_workspace_bytes(const ym_nms_cfg* cfg, int B) {
+    if (check_cfg(cfg) != YM_OK || B < 1) return 0;
+    return greedy_batch_stride(cfg->num_anchors, cfg->num_classes) * (size_t)B;
+}
+
+extern "C" int ym_detect_greedy_nms_batch(const float* class_pred, const float* box_pred, const float* coef_pred,
+                                          const float* anchors, const ym_nms_cfg* cfg, int B, int32_t* out_count, int64_t* out_ids,
+                                          float* out_scores, float* out_boxes, float* out_coefs, void* workspace,
+                                          size_t workspace_bytes, ym_stream_t s) {
+    int rc = check_cfg(cfg);
+    if (rc != YM_OK) return rc;
+    YM_REQUIRE(B >= 1 && B <= 65535, "greedy_nms_batch: batch must be 1..65535");
+    YM_REQUIRE(class_pred && box_pred && coef_pred && anchors && out_count && out_ids && out_scores && out_boxes &&
+                   out_coefs && workspace, "greedy_nms_batch: null pointer");
+    const int N = cfg->num_anchors, C = cfg->num_classes;
+    const size_t stride = greedy_batch_stride(N, C);
+    if (stride * (size_t)B > workspace_bytes) {
+        ym_set_error("greedy_nms_batch: workspace %zu < %zu", workspace_bytes, stride * (size_t)B);
+        return YM_ENOSPC;
+    }
+    const size_t lds = greedy_lds_bytes(N);
+    static YmLdsAttr lds_set = {};
+    if ((rc = ym_ensure_dyn_lds(lds_set, reinterpret_cast<const void*>(k_greedy_per_class_batch), lds, "greedy_per_class_batch")) != YM_OK)
+        return rc;
+    NmsWs w = carve(workspace, N, C);
+    GreedyBatchWs g;
+    carve_greedy_batch((char*)workspace + align_up(w.bytes), N, C, &g);
+    hipStream_t st = (hipStream_t)s;
+    rc = run_stage_a(class_pred, box_pred, anchors, cfg, w, st, B, stride);
+    if (rc != YM_OK) return rc;
+    hipLaunchKernelGGL(k_greedy_per_class_batch, dim3(C - 1, B), dim3(NT), lds, st, w, g, N, cfg->score_thre, cfg->iou_thre,
+                       cfg->img_size, stride, greedy_lds_cap(N));
+    const FinalOut fo = {coef_pred, cfg->coef_dim, out_count, out_ids, out_scores, out_boxes, out_coefs};
+    hipLaunchKernelGGL(k_greedy_final_batch, dim3(1, B), dim3(NT), 0, st, w, g, N, C - 1, cfg->max_det, cfg->img_size, fo, stride);
+    return ym_check_launch("greedy_nms_batch");
 }
 
 extern "C" int ym_expf_cr(const float* x, float* y, int64_t n, ym_stream_t s) {

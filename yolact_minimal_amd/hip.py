@@ -26,6 +26,7 @@ ABI_SYMBOLS = (
     'ym_greedy_nms_workspace_bytes', 'ym_greedy_nms', 'ym_mask_assemble', 'ym_mask_resize_binarize',
     'ym_boxes_to_pixels', 'ym_expf_cr', 'ym_nms_batch_workspace_bytes', 'ym_detect_fast_nms_batch', 'ym_after_nms_batch_workspace_bytes',
     'ym_after_nms_batch', 'ym_head_grad_gather', 'ym_scatter3',
+    'ym_greedy_nms_batch_workspace_bytes', 'ym_detect_greedy_nms_batch',
     'ym_pack_conv_weight_dgrad', 'ym_pack_conv_weights_batch', 'ym_conv2d_wgrad_workspace_bytes', 'ym_conv2d_wgrad', 'ym_conv2d_wgrad_slabs', 'ym_wgrad_reduce_batch', 'ym_bn_train_fwd',
     'ym_val_preprocess', 'ym_layernorm', 'ym_patch_merge_layernorm', 'ym_swin_window_attention',
     'ym_mask_loss_workspace_bytes', 'ym_mask_loss_fwd_bwd', 'ym_mask_loss_batch_workspace_bytes', 'ym_mask_loss_batch',
@@ -150,6 +151,9 @@ def lib():
         L.ym_nms_batch_workspace_bytes.argtypes = [ctypes.POINTER(NmsCfg), i32]
         L.ym_nms_batch_workspace_bytes.restype = sz
         L.ym_detect_fast_nms_batch.argtypes = [vp, vp, vp, vp, ctypes.POINTER(NmsCfg), i32, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.ym_greedy_nms_batch_workspace_bytes.argtypes = L.ym_nms_batch_workspace_bytes.argtypes
+        L.ym_greedy_nms_batch_workspace_bytes.restype = sz
+        L.ym_detect_greedy_nms_batch.argtypes = L.ym_detect_fast_nms_batch.argtypes
         L.ym_after_nms_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
         L.ym_after_nms_batch_workspace_bytes.restype = sz
         L.ym_after_nms_batch.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
@@ -242,7 +246,7 @@ def lib():
                             'ym_greedy_nms_workspace_bytes', 'ym_conv2d_wgrad_workspace_bytes',
                             'ym_sizeof_conv_desc', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
                             'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes',
-                            'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes'):
+                            'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

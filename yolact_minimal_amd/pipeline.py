@@ -8,7 +8,7 @@ flight: `RequestPipeline` owns `depth` complete engines (activations, split-K sc
 but the read-only weights) and `depth` HIP streams, and runs request i on slot i % depth.  Each request is still ONE image through
 `Yolact.forward` -> `nms` -> `after_nms` with ONE host read (its detection count, which `after_nms` needs to size what it returns);
 the count is copied to pinned host memory behind the request and read when the slot comes up again, so the host never waits on
-the request it has just enqueued.
+the request it has just enqueued.  `cfg.traditional_nms` is served the same way (`nms_batch` picks the batched greedy entry).
 
 Measured mid-round 3 (res101_coco 544 px, MI355X, forward + nms + after_nms(480x640)): depth 1: 325 img/s, 2: 468, 3: 545, 4: 594, 5: 495,
 8: 479; with round 4's kernels 3: 580, 4: 603-617, 5: 499, 6: 527 -- the part schedules four compute pipes; GPU_MAX_HW_QUEUES must be >= depth + 1 (ROCm multiplexes HIP streams onto 4

@@ -183,12 +183,11 @@ class BatchDetections:
 
 
 def nms_batch(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
-    """`nms` (fast_nms) for a whole batch [B, N, *] in one launch set, no host synchronisation.  Per image the result equals
-    `nms(class_pred[b:b+1], ...)` (tests/test_gpu_postproc.py::test_batched_postprocessing_equals_per_image)."""
+    """`nms` for a whole batch [B, N, *] in one launch set, no host synchronisation: fast_nms, or with `cfg.traditional_nms` the
+    greedy per-class path (`ym_detect_greedy_nms_batch`).  Per image the result equals `nms(class_pred[b:b+1], ...)`
+    (tests/test_gpu_postproc.py::test_batched_postprocessing_equals_per_image, tests/test_gpu_greedy_batch.py)."""
     if not class_pred.is_cuda:
         raise RuntimeError('yolact_minimal_amd.utils.output_utils.nms_batch needs CUDA (HIP) tensors; there is no CPU path.')
-    if getattr(cfg, 'traditional_nms', False):
-        raise NotImplementedError('nms_batch implements fast_nms; use nms() per image for --traditional_nms')
     if class_pred.dim() != 3:
         raise RuntimeError('nms_batch expects [B, N, C] predictions')
     device = class_pred.device
@@ -198,18 +197,22 @@ def nms_batch(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
         raise RuntimeError(f'{anchors_t.shape[0]} anchors for {n_anchors} predictions')
     # everything that depends only on the shapes and the thresholds is built once: an eager call spends its time between the
     # caller's line and the first launch HERE (~20 us of Python against ~68 us of device time: bench.post_bench's two columns)
+    greedy = bool(getattr(cfg, 'traditional_nms', False))
     pkey = (device.index, batch, n_anchors, n_classes, coef_pred.shape[2], cfg.top_k, cfg.max_detections, cfg.nms_score_thre,
-            cfg.nms_iou_thre, getattr(cfg, 'img_size', 544))
+            cfg.nms_iou_thre, getattr(cfg, 'img_size', 544), greedy)
     plan = _plan_cache.get(pkey)
     L = hip.lib()
     if plan is None:
         ncfg = hip.NmsCfg(n_anchors, n_classes, coef_pred.shape[2], int(cfg.top_k), int(cfg.max_detections),
                           float(cfg.nms_score_thre), float(cfg.nms_iou_thre), float(getattr(cfg, 'img_size', 544)))
-        nbytes = L.ym_nms_batch_workspace_bytes(ctypes.byref(ncfg), batch)
+        # (the two paths carve different workspaces: the entry, its name and its size travel together)
+        name = 'ym_detect_greedy_nms_batch' if greedy else 'ym_detect_fast_nms_batch'
+        ws_bytes = L.ym_greedy_nms_batch_workspace_bytes if greedy else L.ym_nms_batch_workspace_bytes
+        nbytes = ws_bytes(ctypes.byref(ncfg), batch)
         if nbytes == 0:
-            raise RuntimeError('ym_nms_batch_workspace_bytes: ' + L.ym_last_error().decode())
-        plan = _plan_cache[pkey] = (ncfg, ctypes.byref(ncfg), nbytes)
-    ncfg, ncfg_ref, nbytes = plan
+            raise RuntimeError(('ym_greedy_nms_batch_workspace_bytes: ' if greedy else 'ym_nms_batch_workspace_bytes: ') + L.ym_last_error().decode())
+        plan = _plan_cache[pkey] = (ncfg, ctypes.byref(ncfg), nbytes, getattr(L, name), name)
+    ncfg, ncfg_ref, nbytes, entry, entry_name = plan
     md = ncfg.max_det
     other_device = torch.cuda.current_device() != device.index
     if other_device:
@@ -217,7 +220,7 @@ def nms_batch(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
         torch.cuda.set_device(device)
     try:
         stream = torch.cuda.current_stream().cuda_stream
-        key = ('batch', device.index, stream, batch, n_anchors, n_classes)      # (scratch is per STREAM, like _nms_buffers)
+        key = ('batch', device.index, stream, batch, n_anchors, n_classes, greedy)      # (scratch is per STREAM, like _nms_buffers)
         ws = _ws_cache.get(key)
         if ws is None or ws.numel() < nbytes:
             ws = _ws_cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -226,10 +229,10 @@ def nms_batch(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
         scores = torch.empty(batch, md, dtype=torch.float32, device=device)
         boxes = torch.empty(batch, md, 4, dtype=torch.float32, device=device)
         coefs = torch.empty(batch, md, ncfg.coef_dim, dtype=torch.float32, device=device)
-        hip.check(L.ym_detect_fast_nms_batch(hip.ptr(class_pred.contiguous()), hip.ptr(box_pred.contiguous()), hip.ptr(coef_pred.contiguous()),
-                                             hip.ptr(anchors_t), ncfg_ref, batch, hip.ptr(counts, torch.int32),
-                                             hip.ptr(ids, torch.int64), hip.ptr(scores), hip.ptr(boxes), hip.ptr(coefs),
-                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream)), 'ym_detect_fast_nms_batch')
+        hip.check(entry(hip.ptr(class_pred.contiguous()), hip.ptr(box_pred.contiguous()), hip.ptr(coef_pred.contiguous()),
+                        hip.ptr(anchors_t), ncfg_ref, batch, hip.ptr(counts, torch.int32),
+                        hip.ptr(ids, torch.int64), hip.ptr(scores), hip.ptr(boxes), hip.ptr(coefs),
+                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream)), entry_name)
     finally:
         if other_device:
             torch.cuda.set_device(prev)
