@@ -670,6 +670,45 @@ int ym_draw_detections_batch_packed(const uint8_t* img, const uint64_t* mask_bit
                                     uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s);
 int ym_draw_cutout_objects_packed(const uint8_t* img, const uint64_t* mask_bits, int n, int H, int W, uint8_t* out, ym_stream_t s);
 
+/* ---- device-resident mAP accumulator (utils/common_utils.py:107-262, eval.py:35-69,106) ---------------------------------------
+ * The log: one row per (image slot, detection row) at position image_index * max_det + row, kept as three arrays:
+ *   log_score fp32, log_class int32 (-1 = no data point), log_flags uint32 (bit type * T + k set = prediction matched at
+ *   threshold k of IoU type `type`, 0 = box, 1 = mask; T <= YM_EVAL_MAX_THRESHOLDS),
+ * plus gt_count int64 [num_classes] (ground-truth instances per class) and class_rows int32 [num_classes] (data points per class).
+ * The caller initialises log_class to -1 and the two counters to 0; nothing here reads the host.
+ *
+ * ym_eval_match_log: prep_metrics (utils/common_utils.py:174-216) for ONE image on its padded after_nms_batch(sync=False) rows.
+ *   ids int64 [n], scores fp32 [n], count int32 on the device (NULL = all n rows valid; clamped to 0..n), n <= YM_EVAL_MAX_DET;
+ *   iou_box / iou_mask fp32 [n][g]; gt fp32 [g][5] whose column 4 is the class (float -> int by truncation); g <= 512 (g = 0 is
+ *   allowed: nothing matches); thresholds fp64 [T] on the device.
+ * The matching is ym_match_detections' (one device function): predictions in row order, rows below the count only, IoU strictly
+ * greater than the fp64 threshold, the first gt wins among equal IoUs, a gt is used once per (type, threshold).  Rows at or past
+ * the count, and rows whose class is outside 0..num_classes-1, are written with class -1, score 0 and no flags.  The image's gt
+ * instances are added to gt_count and its data points to class_rows with INTEGER atomics.  An image whose count is 0 writes no data
+ * point and adds no gt positives (eval.py:53-54 skips it before prep_metrics).  The image's rows are log_*[log_offset .. log_offset + n).
+ *
+ * ym_eval_ap: the AP of every (type, threshold, class) cell, APDataObject.get_ap operation for operation in fp64 (no contraction):
+ *   log_flags uint32 [rows]; order int64 [rows] = log positions sorted by (class ascending, score descending, position ascending),
+ *   NULL when log_flags already is in that order; seg int64 [num_classes + 1] = first sorted row of each class (rows of class -1
+ *   sort first: seg[0] is their number); gt_count int64 [num_classes].
+ *   ap fp64 [2][T][num_classes]: tp = running count of set flags, precision = tp / (rank + 1), recall = tp / num_gt, envelope =
+ *   suffix maximum of precision; for each of the 101 grid values (double)k / 100.0 the envelope at the first rank whose recall
+ *   quotient is >= the grid value (0 when it never is); the 101 samples are added left to right and divided by 101.  A cell with
+ *   num_gt == 0 or without rows is 0.  empty uint8 [num_classes] = 1 when the class has no rows and num_gt == 0.
+ * A class is walked in passes of YM_EVAL_AP_ROWS_PER_PASS rows with carried state (true positives still ahead, envelope so far), so
+ * its length is unbounded.  workspace >= ym_eval_ap_workspace_bytes(rows) (the flags in sorted order: O(rows)).  No floating-point
+ * atomics: results repeat bit for bit. */
+#define YM_EVAL_MAX_DET 1024
+#define YM_EVAL_MAX_THRESHOLDS 16
+#define YM_EVAL_AP_ROWS_PER_PASS 1024
+int ym_eval_match_log(const int64_t* ids, const float* scores, const int32_t* count, int n, const float* iou_box,
+                      const float* iou_mask, const float* gt, int g, const double* thresholds, int T, int num_classes,
+                      float* log_score, int32_t* log_class, uint32_t* log_flags, int64_t log_offset, int64_t* gt_count,
+                      int32_t* class_rows, ym_stream_t s);
+size_t ym_eval_ap_workspace_bytes(int64_t rows);
+int ym_eval_ap(const uint32_t* log_flags, const int64_t* order, int64_t rows, const int64_t* seg, const int64_t* gt_count, int T,
+               int num_classes, double* ap, uint8_t* empty, void* workspace, size_t workspace_bytes, ym_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

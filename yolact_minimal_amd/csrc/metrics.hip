@@ -202,6 +202,28 @@ __global__ void k_box_iou(const float* __restrict__ a, const float* __restrict__
 // visited in their given order; each takes the unused same-class gt with the largest IoU strictly above the running maximum
 // (which starts AT the threshold; python compares float32->double IoUs with the double threshold).
 constexpr int MAXG = 512;
+// One (IoU type, threshold, class) matching: `emit(i, hit)` for every prediction i < n of class c, in row order.  The ONE statement
+// of the rule: k_match_detections and the accumulator's k_eval_match_log both call it.
+template <class Emit>
+__device__ __forceinline__ void match_class(const float* __restrict__ iou, const int* pred_cls, const int* gt_cls, int n, int g,
+                                            double th, int c, Emit emit) {
+    unsigned used[MAXG / 32];
+#pragma unroll
+    for (int w = 0; w < MAXG / 32; ++w) used[w] = 0u;
+    for (int i = 0; i < n; ++i) {
+        if (pred_cls[i] != c) continue;
+        double best = th;
+        int bj = -1;
+        for (int j = 0; j < g; ++j) {
+            if (gt_cls[j] != c || ((used[j >> 5] >> (j & 31)) & 1u)) continue;
+            const double v = (double)iou[(size_t)i * g + j];
+            if (v > best) { best = v; bj = j; }
+        }
+        if (bj >= 0) used[bj >> 5] |= 1u << (bj & 31);
+        emit(i, bj >= 0);
+    }
+}
+
 __global__ __launch_bounds__(128) void k_match_detections(const float* __restrict__ iou_box, const float* __restrict__ iou_mask,
                                                           const int* __restrict__ pred_cls, const int* __restrict__ gt_cls, int n, int g,
                                                           const double* __restrict__ thr, int T, int num_classes,
@@ -210,22 +232,198 @@ __global__ __launch_bounds__(128) void k_match_detections(const float* __restric
     const float* iou = type == 0 ? iou_box : iou_mask;
     uint8_t* out = matched + ((size_t)type * T + k) * n;
     const double th = thr[k];
-    for (int c = threadIdx.x; c < num_classes; c += blockDim.x) {
-        unsigned used[MAXG / 32];
-#pragma unroll
-        for (int w = 0; w < MAXG / 32; ++w) used[w] = 0u;
-        for (int i = 0; i < n; ++i) {
-            if (pred_cls[i] != c) continue;
-            double best = th;
-            int bj = -1;
-            for (int j = 0; j < g; ++j) {
-                if (gt_cls[j] != c || ((used[j >> 5] >> (j & 31)) & 1u)) continue;
-                const double v = (double)iou[(size_t)i * g + j];
-                if (v > best) { best = v; bj = j; }
-            }
-            if (bj >= 0) used[bj >> 5] |= 1u << (bj & 31);
-            out[i] = bj >= 0 ? 1 : 0;
+    for (int c = threadIdx.x; c < num_classes; c += blockDim.x)
+        match_class(iou, pred_cls, gt_cls, n, g, th, c, [&](int i, bool hit) { out[i] = hit ? 1 : 0; });
+}
+
+// ---- device-resident mAP accumulator (include/yolact_hip.h "device-resident mAP accumulator") ---------------------------------
+// prep_metrics for one image on its padded rows: the classes are staged in LDS once (int64 ids / the float gt column -> int), every
+// (cell = type * T + k, class) pair is one work item of match_class, a hit sets bit `cell` of the row's flag word (LDS integer
+// atomic: the cells of a row are spread over threads), then the rows go to the log.  One workgroup of 16 waves.  The items of a
+// class are NEIGHBOURING lanes: a wave executes the gt loop of a prediction whenever one of its lanes owns that prediction's class,
+// so with 2T lanes per class a wave holds ~3 classes (T = 10) and walks only their predictions.
+constexpr int EVAL_THREADS = 1024;
+__global__ __launch_bounds__(EVAL_THREADS) void k_eval_match_log(const long long* __restrict__ ids, const float* __restrict__ scores,
+                                                                 const int* __restrict__ count, int n, const float* __restrict__ iou_box,
+                                                                 const float* __restrict__ iou_mask, const float* __restrict__ gt, int g,
+                                                                 const double* __restrict__ thr, int T, int num_classes,
+                                                                 float* __restrict__ log_score, int* __restrict__ log_class,
+                                                                 unsigned* __restrict__ log_flags, unsigned long long* __restrict__ gt_count,
+                                                                 int* __restrict__ class_rows) {
+    __shared__ int s_pred[YM_EVAL_MAX_DET];
+    __shared__ unsigned s_flags[YM_EVAL_MAX_DET];
+    __shared__ int s_gt[MAXG];
+    const int tid = threadIdx.x;
+    const int valid = count ? min(max(*count, 0), n) : n;
+    for (int i = tid; i < n; i += EVAL_THREADS) {
+        const long long id = ids[i];
+        s_pred[i] = (i < valid && id >= 0 && id < num_classes) ? (int)id : -1;
+        s_flags[i] = 0u;
+    }
+    for (int j = tid; j < g; j += EVAL_THREADS) {
+        const float v = gt[(size_t)j * 5 + 4];              // .int(): truncation toward zero
+        const int c = (v > -1.f && v < (float)num_classes) ? (int)v : -1;
+        s_gt[j] = c;
+        if (valid > 0 && c >= 0) atomicAdd(&gt_count[c], 1ull);    // an image without detections never reaches prep_metrics
+    }
+    __syncthreads();
+    if (valid > 0 && g > 0)
+        for (int item = tid; item < 2 * T * num_classes; item += EVAL_THREADS) {
+            const int c = item / (2 * T), cell = item - c * 2 * T;     // (neighbouring lanes: one class, its 2T cells -- see above)
+            const int type = cell / T, k = cell - type * T;
+            match_class(type == 0 ? iou_box : iou_mask, s_pred, s_gt, valid, g, thr[k], c,
+                        [&](int i, bool hit) { if (hit) atomicOr(&s_flags[i], 1u << cell); });
         }
+    __syncthreads();
+    for (int i = tid; i < n; i += EVAL_THREADS) {
+        const int c = s_pred[i];
+        log_class[i] = c;
+        log_score[i] = c >= 0 ? scores[i] : 0.f;
+        log_flags[i] = s_flags[i];
+        if (c >= 0) atomicAdd(&class_rows[c], 1);
+    }
+}
+
+// The flags in sorted order, once: the 2T workgroups of a class then read consecutive words.
+__global__ void k_eval_gather(const unsigned* __restrict__ flags, const long long* __restrict__ order, long long rows,
+                              unsigned* __restrict__ sorted) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const long long p = order[r];
+    sorted[r] = (p >= 0 && p < rows) ? flags[p] : 0u;
+}
+
+__device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(v, d);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double wave_suffix_max(double v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = __shfl_down(v, d);
+        if (lane + d < 64) v = fmax(v, o);
+    }
+    return v;
+}
+
+// APDataObject.get_ap of one (class, cell): workgroup (class, cell) walks the class's sorted rows twice.  Pass A counts the true
+// positives.  Pass B goes BACKWARDS in chunks of YM_EVAL_AP_ROWS_PER_PASS rows carrying (true positives before the chunk, envelope
+// of everything behind it): tp of a row = tp before the chunk + an integer scan, precision = tp / (rank + 1), envelope = suffix
+// maximum (max is exact: any association gives the reference's value).  recall = tp / num_gt depends on tp alone and grows with it, so the
+// first rank that reaches grid value k is the first rank whose tp reaches t_k = the smallest t with (double)t / num_gt >= k / 100.0
+// (found with those very quotients); it lies in the one chunk with tp_before < t_k <= tp_after (t_k = 0: rank 0), where a binary
+// search over the chunk's tp finds it and the envelope there is the sample.  Thread 0 adds the 101 samples left to right.
+constexpr int AP_THREADS = 256, AP_RPT = YM_EVAL_AP_ROWS_PER_PASS / AP_THREADS, AP_GRID = 101;
+static_assert(AP_THREADS * AP_RPT == YM_EVAL_AP_ROWS_PER_PASS && AP_THREADS >= AP_GRID, "one pass = AP_RPT rows per thread");
+__global__ __launch_bounds__(AP_THREADS) void k_eval_ap(const unsigned* __restrict__ flags, long long rows, const long long* __restrict__ seg,
+                                                        const long long* __restrict__ gt_count, int num_classes, double* __restrict__ ap,
+                                                        uint8_t* __restrict__ empty) {
+    __shared__ long long s_t[AP_GRID];
+    __shared__ double s_sample[AP_GRID];
+    __shared__ int s_tp[YM_EVAL_AP_ROWS_PER_PASS];           // tp of each row of the chunk, minus the tp before the chunk
+    __shared__ double s_env[YM_EVAL_AP_ROWS_PER_PASS];
+    __shared__ int s_wsum[AP_THREADS / 64];
+    __shared__ double s_wmax[AP_THREADS / 64];
+    __shared__ long long s_total;
+    const int c = blockIdx.x, cell = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long beg = min(max(seg[c], 0ll), rows), end = min(max(seg[c + 1], 0ll), rows);
+    if (end < beg) end = beg;
+    const long long m = end - beg, G = gt_count[c];
+    if (cell == 0 && tid == 0) empty[c] = (m == 0 && G == 0) ? 1 : 0;
+    double* out = ap + (size_t)cell * num_classes + c;
+    if (G <= 0 || m == 0) {                                    // (uniform over the workgroup)
+        if (tid == 0) *out = 0.0;
+        return;
+    }
+    const unsigned* f = flags + beg;
+    const double Gd = (double)G;
+    if (tid < AP_GRID) {
+        const double x = (double)tid / 100.0;
+        long long t = (long long)(x * Gd);
+        t = min(max(t, 0ll), G);
+        while (t > 0 && (double)(t - 1) / Gd >= x) --t;
+        while (t < G && (double)t / Gd < x) ++t;               // (G / G = 1 >= every grid value)
+        s_t[tid] = t;
+        s_sample[tid] = 0.0;
+    }
+    // pass A: true positives of the whole class
+    long long mine = 0;
+    for (long long r = tid; r < m; r += AP_THREADS) mine += (f[r] >> cell) & 1u;
+    if (tid == 0) s_total = 0;
+    __syncthreads();
+    atomicAdd((unsigned long long*)&s_total, (unsigned long long)mine);      // (integers: any order gives the same sum)
+    __syncthreads();
+    long long remaining = s_total;                              // true positives at or before the end of the current chunk
+    double carry = -1.0;                                        // envelope of the rows behind the current chunk (precision >= 0)
+    const long long chunks = (m + YM_EVAL_AP_ROWS_PER_PASS - 1) / YM_EVAL_AP_ROWS_PER_PASS;
+    for (long long ch = chunks - 1; ch >= 0; --ch) {
+        const long long r0 = ch * YM_EVAL_AP_ROWS_PER_PASS;
+        const int cn = (int)min((long long)YM_EVAL_AP_ROWS_PER_PASS, m - r0);
+        int b[AP_RPT], local = 0;
+#pragma unroll
+        for (int e = 0; e < AP_RPT; ++e) {
+            const int q = tid * AP_RPT + e;
+            b[e] = q < cn ? (int)((f[r0 + q] >> cell) & 1u) : 0;
+            local += b[e];
+        }
+        const int incl = wave_inclusive_sum(local, lane);
+        if (lane == 63) s_wsum[wave] = incl;
+        __syncthreads();
+        int before = incl - local, chunk_tp = 0;
+#pragma unroll
+        for (int w = 0; w < AP_THREADS / 64; ++w) {
+            before += w < wave ? s_wsum[w] : 0;
+            chunk_tp += s_wsum[w];
+        }
+        const long long tp_in = remaining - chunk_tp;
+        double p[AP_RPT];
+        int run = before;
+#pragma unroll
+        for (int e = 0; e < AP_RPT; ++e) {
+            const int q = tid * AP_RPT + e;
+            run += b[e];
+            s_tp[q] = run;
+            p[e] = q < cn ? (double)(tp_in + run) / (double)(r0 + q + 1) : -1.0;
+        }
+#pragma unroll
+        for (int e = AP_RPT - 2; e >= 0; --e) p[e] = fmax(p[e], p[e + 1]);
+        const double sfx = wave_suffix_max(p[0], lane);         // max over this thread's rows and the later lanes'
+        if (lane == 0) s_wmax[wave] = sfx;
+        __syncthreads();
+        double behind = carry;                                  // everything after this thread's rows
+#pragma unroll
+        for (int w = 0; w < AP_THREADS / 64; ++w) behind = w > wave ? fmax(behind, s_wmax[w]) : behind;
+        const double next_lane = __shfl_down(sfx, 1);
+        if (lane < 63) behind = fmax(behind, next_lane);
+#pragma unroll
+        for (int e = 0; e < AP_RPT; ++e) s_env[tid * AP_RPT + e] = fmax(p[e], behind);
+        __syncthreads();
+        if (tid < AP_GRID) {
+            const long long t = s_t[tid];
+            const bool here = t == 0 ? ch == 0 : (tp_in < t && t <= tp_in + chunk_tp);
+            if (here) {
+                const int want = (int)(t - tp_in);              // first row of the chunk with s_tp >= want
+                int lo = 0, hi = cn - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (s_tp[mid] >= want) hi = mid; else lo = mid + 1;
+                }
+                s_sample[tid] = s_env[lo];
+            }
+        }
+        carry = s_env[0];
+        remaining = tp_in;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double sum = 0.0;
+        for (int k = 0; k < AP_GRID; ++k) sum += s_sample[k];
+        *out = sum / 101.0;
     }
 }
 
@@ -306,4 +504,39 @@ extern "C" int ym_match_detections(const float* iou_box, const float* iou_mask, 
     hipLaunchKernelGGL(k_match_detections, dim3(2 * T), dim3(128), 0, (hipStream_t)s, iou_box, iou_mask, pred_cls, gt_cls, n, g,
                        thresholds, T, num_classes, matched);
     return ym_check_launch("match_detections");
+}
+
+extern "C" int ym_eval_match_log(const int64_t* ids, const float* scores, const int32_t* count, int n, const float* iou_box,
+                                 const float* iou_mask, const float* gt, int g, const double* thresholds, int T, int num_classes,
+                                 float* log_score, int32_t* log_class, uint32_t* log_flags, int64_t log_offset, int64_t* gt_count,
+                                 int32_t* class_rows, ym_stream_t s) {
+    YM_REQUIRE(ids && scores && thresholds && log_score && log_class && log_flags && gt_count && class_rows, "eval_match_log: null pointer");
+    YM_REQUIRE(g == 0 || (iou_box && iou_mask && gt), "eval_match_log: null pointer");
+    YM_REQUIRE(n > 0 && n <= YM_EVAL_MAX_DET && log_offset >= 0, "eval_match_log: need 0 < n <= %d rows and a log offset >= 0", YM_EVAL_MAX_DET);
+    YM_REQUIRE(g >= 0 && g <= MAXG && T > 0 && num_classes > 0, "eval_match_log: need 0 <= g <= %d", MAXG);
+    YM_REQUIRE(T <= YM_EVAL_MAX_THRESHOLDS, "eval_match_log: at most %d thresholds (2T flag bits per row)", YM_EVAL_MAX_THRESHOLDS);
+    hipLaunchKernelGGL(k_eval_match_log, dim3(1), dim3(EVAL_THREADS), 0, (hipStream_t)s, reinterpret_cast<const long long*>(ids), scores,
+                       count, n, iou_box, iou_mask, gt, g, thresholds, T, num_classes, log_score + log_offset, log_class + log_offset,
+                       log_flags + log_offset, reinterpret_cast<unsigned long long*>(gt_count), class_rows);
+    return ym_check_launch("eval_match_log");
+}
+
+extern "C" size_t ym_eval_ap_workspace_bytes(int64_t rows) { return rows > 0 ? (size_t)rows * sizeof(uint32_t) : 0; }
+
+extern "C" int ym_eval_ap(const uint32_t* log_flags, const int64_t* order, int64_t rows, const int64_t* seg, const int64_t* gt_count, int T,
+                          int num_classes, double* ap, uint8_t* empty, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    YM_REQUIRE(log_flags && seg && gt_count && ap && empty, "eval_ap: null pointer");
+    YM_REQUIRE(rows > 0 && T > 0 && T <= YM_EVAL_MAX_THRESHOLDS && num_classes > 0 && num_classes <= 65535,
+               "eval_ap: need rows > 0, 0 < T <= %d, 0 < num_classes <= 65535", YM_EVAL_MAX_THRESHOLDS);
+    hipStream_t st = (hipStream_t)s;
+    const unsigned* sorted = log_flags;
+    if (order) {
+        if (!workspace || workspace_bytes < ym_eval_ap_workspace_bytes(rows)) { ym_set_error("eval_ap: workspace too small"); return YM_ENOSPC; }
+        hipLaunchKernelGGL(k_eval_gather, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, log_flags,
+                           reinterpret_cast<const long long*>(order), (long long)rows, (unsigned*)workspace);
+        sorted = (const unsigned*)workspace;
+    }
+    hipLaunchKernelGGL(k_eval_ap, dim3((unsigned)num_classes, (unsigned)(2 * T)), dim3(AP_THREADS), 0, st, sorted, (long long)rows,
+                       reinterpret_cast<const long long*>(seg), reinterpret_cast<const long long*>(gt_count), num_classes, ap, empty);
+    return ym_check_launch("eval_ap");
 }

@@ -1,0 +1,46 @@
+"""Evaluation with several requests in flight: eval.py's loop (`eval.py:35-69,106`) through `RequestPipeline` and the
+device-resident accumulator (`utils/device_metrics.DeviceAPData`).
+
+The reference evaluates one image at a time and its `prep_metrics` reads the detections on the host, so every image is a
+synchronisation point.  Here every image is one pipeline request (forward -> nms -> after_nms on the slot's stream) whose consumer
+is `DeviceAPData.add(..., image_index=i)` on that same stream: nothing of an image is read on the host, and the log keeps the
+sample order whatever order the slots finish in.  The one download is `calc_map`'s AP grid at the end.
+"""
+import torch
+
+from .pipeline import RequestPipeline
+from .utils.device_metrics import DeviceAPData
+
+IOU_THRES = [x / 100 for x in range(50, 100, 5)]                              # eval.py:24
+
+
+def eval_pipeline(net, cfg, img, img_h, img_w, depth=4, packed_masks=True):
+    """The `RequestPipeline` `evaluate_pipelined` runs on, with its hipGraphs captured on `img`: build it once and hand it to several
+    calls (`pipe=`) where the same network evaluates more than one sample set -- four engines and their capture are no part of a set."""
+    device = next(net.parameters()).device
+    pipe = RequestPipeline(net, cfg, img.shape[2], img.shape[3], device, depth=depth, out_hw=(img_h, img_w), packed_masks=packed_masks)
+    pipe.warm_up(img.to(device), rounds=0)
+    return pipe
+
+
+def evaluate_pipelined(net, cfg, samples, depth=4, packed_masks=True, step=None, pipe=None):
+    """`samples` yields eval.py's `(img [1,3,H,W], gt [g,5], gt_masks [g,h,w], img_h, img_w)`; all images share one input size.
+    `pipe`: an idle pipeline of `eval_pipeline` to run on (`depth` and `packed_masks` are then the pipeline's); by default one is
+    built on the first sample.  Returns ((table text, box row, mask row), the DeviceAPData)."""
+    device = next(net.parameters()).device
+    acc = DeviceAPData(len(cfg.class_names), IOU_THRES, device, max_det=cfg.max_detections)
+    for i, (img, gt, gt_masks, img_h, img_w) in enumerate(samples):
+        img, gt, gt_masks = img.to(device), gt.to(device), gt_masks.to(device)
+        if pipe is None:
+            pipe = eval_pipeline(net, cfg, img, img_h, img_w, depth, packed_masks)
+
+        def consume(ids, scores, boxes_px, masks, counts, i=i, img=img, gt=gt, gt_masks=gt_masks, img_h=img_h, img_w=img_w):
+            slot_stream = torch.cuda.current_stream(device)
+            for t in (img, gt, gt_masks):                       # made on the caller's stream, read on the slot's
+                t.record_stream(slot_stream)
+            return acc.add(ids, scores, boxes_px, masks, counts, gt, gt_masks, img_h, img_w, image_index=i)
+
+        pipe.submit(img, out_hw=(img_h, img_w), consumer=consume)
+    if pipe is not None:
+        pipe.drain()
+    return acc.calc_map(step), acc

@@ -26,6 +26,14 @@ from .utils.output_utils import nms_batch, after_nms_batch
 _streams = {}
 
 
+class _Consumed:
+    """What `submit(consumer=...)` leaves in a slot: the consumer's return value and the request's event."""
+    __slots__ = ('value', 'event')
+
+    def __init__(self, value, event):
+        self.value, self.event = value, event
+
+
 def _stream_set(device, n):
     """One process-wide set of streams per device: every pipeline overlaps on the SAME streams (= the same hardware queues)."""
     key = torch.device(device)
@@ -122,6 +130,11 @@ class RequestPipeline:
             # the slot's own buffers are overwritten by its next request: hand out copies, made on the caller's stream (the slot's
             # next run is ordered behind that stream by `submit`)
             return tuple(t.clone() for t in self.engines[slot].outputs())
+        if isinstance(pend, _Consumed):                   # the detections were consumed on the slot's stream: nothing is read back
+            pend.event.synchronize()
+            if self.timed:
+                self.latencies_ms.append(self.t0[slot].elapsed_time(self.t1[slot]))
+            return pend.value
         ids, scores, box_px, masks, counts, ev = pend
         ev.synchronize()                                  # THIS request only
         if self.timed:
@@ -145,16 +158,28 @@ class RequestPipeline:
             out.append(r)
         return out[0] if self.batch == 1 else out
 
-    def submit(self, img, head_outputs=None):
+    def submit(self, img, head_outputs=None, out_hw=None, consumer=None):
         """Enqueue one request ([batch,3,H,W] images, device resident) on the next slot and return the finished result of the request
         that used this slot before (None the first `depth` times).  `head_outputs`: post-process these (class, box, coef, proto)
         tensors instead of the forward's own outputs (bench.py: a random-init network yields degenerate detections).
+        `out_hw`: this request's output size (default: the pipeline's).  `consumer`: a callable run ON THE SLOT'S STREAM, right
+        behind the post-processing, with the padded device tensors `(ids, scores, boxes_px, masks, counts)` of
+        `after_nms_batch(sync=False)`; `finish` / `drain` then hand back ITS return value for the request instead of the detections,
+        and no detection count is read on the host (`utils/device_metrics.DeviceAPData.add` is such a consumer).  What `finish` does
+        with that count is therefore not done for such a request: `detections` is not advanced, and the `cfg.visual_thre` filter is
+        not applied -- the consumer would see unfiltered rows, so a consumer with `cfg.visual_thre` > 0 raises.
         The request is ordered behind everything the caller's current stream has queued; the caller must not overwrite `img` before
         the request has finished (use one input buffer per slot when images arrive by H2D copy)."""
+        if consumer is not None and not self.with_post:
+            raise RuntimeError('RequestPipeline.submit: a consumer takes the post-processed detections (with_post=True)')
+        if consumer is not None and self.vt > 0:
+            raise RuntimeError(f'RequestPipeline.submit: cfg.visual_thre = {self.vt} is applied where the count is read on the host; '
+                               'a consumer would be handed the unfiltered rows')
         slot = self.submitted % self.depth
         self.submitted += 1
         done = self.finish(slot)
         ev = self.events[slot]
+        out_h, out_w = self.out_hw if out_hw is None else out_hw
         # `img` / `head_outputs` were produced on the caller's stream (an H2D copy, `val_aug`), and `finish` may have queued copies
         # of the slot's previous outputs there: the slot's stream starts behind that
         self.streams[slot].wait_stream(torch.cuda.current_stream(self.device))
@@ -165,13 +190,16 @@ class RequestPipeline:
             eng.run(img)
             if self.with_post:
                 cls, box, coef, proto = head_outputs if head_outputs is not None else eng.outputs()
-                r = after_nms_batch(nms_batch(cls, box, coef, proto, self.anchors, self.cfg), self.out_hw[0], self.out_hw[1], self.cfg,
+                r = after_nms_batch(nms_batch(cls, box, coef, proto, self.anchors, self.cfg), out_h, out_w, self.cfg,
                                     sync=False, packed=self.packed_masks)
-                self.counts_host[slot].copy_(r[4], non_blocking=True)
+                if consumer is None:
+                    self.counts_host[slot].copy_(r[4], non_blocking=True)
+                else:
+                    value = consumer(*r)
                 if self.timed:
                     self.t1[slot].record()
                 ev.record()
-                self.pending[slot] = r + (ev,)
+                self.pending[slot] = r + (ev,) if consumer is None else _Consumed(value, ev)
             else:
                 if self.timed:
                     self.t1[slot].record()

@@ -117,14 +117,11 @@ def prep_metrics(ap_data, ids_p, classes_p, boxes_p, masks_p, gt, gt_masks, heig
                     ap_obj.data_points.extend(zip(scores, [row[i] for i in mine]))
 
 
-def calc_map(ap_data, iou_thres, num_classes, step):
-    """mAP table of the reference's `calc_map` (common_utils.py:219-255) from the AP grid [iou type][threshold][class]: per
-    (type, threshold) the mean AP (x 100) over the classes that hold data, then the mean over the thresholds as 'all'.  Python float
-    sums in class / threshold order, so the rounded rows equal the reference's (tests/golden/metrics_*.npz).  Returns
-    (table text, box row, mask row); the table is plain ' | '-joined rows (terminaltables is a formatting dependency)."""
+def map_table(cell_ap, iou_thres, num_classes, step):
+    """The arithmetic and the text of `calc_map` over `cell_ap(kind, t, c)` -> the AP of that cell, or None when the cell is empty:
+    shared by the host accumulator below and `device_metrics.DeviceAPData.calc_map` (whose APs come from `ym_eval_ap`)."""
     def mean_ap(kind, t):
-        cells = ap_data[kind][t]
-        vals = [cells[c].get_ap() for c in range(num_classes) if not cells[c].is_empty()]
+        vals = [v for v in (cell_ap(kind, t, c) for c in range(num_classes)) if v is not None]
         return sum(vals) / len(vals) * 100 if vals else 0
 
     rows = [[f'{step // 1000}k' if step else '', 'all'] + [int(t * 100) for t in iou_thres]]
@@ -132,6 +129,18 @@ def calc_map(ap_data, iou_thres, num_classes, step):
         per_thr = [mean_ap(kind, t) for t in range(len(iou_thres))]
         rows.append([kind] + [round(v, 2) for v in [sum(per_thr) / len(per_thr)] + per_thr])
     return '\n'.join(' | '.join(str(c) for c in row) for row in rows), rows[1], rows[2]
+
+
+def calc_map(ap_data, iou_thres, num_classes, step):
+    """mAP table of the reference's `calc_map` (common_utils.py:219-255) from the AP grid [iou type][threshold][class]: per
+    (type, threshold) the mean AP (x 100) over the classes that hold data, then the mean over the thresholds as 'all'.  Python float
+    sums in class / threshold order, so the rounded rows equal the reference's (tests/golden/metrics_*.npz).  Returns
+    (table text, box row, mask row); the table is plain ' | '-joined rows (terminaltables is a formatting dependency)."""
+    def cell_ap(kind, t, c):
+        cell = ap_data[kind][t][c]
+        return None if cell.is_empty() else cell.get_ap()
+
+    return map_table(cell_ap, iou_thres, num_classes, step)
 
 
 def rle_encode(masks, cap_runs=4096):
@@ -249,3 +258,6 @@ def save_best(net, mask_map, cfg_name, step):
 def save_latest(net, cfg_name, step):
     """`weights/latest_<cfg>_<step>.pth`, replacing the previous one (reference common_utils.py:56-63, train.py:184,196)."""
     _replace_checkpoint('latest', cfg_name, f'latest_{cfg_name}_{step}.pth', net)
+
+
+from .device_metrics import DeviceAPData  # noqa: E402,F401  (the device-resident accumulator; it imports map_table from here lazily)
