@@ -17,6 +17,7 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 from utils import timer                                                       # noqa: E402  (dropin/)
 from utils.output_utils import after_nms, nms                                 # noqa: E402
 from utils.common_utils import APDataObject, DeviceAPData, MakeJson, prep_metrics, calc_map  # noqa: E402
+from yolact_minimal_amd.utils.coco_eval import DeviceCOCOeval, coco_gt, score_results        # noqa: E402  (coco_api='score', coco_summary)
 from yolact_minimal_amd.utils.common_utils import rle_encode                 # noqa: E402  (coco_api='device' only)
 
 
@@ -109,10 +110,13 @@ IOU_THRES = [x / 100 for x in range(50, 100, 5)]                              # 
 
 
 def eval_loop(net, cfg, data_loader, image_ids=None, coco_api=False, make_json=None, sync_stages=True, packed_masks=False,
-              device_metrics=False):
+              device_metrics=False, coco=None):
     """eval.py:35-69 for every `(img, gt, gt_masks, img_h, img_w)` of `data_loader`, one image at a time.  `coco_api`: the
     `--coco_api` branch (eval.py:60-67: boxes and the dense fp32 masks cross PCIe, `MakeJson.add_bbox/add_mask`; 'device' = the
-    same records with the RLE strings made on the GPU); otherwise
+    same records with the RLE strings made on the GPU; 'score' = no JSON at all: the metric stage is `DeviceCOCOeval.add` on
+    `after_nms`' device tensors against the annotation-file ground truth of image `image_ids[i]` in `coco`, the dataset's `COCO`
+    index (default `data_loader.dataset.coco`), every image of the loader counts -- also one without detections -- and the
+    evaluator is returned in place of `make_json`: `coco_summary` prints its twelve numbers per IoU type); otherwise
     `prep_metrics` on the device tensors (eval.py:69).  `sync_stages`: the reference's `timer.counter` fences every stage with a
     device synchronize (utils/timer.py:63-76); False leaves the fences out (the loop is otherwise unchanged).
     `packed_masks`: `after_nms(..., packed=True)` — the masks are a `PackedMasks` (1 bit per pixel) in all three branches; for
@@ -122,7 +126,15 @@ def eval_loop(net, cfg, data_loader, image_ids=None, coco_api=False, make_json=N
     Returns (ap_data, make_json, images with detections, seconds)."""
     ap_data = {'box': [[APDataObject() for _ in cfg.class_names] for _ in IOU_THRES],
                'mask': [[APDataObject() for _ in cfg.class_names] for _ in IOU_THRES]}
-    if coco_api and make_json is None:
+    scorer = None
+    if coco_api == 'score':
+        if device_metrics or image_ids is None:
+            raise ValueError("coco_api='score' needs image_ids (the annotation file's) and does not combine with device_metrics")
+        coco = data_loader.dataset.coco if coco is None else coco
+        # cocoapi walks the images in ascending image id: that is the evaluator's image index
+        slot = {img_id: k for k, img_id in enumerate(sorted(coco.imgs))}
+        make_json = scorer = DeviceCOCOeval(len(cfg.class_names), 'cuda', max_det=cfg.max_detections)
+    elif coco_api and make_json is None:
         make_json = MakeJson()
     if device_metrics:
         if coco_api:
@@ -150,7 +162,17 @@ def eval_loop(net, cfg, data_loader, image_ids=None, coco_api=False, make_json=N
             else:
                 ids_p, class_p, boxes_p, masks_p = after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w)
             if ids_p is None:
+                if scorer is not None:                          # (its gts still count: COCOeval evaluates every image)
+                    scorer.add(None, None, None, None, None, coco_gt(coco, image_ids[i], cfg.continuous_id, 'cuda'),
+                               image_index=slot[image_ids[i]])
                 continue
+
+        if scorer is not None:
+            with counter('metric'):
+                scorer.add(ids_p, class_p, boxes_p, masks_p, None, coco_gt(coco, image_ids[i], cfg.continuous_id, 'cuda'),
+                           image_index=slot[image_ids[i]])
+            seen += 1
+            continue
 
         if device_metrics:
             with counter('metric'):
@@ -198,6 +220,31 @@ class _no_counter:
 
     def __exit__(self, *exc):
         return False
+
+
+def coco_summary(results, ann_file=None, label_map=None):
+    """eval.py:86-104 after the dump: "Evaluating BBoxes:" / "Evaluating Masks:" and cocoapi's twelve lines each.  `results`: the
+    `DeviceCOCOeval` of `eval_loop(coco_api='score')`, a `MakeJson` (dumped to a temporary directory first) or the
+    `(bbox_path, mask_path)` of files already dumped; the last two are scored against `ann_file` (`score_results`).
+    Returns {'bbox': (stats, text), 'segm': (stats, text)}."""
+    if isinstance(results, DeviceCOCOeval):
+        out = results.summarize()
+    else:
+        import os
+        import tempfile
+        with tempfile.TemporaryDirectory() as tmp:
+            if isinstance(results, MakeJson):
+                paths = (os.path.join(tmp, 'bbox_detections.json'), os.path.join(tmp, 'mask_detections.json'))
+                results.dump(*paths)
+            else:
+                paths = tuple(results)
+            scored = score_results(ann_file, paths[0], paths[1], label_map=label_map)
+        out = {kind: (r['stats'], r['text']) for kind, r in scored.items()}
+    for kind, title in (('bbox', 'BBoxes'), ('segm', 'Masks')):
+        if kind in out:
+            print(f'\nEvaluating {title}:')
+            print(out[kind][1])
+    return out
 
 
 def table(ap_data, cfg, step=None):

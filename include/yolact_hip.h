@@ -709,6 +709,61 @@ size_t ym_eval_ap_workspace_bytes(int64_t rows);
 int ym_eval_ap(const uint32_t* log_flags, const int64_t* order, int64_t rows, const int64_t* seg, const int64_t* gt_count, int T,
                int num_classes, double* ap, uint8_t* empty, void* workspace, size_t workspace_bytes, ym_stream_t s);
 
+/* ---- device-resident COCO evaluator (eval.py:90-104: pycocotools COCOeval on the dumped detections) --------------------------
+ * The protocol is the published cocoapi's (cocoeval.py evaluate / computeIoU / evaluateImg / accumulate, maskApi.c bbIou / rleIou)
+ * with its default parameters, which the caller passes as device arrays (iouThrs, recThrs, areaRng, maxDets, eps = spacing(1)).
+ * All IoUs and quotients are fp64 without contraction; every sum is an integer count; integer atomics only; nothing reads the host.
+ *
+ * ym_coco_iou_box: bbIou.  dt_xywh fp64 [n][4], gt_xywh fp64 [g][4] ([x, y, w, h]), iscrowd uint8 [g] -> iou fp64 [n][g]:
+ *   w = min(dx+dw, gx+gw) - max(dx, gx), h likewise; w <= 0 or h <= 0 -> 0; i = w*h; u = crowd ? da : da + ga - i; i / u.
+ * ym_coco_iou_mask_packed: rleIou on bit rows ("bit-packed instance masks": bits_d [n][words], bits_g [g][words], words = H * Wq):
+ *   i = |d & g|; i == 0 -> 0; else i / (crowd ? |d| : |d| + |g| - i).  area_d int32 [n] = |d| (the detection's segm area).
+ *
+ * The log: one row per (image slot, detection row) at position image_index * max_det + row: log_score fp32, log_class int32 (-1 =
+ * no data point), log_rank int32 (the row's rank among the image's rows of its class: score descending, equal scores in row order),
+ * log_flags uint32 [YM_COCO_WORDS_PER_ROW] = one word per (IoU type, area range), word type * YM_COCO_AREAS + a: bit k = matched at
+ * threshold k, bit 16 + k = ignored at threshold k.  npig int64 [YM_COCO_AREAS][num_classes] (non-ignored gts), class_rows int32
+ * [num_classes] (data points per class).  The caller initialises log_class to -1 and the counters to 0.
+ *
+ * ym_coco_match_log: computeIoU's ordering and evaluateImg for ONE image, every category, area range, threshold and IoU type.
+ *   ids int64 [n], scores fp32 [n], count int32 on the device (NULL = n), n <= YM_EVAL_MAX_DET (n = 0: only the gts are counted);
+ *   boxes_px int32 [n][4] or NULL: rows whose pixel box has (x2-x1)*(y2-y1) <= 0 are no detections (eval.py:65);
+ *   iou_box / iou_mask fp64 [n][g] and area_box fp64 [n] / area_mask int32 [n] (the detection's area per IoU type); an IoU type whose
+ *   area pointer is NULL is not evaluated; gt_class int32 [g], gt_iscrowd uint8 [g], gt_area fp64 [g], g <= YM_COCO_MAX_GT;
+ *   thresholds fp64 [T], T <= YM_EVAL_MAX_THRESHOLDS; area_rng fp64 [YM_COCO_AREAS][2]; max_rank = maxDets[-1].
+ *   A gt is ignored when iscrowd or area < lo or area > hi; the gts of a category are walked non-ignored first (stable).  Per
+ *   detection in rank order: best = min(t, 1 - 1e-10), m = none; skip a gt already matched at this threshold unless it is a crowd;
+ *   STOP when m is a non-ignored gt and the current gt is ignored; skip if iou < best; else take it (among equal IoUs the later
+ *   gt wins).  A matched detection inherits its gt's ignore flag; an unmatched one whose own area is outside the range is ignored.
+ *   Rows of rank >= max_rank, rows at or past the count and rows of a class outside 0..num_classes-1 are written with class -1.
+ *
+ * ym_coco_accumulate: accumulate.  order int64 [rows] = log positions by (class ascending, score descending, position ascending), seg
+ *   int64 [num_classes + 1] as for ym_eval_ap; rec_thrs fp64 [R], max_dets int32 [M] on the device; kinds: bit 0 = bbox, bit 1 = segm.
+ *   precision fp64 [2][T][R][num_classes][YM_COCO_AREAS][M] and recall fp64 [2][T][num_classes][YM_COCO_AREAS][M], which the caller
+ *   initialises to -1; a cell with npig == 0 keeps it.  Otherwise, over the category's rows of rank < maxDet: tp / fp = running
+ *   counts of matched / unmatched non-ignored rows, rc = tp / npig, pr = tp / ((fp + tp) + eps), recall = rc[-1] (0 without rows),
+ *   envelope from the back, precision[r] = pr at the first row with rc >= rec_thrs[r] (0 when there is none).  A category is walked
+ *   in passes of YM_COCO_ROWS_PER_PASS rows with carried state, so its length is unbounded.
+ *   workspace >= ym_coco_accumulate_workspace_bytes(rows) (flag words and ranks in sorted order). */
+#define YM_COCO_MAX_GT 512
+#define YM_COCO_AREAS 4
+#define YM_COCO_WORDS_PER_ROW 8
+#define YM_COCO_ROWS_PER_PASS 1024
+int ym_coco_iou_box(const double* dt_xywh, int n, const double* gt_xywh, int g, const uint8_t* iscrowd, double* iou, ym_stream_t s);
+int ym_coco_iou_mask_packed(const uint64_t* bits_d, int n, const uint64_t* bits_g, int g, int64_t words, const uint8_t* iscrowd,
+                            double* iou, int32_t* area_d, ym_stream_t s);
+int ym_coco_match_log(const int64_t* ids, const float* scores, const int32_t* count, int n, const int32_t* boxes_px,
+                      const double* iou_box, const double* iou_mask, const double* area_box, const int32_t* area_mask,
+                      const int32_t* gt_class, const uint8_t* gt_iscrowd, const double* gt_area, int g,
+                      const double* thresholds, int T, const double* area_rng, int num_classes, int max_rank,
+                      float* log_score, int32_t* log_class, int32_t* log_rank, uint32_t* log_flags, int64_t log_offset,
+                      int64_t* npig, int32_t* class_rows, ym_stream_t s);
+size_t ym_coco_accumulate_workspace_bytes(int64_t rows);
+int ym_coco_accumulate(const uint32_t* log_flags, const int32_t* log_rank, const int64_t* order, int64_t rows, const int64_t* seg,
+                       const int64_t* npig, const double* rec_thrs, int R, const int32_t* max_dets, int M, int T,
+                       int num_classes, double eps, int kinds, double* precision, double* recall, void* workspace,
+                       size_t workspace_bytes, ym_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ DRAW_HIDE_MASK, DRAW_HIDE_BBOX, DRAW_HIDE_SCORE, DRAW_REAL_TIME = 1, 2, 4, 8
 DRAW_FONT_ADVANCE, DRAW_FONT_HEIGHT, DRAW_NAME_STRIDE, DRAW_LABEL_MAX, DRAW_MAX_DET = 12, 14, 40, 44, 512
 # YM_EVAL_* of include/yolact_hip.h (tests/test_device_metrics_cpu.py compares them with the header)
 EVAL_MAX_DET, EVAL_MAX_THRESHOLDS, EVAL_AP_ROWS_PER_PASS = 1024, 16, 1024
+# YM_COCO_* of include/yolact_hip.h (tests/test_coco_eval_cpu.py compares them with the header)
+COCO_MAX_GT, COCO_AREAS, COCO_WORDS_PER_ROW, COCO_ROWS_PER_PASS = 512, 4, 8, 1024
 
 # every symbol include/yolact_hip.h declares (checked by tests/test_abi.py without a GPU)
 ABI_SYMBOLS = (
@@ -43,6 +45,7 @@ ABI_SYMBOLS = (
     'ym_bn_train_bwd_workspace_bytes', 'ym_bn_train_bwd', 'ym_bn_train_bwd_apply', 'ym_act_bias_bwd', 'ym_conv2d_fuses_bn_stats', 'ym_bn_train_fwd_stats', 'ym_maxpool3x3s2_bwd', 'ym_maxpool3x3s2_fwd_idx', 'ym_maxpool3x3s2_bwd_idx', 'ym_bilinear2x_bwd', 'ym_sgd_step',
     'ym_conv2d_bn_partial_rows', 'ym_conv2d_effective_plan', 'ym_bn_partials_finish', 'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes',
     'ym_eval_match_log', 'ym_eval_ap_workspace_bytes', 'ym_eval_ap',
+    'ym_coco_iou_box', 'ym_coco_iou_mask_packed', 'ym_coco_match_log', 'ym_coco_accumulate_workspace_bytes', 'ym_coco_accumulate',
 )
 
 
@@ -247,6 +250,12 @@ def lib():
         L.ym_eval_ap_workspace_bytes.argtypes = [i64]
         L.ym_eval_ap_workspace_bytes.restype = sz
         L.ym_eval_ap.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, vp, vp, sz, vp]
+        L.ym_coco_iou_box.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+        L.ym_coco_iou_mask_packed.argtypes = [vp, i32, vp, i32, i64, vp, vp, vp, vp]
+        L.ym_coco_match_log.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
+        L.ym_coco_accumulate_workspace_bytes.argtypes = [i64]
+        L.ym_coco_accumulate_workspace_bytes.restype = sz
+        L.ym_coco_accumulate.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, vp, i32, i32, i32, ctypes.c_double, i32, vp, vp, vp, sz, vp]
         for name in ABI_SYMBOLS:
             fn = getattr(L, name)
             if name not in ('ym_last_error', 'ym_conv2d_workspace_bytes', 'ym_nms_workspace_bytes',
@@ -254,7 +263,7 @@ def lib():
                             'ym_sizeof_conv_desc', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
                             'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes',
                             'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes',
-                            'ym_eval_ap_workspace_bytes'):
+                            'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

@@ -9,8 +9,9 @@ several requests in flight.  `DeviceAPData` keeps what those lists hold in a dev
 on the caller's stream; `calc_map` is one stable device sort, `ym_eval_ap` and ONE download of the AP grid.  `to_ap_data()` rebuilds
 the host accumulator from the log (the bridge to everything that takes `ap_data`).
 
-Not covered: merging accumulators across ranks, the `--coco_api` branch, more than 512 gt instances per image, NaN scores as data
-points (a NaN below the count would be ordered by its bit pattern, not like python's sort).
+Not covered: merging accumulators across ranks, more than 512 gt instances per image, NaN scores as data points (a NaN below the
+count would be ordered by its bit pattern, not like python's sort).  The `--coco_api` branch's scores (the COCO protocol: crowds, area
+ranges, maxDets, average recall) are `utils/coco_eval.py`'s `DeviceCOCOeval`.
 """
 import ctypes
 
