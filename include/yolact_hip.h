@@ -506,6 +506,8 @@ typedef struct {
     float img_size;          /* cfg.img_size, used by the greedy ("traditional") path only */
 } ym_nms_cfg;
 
+/* The one workspace size for both single-image entries below: the larger of what fast_nms and greedy NMS need for one image (the
+ * latter, = ym_greedy_nms_batch_workspace_bytes(cfg, 1)).  Host only, 0 on a bad cfg. */
 size_t ym_nms_workspace_bytes(const ym_nms_cfg* cfg);
 
 /* `nms()` with fast_nms (utils/output_utils.py:126-163 + :11-43 + box_iou utils/box_utils.py:8-37)
@@ -529,7 +531,8 @@ int ym_detect_fast_nms_batch(const float* class_pred, const float* box_pred, con
                              float* out_boxes, float* out_coefs, void* workspace, size_t workspace_bytes, ym_stream_t s);
 
 /* Same contract, greedy per-class NMS: replaces traditional_nms (utils/output_utils.py:84-123) and the
- * Cython kernel it calls (cython_nms.pyx:24-74) without the 80 D2H/H2D round trips. */
+ * Cython kernel it calls (cython_nms.pyx:24-74) without the 80 D2H/H2D round trips.  It IS ym_detect_greedy_nms_batch (below) with
+ * B = 1: its rule, its checks, its workspace (workspace >= ym_nms_workspace_bytes(cfg)). */
 int ym_detect_greedy_nms(const float* class_pred, const float* box_pred, const float* coef_pred,
                          const float* anchors, const ym_nms_cfg* cfg, int32_t* out_count, int64_t* out_ids,
                          float* out_scores, float* out_boxes, float* out_coefs, void* workspace,
@@ -546,13 +549,13 @@ int ym_detect_greedy_nms(const float* class_pred, const float* box_pred, const f
  *   candidates, the sequential result exactly.  The order is a counting rank, O(n^2) per class of n candidates.
  *   Per image: the max_det highest scores over all kept (class, candidate) pairs, equal scores in class-major, ascending anchor
  *   order; boxes = (b * img_size) / img_size; coefficients gathered from coef_pred.
- * B = 1 gives the values of ym_detect_greedy_nms bit for bit.
+ * ym_detect_greedy_nms is this entry with B = 1, so B = 1 gives its values bit for bit by construction.
  * Workspace per image (every term rounded up to 256 bytes), with S = ym_nms_batch_workspace_bytes(cfg, 1), n = (C-1) * N:
  *   S + 4 n (candidate lists) + 4 (C-1) (their lengths) + n (kept flags)          when N <= 4096
  *   ... + 4 n (candidate by rank)                                                 when N >  4096
  * A class of up to 4096 candidates keeps its sorted boxes, scores, order and alive flags in LDS (25 bytes per candidate); a larger
- * one reads its boxes through the order in global memory.  N = 18525, C = 81: 19.8 MB against the 45.0 MB of
- * ym_nms_workspace_bytes.  ym_greedy_nms_batch_workspace_bytes is host only, linear in B, 0 on a bad cfg or B < 1. */
+ * one reads its boxes through the order in global memory.  N = 18525, C = 81: 19.8 MB per image.
+ * ym_greedy_nms_batch_workspace_bytes is host only, linear in B, 0 on a bad cfg or B < 1. */
 size_t ym_greedy_nms_batch_workspace_bytes(const ym_nms_cfg* cfg, int B);
 int ym_detect_greedy_nms_batch(const float* class_pred, const float* box_pred, const float* coef_pred, const float* anchors,
                                const ym_nms_cfg* cfg, int B, int32_t* out_count, int64_t* out_ids, float* out_scores,
@@ -565,7 +568,8 @@ int ym_expf_cr(const float* x, float* y, int64_t n, ym_stream_t s);
 
 /* Drop-in for `cython_nms.nms(dets, thresh)` (cython_nms.pyx:24) on device data: dets [n][5]
  * (x1,y1,x2,y2,score), "+1" areas, suppress ovr >= thresh; keep_mask uint8[n] (1 = kept), in original
- * index order like np.where(suppressed == 0).  workspace >= ym_greedy_nms_workspace_bytes(n). */
+ * index order like np.where(suppressed == 0).  Equal scores go by HIGHER index first; one workgroup, the chunked suppression of
+ * ym_detect_greedy_nms_batch over the one list, its order a counting rank (O(n^2)).  workspace >= ym_greedy_nms_workspace_bytes(n). */
 size_t ym_greedy_nms_workspace_bytes(int n);
 int ym_greedy_nms(const float* dets, int n, float thresh, uint8_t* keep_mask, int32_t* out_count,
                   void* workspace, size_t workspace_bytes, ym_stream_t s);

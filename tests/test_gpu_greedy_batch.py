@@ -2,8 +2,9 @@
 `ym_detect_greedy_nms_batch` (suppression in chunks of 64 sorted candidates).
 
 The contract is the CPU oracle `R.nms(..., traditional=True, stable=True, exp='cr')` per image: ids, scores, boxes and coefs bit for
-bit, `None` <-> count 0.  Every case also asserts equality with the per-image `nms()` (the older one-barrier-per-candidate kernel)
-on the same tensors, and that a second call returns the same bits.  The inputs sit on the edges of the new kernel: a class of
+bit, `None` <-> count 0.  Every case also asserts equality with the per-image `nms()` (the same kernels as a batch of one: image b
+of a larger batch against a batch of its own checks the workspace striding) on the same tensors, and that a second call returns the
+same bits.  The inputs sit on the edges of the kernel: a class of
 exactly one chunk and one just past it, an empty image between two full ones, ties everywhere (also on the max_det cut), a chain
 whose suppressed links sit in other chunks than their neighbours, the full 544 px geometry, and classes larger than what the
 kernel stages in LDS (4096 candidates) and than what it holds of their scores there (25 600)."""
@@ -289,6 +290,43 @@ def test_workspace_is_respected_and_checked_before_any_launch():
     assert bool((ws[need:] == 0xA5).all()), 'the call wrote past ym_greedy_nms_batch_workspace_bytes'
     for b, w in ((0, want[0]), (2, want[1])):
         _check_nms(tuple(t[b] for t in out), w)
+
+
+def test_single_image_entry_workspace_is_respected_and_checked_before_any_launch():
+    """`ym_detect_greedy_nms` with `ym_nms_workspace_bytes`: one byte less is refused before anything runs, the stated size is
+    enough, and neither the guard behind the workspace nor an output row at or beyond the count is written."""
+    from yolact_minimal_amd import hip
+    parts, anchors, want = _three_at_128()
+    head = [t[0].contiguous() for t in _to_dev([parts[0]])[:3]]
+    a = anchors.to(DEV)
+    ncfg = hip.NmsCfg(1023, 81, 32, 200, 100, 0.05, 0.5, 128.0)
+    need = hip.lib().ym_nms_workspace_bytes(ctypes.byref(ncfg))
+    assert need > 0
+    guard, md = 4096, 128                                                   # (28 output rows behind the 100 the call may fill)
+    ws = torch.full((need + guard,), 0xA5, dtype=torch.uint8, device=DEV)
+    count = torch.full((1,), -1, dtype=torch.int32, device=DEV)
+    out = [torch.full((md * w * 4,), 0x5A, dtype=torch.uint8, device=DEV) for w in (2, 1, 4, 32)]     # ids, scores, boxes, coefs
+    patterns = [o.clone() for o in out]
+
+    def call(ws_bytes):
+        return hip.lib().ym_detect_greedy_nms(hip.ptr(head[0]), hip.ptr(head[1]), hip.ptr(head[2]), hip.ptr(a), ctypes.byref(ncfg),
+                                              hip.ptr(count, torch.int32), *[ctypes.c_void_p(o.data_ptr()) for o in out],
+                                              ctypes.c_void_p(ws.data_ptr()), ws_bytes, hip.stream_ptr())
+
+    rc = call(need - 1)
+    torch.cuda.synchronize()
+    assert rc == -2, 'YM_ENOSPC'                                            # include/yolact_hip.h
+    assert count.tolist() == [-1]
+    assert bool((ws == 0xA5).all()), 'a refused call must not have launched anything'
+    assert all(torch.equal(o, p) for o, p in zip(out, patterns))
+    hip.check(call(need), 'ym_detect_greedy_nms')
+    torch.cuda.synchronize()
+    assert count.tolist() == [100]
+    assert bool((ws[need:] == 0xA5).all()), 'the call wrote past ym_nms_workspace_bytes'
+    rows = (out[0].view(torch.int64), out[1].view(torch.float32), out[2].view(torch.float32).view(md, 4), out[3].view(torch.float32).view(md, 32))
+    _check_nms(tuple(r[:100] for r in rows), want[0])
+    for o, p, w in zip(out, patterns, (2, 1, 4, 32)):
+        assert torch.equal(o[100 * w * 4:], p[100 * w * 4:]), 'rows at or beyond the count must keep the caller\'s bytes'
 
 
 def test_a_non_default_stream_has_its_own_scratch():

@@ -232,11 +232,33 @@ def test_greedy_nms_drop_in_known_answers():
     assert run(np.array([[0, 0, 9, 9, 0.9], [4, 0, 13, 9, 0.8], [8, 0, 17, 9, 0.7]], np.float32), 0.4) == [0, 2]
     assert run(np.zeros((0, 5), np.float32), 0.5) == []
     rng = np.random.default_rng(0)
-    for n in (1, 7, 64, 1500):
+
+    def random_dets(n):
         xy = rng.uniform(0, 500, (n, 2)).astype(np.float32)
         wh = rng.uniform(5, 120, (n, 2)).astype(np.float32)
-        dets = np.concatenate([xy, xy + wh, rng.uniform(0.05, 1, (n, 1)).astype(np.float32)], 1)
+        return np.concatenate([xy, xy + wh, rng.uniform(0.05, 1, (n, 1)).astype(np.float32)], 1)
+
+    # the suppression runs in chunks of 64 sorted boxes: one short of a chunk, one chunk, one past it, two, two and one, many
+    for n in (1, 7, 63, 64, 65, 128, 129, 1500):
+        dets = random_dets(n)
         assert run(dets, 0.5) == R.greedy_nms(dets, 0.5).tolist()
+    # tied scores (higher index first: tests/test_oracle_greedy_nms.py pins the oracle's order)
+    for n in (129, 1500):
+        dets = random_dets(n)
+        dets[:, 4] = np.round(dets[:, 4] * 8) / 8
+        same = np.unique(dets[:, 4], return_counts=True)[1].astype(np.int64)
+        assert int((same * (same - 1) // 2).sum()) >= n // 2, 'the input is meant to hold many equal-score pairs'
+        assert run(dets, 0.5) == R.greedy_nms(dets, 0.5).tolist()
+    # the 204-box chain whose suppressed links sit in other chunks than their neighbours, given in sorted order
+    from tests.test_gpu_greedy_batch import _chain
+    part, anchors, idx = _chain()
+    dets = torch.cat([R.decode(part[1][0], anchors, 'cr')[idx] * 544.0, part[0][0, idx, 1:2]], 1).numpy()
+    want = R.greedy_nms(dets, 0.5).tolist()
+    kept = np.zeros(204, dtype=bool)
+    kept[want] = True
+    for k in range(4):
+        assert kept[64 * k:64 * (k + 1)].any() and not kept[64 * k:64 * (k + 1)].all(), f'chunk {k} must hold keeps and drops'
+    assert run(dets, 0.5) == want
 
 
 def test_mask_assemble_matches_oracle():

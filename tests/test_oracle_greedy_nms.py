@@ -37,5 +37,16 @@ def test_touching_boxes_overlap_by_plus_one_convention():
     assert R.greedy_nms(dets, 0.05).tolist() == [0]
 
 
+def test_equal_scores_go_by_higher_index_first():
+    # the order the kernels are held to on tied inputs (oracle/greedy_nms.c: reversed stable-ascending sort)
+    dets = np.array([[0, 0, 9, 9, 0.5], [0, 0, 9, 9, 0.5], [1, 0, 10, 9, 0.5]], np.float32)
+    assert R.greedy_nms(dets, 0.5).tolist() == [2]
+    assert R.greedy_nms(dets[:2], 0.5).tolist() == [1]
+    # index 2 goes first and is far from 0; 1 falls to 2, so 0 stays although 1 (a copy of it) would have taken it
+    dets = np.array([[0, 0, 9, 9, 0.5], [0, 0, 9, 9, 0.5], [0, 0, 9, 5, 0.5]], np.float32)    # 2 against 0 / 1: 60 / 100
+    assert R.greedy_nms(dets, 0.7).tolist() == [1, 2]
+    assert R.greedy_nms(dets, 0.6).tolist() == [2]
+
+
 def test_empty():
     assert R.greedy_nms(np.zeros((0, 5), np.float32), 0.5).tolist() == []

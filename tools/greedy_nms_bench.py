@@ -1,18 +1,17 @@
 #!/usr/bin/env python3
-"""What `--traditional_nms` costs through the batched entry (`nms_batch` with `cfg.traditional_nms`: `ym_detect_greedy_nms_batch`,
-suppression in chunks of 64 sorted candidates) against the single-image entry behind `nms()` (`ym_detect_greedy_nms`: one workgroup
-barrier per candidate), on the 544 px geometry: `synth_head_outputs(18525, seed=1, bg_bias=4.0)` (dense, up to 879 candidates per
-class) and `seed=2, bg_bias=9.0` (sparse, up to 279).
+"""What `--traditional_nms` costs through `nms()` (`ym_detect_greedy_nms`, the batch of one plus the host read of the count) and through
+`nms_batch` with `cfg.traditional_nms` (`ym_detect_greedy_nms_batch`: suppression in chunks of 64 sorted candidates), on the 544 px
+geometry: `synth_head_outputs(18525, seed=1, bg_bias=4.0)` (dense, up to 879 candidates per class) and `seed=2, bg_bias=9.0`
+(sparse, up to 279).
 
 One process.  Per input the variants are alternated `--rounds` times after `--warmup` calls each; a window holds as many calls as
 fill `--window-ms` (at least `--iters`); the figure is HIP-event time per call around the window.  Variants:
   nms_greedy        `nms()` with the flag: the single-image entry plus its one host read of the count, as a caller gets it
-  entry_greedy      `ym_detect_greedy_nms` called directly, no host read: the older kernels alone
   batch_greedy_b1 / _b8   `nms_batch` with the flag, 1 and 8 images (8 copies of the input)
   batch_fast_b1 / _b8     `nms_batch` without it (fast_nms), for scale
 Before anything is timed the batched results are compared with `nms()`'s, bit for bit.  Prints one JSON line (every round, medians,
-min / max, workspace bytes per image of both greedy entries, the acceptance verdict) and writes the table to `--out`.
-Acceptance (dense, one image): the SLOWEST batch_greedy_b1 window must be below the FASTEST nms_greedy window."""
+min / max, workspace bytes per image) and writes the table to `--out`.  `profiles/greedy_nms_batch_544.md` is the record of the
+retired one-barrier-per-candidate kernels, `profiles/greedy_nms_one_path_544.md` of their removal."""
 import argparse
 import ctypes
 import gc
@@ -32,7 +31,7 @@ from yolact_minimal_amd.config import build_cfg  # noqa: E402
 from yolact_minimal_amd.utils.output_utils import nms, nms_batch  # noqa: E402
 
 INPUTS = (('dense544', dict(seed=1, bg_bias=4.0)), ('sparse544', dict(seed=2, bg_bias=9.0)))
-ORDER = ('nms_greedy', 'entry_greedy', 'batch_greedy_b1', 'batch_greedy_b8', 'batch_fast_b1', 'batch_fast_b8')
+ORDER = ('nms_greedy', 'batch_greedy_b1', 'batch_greedy_b8', 'batch_fast_b1', 'batch_fast_b8')
 
 
 def timed(fn, iters):
@@ -66,38 +65,24 @@ def variants(head, anchors, dev):
         for got in nms_batch(*batch, a, greedy).split():
             assert all(torch.equal(x, y) for x, y in zip(got[:4], want[:4])), 'nms_batch(traditional_nms) differs from nms()'
     ncfg = nms_cfg(greedy, one[0].shape[1], one[0].shape[2])
-    L = hip.lib()
-    ws = torch.empty(L.ym_nms_workspace_bytes(ctypes.byref(ncfg)), dtype=torch.uint8, device=dev)
-    md = ncfg.max_det
-    out = (torch.empty(1, dtype=torch.int32, device=dev), torch.empty(md, dtype=torch.int64, device=dev), torch.empty(md, device=dev),
-           torch.empty(md, 4, device=dev), torch.empty(md, 32, device=dev))
-    flat = [t[0].contiguous() for t in one[:3]]
-
-    def entry():
-        hip.check(L.ym_detect_greedy_nms(hip.ptr(flat[0]), hip.ptr(flat[1]), hip.ptr(flat[2]), hip.ptr(a), ctypes.byref(ncfg),
-                                         hip.ptr(out[0], torch.int32), hip.ptr(out[1], torch.int64), hip.ptr(out[2]), hip.ptr(out[3]),
-                                         hip.ptr(out[4]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()), 'ym_detect_greedy_nms')
-
-    fns = {'nms_greedy': lambda: nms(*one, a, greedy), 'entry_greedy': entry,
+    fns = {'nms_greedy': lambda: nms(*one, a, greedy),
            'batch_greedy_b1': lambda: nms_batch(*one, a, greedy), 'batch_greedy_b8': lambda: nms_batch(*eight, a, greedy),
            'batch_fast_b1': lambda: nms_batch(*one, a, fast), 'batch_fast_b8': lambda: nms_batch(*eight, a, fast)}
-    ws_bytes = {'ym_detect_greedy_nms': int(L.ym_nms_workspace_bytes(ctypes.byref(ncfg))),
-                'ym_detect_greedy_nms_batch': int(L.ym_greedy_nms_batch_workspace_bytes(ctypes.byref(ncfg), 1))}
+    ws_bytes = int(hip.lib().ym_nms_workspace_bytes(ctypes.byref(ncfg)))
+    assert ws_bytes == int(hip.lib().ym_greedy_nms_batch_workspace_bytes(ctypes.byref(ncfg), 1))
     return fns, ws_bytes, int(want[0].numel())
 
 
 def write_table(path, result, argv):
-    lines = ['# Batched greedy NMS (`--traditional_nms`) against the single-image entry, 544 px', '',
+    lines = ['# Greedy NMS (`--traditional_nms`) through `nms()` and `nms_batch`, 544 px', '',
              f'`{argv}` on one MI355X.  One process; per input the variants are alternated {result["rounds"]} times after '
              f'{result["warmup"]} warm-up calls each; a window holds as many calls as fill {result["window_ms"]:g} ms (at least '
              f'{result["iters"]}); HIP-event time per call around the window, median with (min–max) of the windows.  `nms_greedy` is '
-             '`nms()` with `cfg.traditional_nms` (the single-image entry `ym_detect_greedy_nms` plus its host read of the count; this '
-             'code is the parent commit\'s, untouched), `entry_greedy` the same entry without the host read, `batch_greedy_b*` '
-             '`nms_batch` with the flag (`ym_detect_greedy_nms_batch`) on 1 and 8 images, `batch_fast_b*` `nms_batch` without it.  '
+             '`nms()` with `cfg.traditional_nms` (the single-image entry `ym_detect_greedy_nms`, a batch of one, plus its host read of '
+             'the count), `batch_greedy_b*` `nms_batch` with the flag (`ym_detect_greedy_nms_batch`) on 1 and 8 images, `batch_fast_b*` '
+             '`nms_batch` without it.  '
              'The batched results were compared with `nms()`\'s bit for bit before timing.', '']
-    ws = result['workspace_bytes_per_image']
-    lines += [f'Workspace per image (N = 18525, C = 81): `ym_detect_greedy_nms` {ws["ym_detect_greedy_nms"]} bytes, '
-              f'`ym_detect_greedy_nms_batch` {ws["ym_detect_greedy_nms_batch"]} bytes.', '']
+    lines += [f'Workspace per image (N = 18525, C = 81), either greedy entry: {result["workspace_bytes_per_image"]} bytes.', '']
     for name, case in result['cases'].items():
         lines += [f'### {name} ({case["detections"]} detections)', '', '| variant | ms per call (min–max) | ms per image | calls per window |',
                   '|---|---|---|---|']
@@ -106,12 +91,8 @@ def write_table(path, result, argv):
             lo, hi = case['spread'][v]
             lines.append(f'| {v} | {case["median"][v]:.4f} ({lo:.4f}–{hi:.4f}) | {case["median"][v] / imgs:.4f} | {case["calls_per_window"][v]} |')
         r = case['ratios']
-        lines += ['', f'nms_greedy / batch_greedy_b1 = {r["nms_greedy_over_batch_b1"]:.2f}, entry_greedy / batch_greedy_b1 = '
-                      f'{r["entry_greedy_over_batch_b1"]:.2f}, batch_greedy_b8 per image = {r["batch_b8_ms_per_image"]:.4f} ms.', '']
-    acc = result['acceptance']
-    lines += [f'Acceptance (dense544, one image): slowest batch_greedy_b1 window {acc["slowest_new_ms"]:.4f} ms against fastest nms_greedy '
-              f'window {acc["fastest_old_ms"]:.4f} ms (fastest entry_greedy window {acc["fastest_old_entry_ms"]:.4f} ms): '
-              f'**{"met" if acc["met"] else "NOT met"}**.', '']
+        lines += ['', f'nms_greedy / batch_greedy_b1 = {r["nms_greedy_over_batch_b1"]:.2f}, batch_greedy_b8 per image = '
+                      f'{r["batch_b8_ms_per_image"]:.4f} ms.', '']
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, 'w') as f:
         f.write('\n'.join(lines))
@@ -123,7 +104,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--window-ms', type=float, default=150.0)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'greedy_nms_batch_544.md'))
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'greedy_nms_544.md'))
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'greedy_nms_bench measures on the GPU; there is nothing to measure without one'
     gc.disable()
@@ -147,17 +128,10 @@ def main():
         result['cases'][name] = dict(detections=n_det, rows=rows, calls_per_window=iters, median=med,
                                      spread={v: [min(r), max(r)] for v, r in rows.items()},
                                      ratios={'nms_greedy_over_batch_b1': med['nms_greedy'] / med['batch_greedy_b1'],
-                                             'entry_greedy_over_batch_b1': med['entry_greedy'] / med['batch_greedy_b1'],
                                              'batch_b8_ms_per_image': med['batch_greedy_b8'] / 8})
-    dense = result['cases']['dense544']['rows']
-    result['acceptance'] = {'slowest_new_ms': max(dense['batch_greedy_b1']), 'fastest_old_ms': min(dense['nms_greedy']),
-                            'fastest_old_entry_ms': min(dense['entry_greedy']),
-                            'met': max(dense['batch_greedy_b1']) < min(dense['nms_greedy'])}
     argv = 'python tools/greedy_nms_bench.py' + ''.join(f' --{k.replace("_", "-")} {getattr(args, k):g}' for k in ('iters', 'rounds', 'window_ms', 'warmup'))
     write_table(args.out, result, argv)
     print(json.dumps(result))
-    if not result['acceptance']['met']:
-        sys.exit('acceptance NOT met: the slowest batched window is not below the fastest single-image window')
 
 
 if __name__ == '__main__':

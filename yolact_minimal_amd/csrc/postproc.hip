@@ -718,168 +718,13 @@ __global__ __launch_bounds__(NT) void k_final_select(const NmsWs w0, int ncls, i
 }
 
 // ---------------------------------------------------------------------------------------------------
-// greedy NMS (cython_nms.pyx:24-74): rank by counting -> sorted order -> sequential suppression
+// greedy NMS (cython_nms.pyx:24-74): rank by counting -> sorted order -> suppression in chunks of 64 sorted candidates
 // ---------------------------------------------------------------------------------------------------
 // order: score descending, ties by HIGHER index first (argsort()[::-1] of a stable ascending sort).
 __device__ __forceinline__ bool greedy_before(float sa, int ia, float sb, int ib) {
     return sa > sb || (sa == sb && ia > ib);
 }
 
-// One block handles one list of n detections given as (box[4], score) with element accessor lambdas.
-// sorted_box/sorted_id/alive are global scratch of n entries each.
-template <typename BoxAt, typename ScoreAt>
-__device__ void block_greedy_nms(BoxAt box_at, ScoreAt score_at, int n, float thresh, float scale,
-                                 float* sorted_box, int* sorted_id, uint8_t* alive) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    for (int i = tid; i < n; i += nt) {
-        const float s = score_at(i);
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += greedy_before(score_at(j), j, s, i) ? 1 : 0;
-        const f32x4 b = box_at(i);
-        f32x4 sb = {b[0] * scale, b[1] * scale, b[2] * scale, b[3] * scale};
-        *reinterpret_cast<f32x4*>(sorted_box + (size_t)rank * 4) = sb;
-        sorted_id[rank] = i;
-        alive[rank] = 1;
-    }
-    __syncthreads();
-    for (int a = 0; a < n; ++a) {
-        if (alive[a]) {   // uniform: written before the previous barrier
-            const f32x4 bi = *reinterpret_cast<const f32x4*>(sorted_box + (size_t)a * 4);
-            const float iarea = (bi[2] - bi[0] + 1.f) * (bi[3] - bi[1] + 1.f);
-            for (int b = a + 1 + tid; b < n; b += nt) {
-                if (!alive[b]) continue;
-                const f32x4 bj = *reinterpret_cast<const f32x4*>(sorted_box + (size_t)b * 4);
-                const float xx1 = fmaxf(bi[0], bj[0]), yy1 = fmaxf(bi[1], bj[1]);
-                const float xx2 = fminf(bi[2], bj[2]), yy2 = fminf(bi[3], bj[3]);
-                float ww = xx2 - xx1 + 1.f, hh = yy2 - yy1 + 1.f;
-                ww = ww >= 0.f ? ww : 0.f;
-                hh = hh >= 0.f ? hh : 0.f;
-                const float inter = ww * hh;
-                const float jarea = (bj[2] - bj[0] + 1.f) * (bj[3] - bj[1] + 1.f);
-                const float ovr = __fdiv_rn(inter, (iarea + jarea) - inter);
-                if (ovr >= thresh) alive[b] = 0;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(NT) void k_greedy_standalone(const float* __restrict__ dets, int n, float thresh,
-                                                           uint8_t* __restrict__ keep_mask, int32_t* __restrict__ out_count,
-                                                           float* sorted_box, int* sorted_id, uint8_t* alive) {
-    __shared__ int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    block_greedy_nms(
-        [&](int i) { const float* d = dets + (size_t)i * 5; return f32x4{d[0], d[1], d[2], d[3]}; },
-        [&](int i) { return dets[(size_t)i * 5 + 4]; }, n, thresh, 1.f, sorted_box, sorted_id, alive);
-    for (int r = threadIdx.x; r < n; r += NT) {
-        keep_mask[sorted_id[r]] = alive[r];
-        if (alive[r]) atomicAdd(&cnt, 1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && out_count) out_count[0] = cnt;
-}
-
-// per class: candidates = kept anchors with score[c] > thre (utils/output_utils.py:93-109)
-struct GreedyWs {
-    int* cand;          // [C-1][N] compacted-list indices of the class candidates (ascending)
-    int* cand_cnt;      // [C-1]
-    float* sorted_box;  // [C-1][N][4]
-    int* sorted_id;     // [C-1][N]
-    uint8_t* alive;     // [C-1][N]
-    uint8_t* kept;      // [C-1][N] kept flag by candidate position (ascending index order)
-};
-
-__global__ __launch_bounds__(NT) void k_greedy_per_class(const NmsWs w, const GreedyWs g, int N, float score_thre,
-                                                          float iou_thre, float img_size) {
-    __shared__ int wave_tot[NT / 64];
-    __shared__ int running;
-    const int K = w.counters[0];
-    if (K == 0) return;
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float* srow = w.scores_t + (size_t)c * N;
-    int* cand = g.cand + (size_t)c * N;
-    if (tid == 0) running = 0;
-    __syncthreads();
-    for (int base = 0; base < K; base += NT) {
-        const int i = base + tid;
-        const bool f = i < K && srow[i] > score_thre;
-        const unsigned long long bal = __ballot(f);
-        const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_tot[wv] = __popcll(bal);
-        __syncthreads();
-        int off = running;
-        for (int x = 0; x < wv; ++x) off += wave_tot[x];
-        if (f) cand[off + pre] = i;
-        __syncthreads();
-        if (tid == 0) { int t = 0; for (int x = 0; x < NT / 64; ++x) t += wave_tot[x]; running += t; }
-        __syncthreads();
-    }
-    const int n = running;
-    if (tid == 0) g.cand_cnt[c] = n;
-    if (n == 0) return;
-    float* sbox = g.sorted_box + (size_t)c * N * 4;
-    int* sid = g.sorted_id + (size_t)c * N;
-    uint8_t* alive = g.alive + (size_t)c * N;
-    block_greedy_nms(
-        [&](int i) { return *reinterpret_cast<const f32x4*>(w.boxes_k + (size_t)cand[i] * 4); },
-        [&](int i) { return srow[cand[i]]; }, n, iou_thre, img_size, sbox, sid, alive);
-    uint8_t* kept = g.kept + (size_t)c * N;
-    for (int r = tid; r < n; r += NT) kept[sid[r]] = alive[r];
-}
-
-// global top max_det over all kept (class, candidate) pairs; flat order = class-major, ascending index
-// inside a class (torch.cat of idx[keep] with keep ascending, utils/output_utils.py:107-115).
-__global__ __launch_bounds__(NT) void k_greedy_final(const NmsWs w, const GreedyWs g, int N, int ncls, int max_det,
-                                                     float img_size, const float* __restrict__ coef, int coef_dim,
-                                                     int32_t* __restrict__ out_count, int64_t* __restrict__ out_ids,
-                                                     float* __restrict__ out_scores, float* __restrict__ out_boxes,
-                                                     float* __restrict__ out_coefs) {
-    __shared__ TopkShared<DET_CAP> sh;
-    __shared__ int n_valid;
-    const int tid = threadIdx.x;
-    const int K = w.counters[0];
-    if (K == 0) {
-        if (tid == 0) out_count[0] = 0;
-        return;
-    }
-    const long long Lfull = (long long)ncls * N;
-    const int L = (int)Lfull;
-    auto key_at = [&](int f) -> uint32_t {
-        const int c = f / N, p = f - c * N;
-        if (p < g.cand_cnt[c] && g.kept[f]) return f2key(w.scores_t[(size_t)c * N + g.cand[f]]);
-        return 0u;
-    };
-    block_topk_sorted<DET_CAP>(key_at, L, max_det, sh);
-    if (tid == 0) n_valid = 0;
-    __syncthreads();
-    if (tid < max_det && sh.keys[tid] != 0u) atomicAdd(&n_valid, 1);
-    __syncthreads();
-    const int n = n_valid;
-    if (tid == 0) out_count[0] = n;
-    for (int j = tid; j < n; j += NT) {
-        const int f = sh.idx[j];
-        const int c = f / N;
-        const int k = g.cand[f];
-        out_ids[j] = c;
-        out_scores[j] = key2f(sh.keys[j]);
-        // boxes[idx] / img_size of boxes * img_size (utils/output_utils.py:90,123)
-        const f32x4 b = *reinterpret_cast<const f32x4*>(w.boxes_k + (size_t)k * 4);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = __fdiv_rn(b[e] * img_size, img_size);
-        *reinterpret_cast<f32x4*>(out_boxes + j * 4) = o;
-    }
-    for (int e = tid; e < n * coef_dim; e += NT) {
-        const int j = e / coef_dim, d = e - j * coef_dim;
-        const int a = w.keep_idx[g.cand[sh.idx[j]]];
-        out_coefs[e] = coef[(size_t)a * coef_dim + d];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// batched greedy NMS (ym_detect_greedy_nms_batch): grid row = image, suppression in chunks of 64 sorted candidates
-// ---------------------------------------------------------------------------------------------------
 // The sequential definition (a candidate is dropped iff an earlier KEPT candidate overlaps it) needs one step per candidate only
 // INSIDE a window where keeps are still undecided.  So: one wave settles 64 consecutive sorted candidates among themselves (the
 // alive bits are a ballot, the current box a readlane: no barrier), then the whole workgroup tests every later candidate against
@@ -910,6 +755,11 @@ size_t carve_greedy_batch(void* base, int N, int C, GreedyBatchWs* g) {
     return off;
 }
 
+// per image: the stage-A workspace, then cand / cand_cnt / kept (+ sorted_id when a class can outgrow the staged form)
+size_t greedy_batch_stride(int N, int C) {
+    return align_up(carve(nullptr, N, C).bytes) + carve_greedy_batch(nullptr, N, C, nullptr);
+}
+
 __device__ __forceinline__ GreedyBatchWs image_gws(const GreedyBatchWs& g, size_t stride, int b) {
     GreedyBatchWs o = g;
     const size_t sh = stride * (size_t)b;
@@ -920,7 +770,8 @@ __device__ __forceinline__ GreedyBatchWs image_gws(const GreedyBatchWs& g, size_
     return o;
 }
 
-// block_greedy_nms's overlap test, operation for operation (bi = the earlier, kept box; iarea its "+1" area)
+// THE overlap rule of cython_nms.pyx:49-72, in its order of operations: "+1" widths and areas, ovr = inter / (iarea + jarea - inter)
+// correctly rounded, suppressed at ovr >= thresh (bi = the earlier, kept box; iarea its "+1" area)
 __device__ __forceinline__ bool greedy_overlaps(const f32x4 bi, float iarea, const f32x4 bj, float thresh) {
     const float xx1 = fmaxf(bi[0], bj[0]), yy1 = fmaxf(bi[1], bj[1]);
     const float xx2 = fminf(bi[2], bj[2]), yy2 = fminf(bi[3], bj[3]);
@@ -1070,9 +921,38 @@ __global__ __launch_bounds__(NT) void k_greedy_per_class_batch(const NmsWs w0, c
                            n, iou_thre, s_surv);
 }
 
-// grid (1, B): global top max_det over the kept (class, candidate) pairs of one image, k_greedy_final's order (score descending,
-// ties in flat class-major, ascending-index order).  The flat list is the classes' candidate lists back to back (their counts'
-// prefix sums in LDS), not (C-1) x N slots: the select reads what exists.
+// ym_greedy_nms: one list of (box, score) rows in one workgroup.  What it does is the global-scratch form above, but its workspace
+// layout is the caller's contract (boxes scattered BY RANK, then ids, then alive flags by rank) while that form reads the boxes
+// through the order and flags `kept` by candidate position: the two share greedy_before, greedy_overlaps and greedy_suppress_chunks
+// and differ only in the accessors they hand to the last.
+__global__ __launch_bounds__(NT) void k_greedy_standalone(const float* __restrict__ dets, int n, float thresh,
+                                                           uint8_t* __restrict__ keep_mask, int32_t* __restrict__ out_count,
+                                                           f32x4* sorted_box, int* sorted_id, uint8_t* alive) {
+    __shared__ unsigned long long s_surv;
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    for (int i = threadIdx.x; i < n; i += NT) {
+        const float* d = dets + (size_t)i * 5;
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += greedy_before(dets[(size_t)j * 5 + 4], j, d[4], i) ? 1 : 0;
+        sorted_box[rank] = f32x4{d[0], d[1], d[2], d[3]};
+        sorted_id[rank] = i;
+        alive[rank] = 1;
+    }
+    __syncthreads();
+    greedy_suppress_chunks([&](int r) { return sorted_box[r]; }, [&](int r) { return alive[r] != 0; }, [&](int r) { alive[r] = 0; },
+                           n, thresh, &s_surv);
+    for (int r = threadIdx.x; r < n; r += NT) {
+        keep_mask[sorted_id[r]] = alive[r];
+        if (alive[r]) atomicAdd(&cnt, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && out_count) out_count[0] = cnt;
+}
+
+// grid (1, B): global top max_det over the kept (class, candidate) pairs of one image: score descending, ties in flat class-major,
+// ascending-index order (torch.cat of idx[keep] with keep ascending, utils/output_utils.py:107-115).  The flat list is the classes'
+// candidate lists back to back (their counts' prefix sums in LDS), not (C-1) x N slots: the select reads what exists.
 __global__ __launch_bounds__(NT) void k_greedy_final_batch(const NmsWs w0, const GreedyBatchWs g0, int N, int ncls, int max_det,
                                                            float img_size, const FinalOut o0, size_t ws_stride) {
     const NmsWs w = image_ws(w0, ws_stride, blockIdx.y);
@@ -1134,25 +1014,6 @@ __global__ __launch_bounds__(NT) void k_greedy_final_batch(const NmsWs w0, const
     }
 }
 
-size_t greedy_extra_bytes(int N, int C) {
-    const size_t cn = (size_t)(C - 1) * N;
-    return align_up(cn * 4) + align_up((size_t)(C - 1) * 4) + align_up(cn * 16) + align_up(cn * 4) + align_up(cn) + align_up(cn);
-}
-
-GreedyWs carve_greedy(void* base, int N, int C) {
-    GreedyWs g;
-    size_t off = 0;
-    const size_t cn = (size_t)(C - 1) * N;
-    auto take = [&](size_t bytes) { char* p = (char*)base + off; off += align_up(bytes); return (void*)p; };
-    g.cand = (int*)take(cn * 4);
-    g.cand_cnt = (int*)take((size_t)(C - 1) * 4);
-    g.sorted_box = (float*)take(cn * 16);
-    g.sorted_id = (int*)take(cn * 4);
-    g.alive = (uint8_t*)take(cn);
-    g.kept = (uint8_t*)take(cn);
-    return g;
-}
-
 int check_cfg(const ym_nms_cfg* cfg) {
     YM_REQUIRE(cfg, "nms: null cfg");
     YM_REQUIRE(cfg->num_anchors > 0 && cfg->num_classes >= 2 && cfg->num_classes <= 256, "nms: bad N/C");
@@ -1177,8 +1038,8 @@ int run_stage_a(const float* cls, const float* box, const float* anchors, const 
 
 extern "C" size_t ym_nms_workspace_bytes(const ym_nms_cfg* cfg) {
     if (check_cfg(cfg) != YM_OK) return 0;
-    NmsWs w = carve(nullptr, cfg->num_anchors, cfg->num_classes);
-    return w.bytes + greedy_extra_bytes(cfg->num_anchors, cfg->num_classes);
+    // one size for both single-image entries: the fast path's bytes or the greedy batch of one, whichever is larger
+    return std::max(carve(nullptr, cfg->num_anchors, cfg->num_classes).bytes, greedy_batch_stride(cfg->num_anchors, cfg->num_classes));
 }
 
 extern "C" size_t ym_nms_batch_workspace_bytes(const ym_nms_cfg* cfg, int B) {
@@ -1228,34 +1089,6 @@ extern "C" int ym_detect_fast_nms(const float* class_pred, const float* box_pred
                                     out_coefs, workspace, workspace_bytes, s);
 }
 
-extern "C" int ym_detect_greedy_nms(const float* class_pred, const float* box_pred, const float* coef_pred,
-                                    const float* anchors, const ym_nms_cfg* cfg, int32_t* out_count, int64_t* out_ids,
-                                    float* out_scores, float* out_boxes, float* out_coefs, void* workspace,
-                                    size_t workspace_bytes, ym_stream_t s) {
-    int rc = check_cfg(cfg);
-    if (rc != YM_OK) return rc;
-    YM_REQUIRE(class_pred && box_pred && coef_pred && anchors && out_count && out_ids && out_scores && out_boxes &&
-                   out_coefs && workspace, "greedy_nms: null pointer");
-    const int N = cfg->num_anchors, C = cfg->num_classes;
-    NmsWs w = carve(workspace, N, C);
-    const size_t need = w.bytes + greedy_extra_bytes(N, C);
-    if (need > workspace_bytes) { ym_set_error("greedy_nms: workspace %zu < %zu", workspace_bytes, need); return YM_ENOSPC; }
-    GreedyWs g = carve_greedy((char*)workspace + w.bytes, N, C);
-    hipStream_t st = (hipStream_t)s;
-    rc = run_stage_a(class_pred, box_pred, anchors, cfg, w, st);
-    if (rc != YM_OK) return rc;
-    hipLaunchKernelGGL(k_greedy_per_class, dim3(C - 1), dim3(NT), 0, st, w, g, N, cfg->score_thre, cfg->iou_thre,
-                       cfg->img_size);
-    hipLaunchKernelGGL(k_greedy_final, dim3(1), dim3(NT), 0, st, w, g, N, C - 1, cfg->max_det, cfg->img_size, coef_pred,
-                       cfg->coef_dim, out_count, out_ids, out_scores, out_boxes, out_coefs);
-    return ym_check_launch("greedy_nms");
-}
-
-// per image: the stage-A workspace, then cand / cand_cnt / kept (+ sorted_id when a class can outgrow the staged form)
-static size_t greedy_batch_stride(int N, int C) {
-    return align_up(carve(nullptr, N, C).bytes) + carve_greedy_batch(nullptr, N, C, nullptr);
-}
-
 extern "C" size_t ym_greedy_nms_batch_workspace_bytes(const ym_nms_cfg* cfg, int B) {
     if (check_cfg(cfg) != YM_OK || B < 1) return 0;
     return greedy_batch_stride(cfg->num_anchors, cfg->num_classes) * (size_t)B;
@@ -1293,6 +1126,14 @@ extern "C" int ym_detect_greedy_nms_batch(const float* class_pred, const float* 
     return ym_check_launch("greedy_nms_batch");
 }
 
+extern "C" int ym_detect_greedy_nms(const float* class_pred, const float* box_pred, const float* coef_pred,
+                                    const float* anchors, const ym_nms_cfg* cfg, int32_t* out_count, int64_t* out_ids,
+                                    float* out_scores, float* out_boxes, float* out_coefs, void* workspace,
+                                    size_t workspace_bytes, ym_stream_t s) {
+    return ym_detect_greedy_nms_batch(class_pred, box_pred, coef_pred, anchors, cfg, 1, out_count, out_ids, out_scores, out_boxes,
+                                      out_coefs, workspace, workspace_bytes, s);
+}
+
 extern "C" int ym_expf_cr(const float* x, float* y, int64_t n, ym_stream_t s) {
     YM_REQUIRE(n >= 0 && (n == 0 || (x && y)), "expf_cr: bad arguments");
     if (n == 0) return YM_OK;
@@ -1317,7 +1158,7 @@ extern "C" int ym_greedy_nms(const float* dets, int n, float thresh, uint8_t* ke
     YM_REQUIRE(dets && keep_mask && workspace, "greedy_nms: null pointer");
     if (ym_greedy_nms_workspace_bytes(n) > workspace_bytes) { ym_set_error("greedy_nms: workspace too small"); return YM_ENOSPC; }
     char* p = (char*)workspace;
-    float* sorted_box = (float*)p; p += align_up((size_t)n * 16);
+    f32x4* sorted_box = (f32x4*)p; p += align_up((size_t)n * 16);
     int* sorted_id = (int*)p; p += align_up((size_t)n * 4);
     uint8_t* alive = (uint8_t*)p;
     hipLaunchKernelGGL(k_greedy_standalone, dim3(1), dim3(NT), 0, (hipStream_t)s, dets, n, thresh, keep_mask, out_count,

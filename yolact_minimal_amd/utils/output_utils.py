@@ -184,7 +184,7 @@ class BatchDetections:
 
 def nms_batch(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
     """`nms` for a whole batch [B, N, *] in one launch set, no host synchronisation: fast_nms, or with `cfg.traditional_nms` the
-    greedy per-class path (`ym_detect_greedy_nms_batch`).  Per image the result equals `nms(class_pred[b:b+1], ...)`
+    greedy per-class path (`ym_detect_greedy_nms_batch`; `nms()` runs it as a batch of one).  Per image the result equals `nms(class_pred[b:b+1], ...)`
     (tests/test_gpu_postproc.py::test_batched_postprocessing_equals_per_image, tests/test_gpu_greedy_batch.py)."""
     if not class_pred.is_cuda:
         raise RuntimeError('yolact_minimal_amd.utils.output_utils.nms_batch needs CUDA (HIP) tensors; there is no CPU path.')
