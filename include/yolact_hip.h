@@ -657,6 +657,36 @@ int ym_after_nms_batch_packed(const float* proto, const float* coefs, float* box
 /* dense masks [n][H][W] (float32, or uint8 when is_u8; nonzero = foreground) -> bits, and bits -> float32 0.0 / 1.0. */
 int ym_pack_masks(const void* masks, int is_u8, int n, int H, int W, uint64_t* bits, ym_stream_t s);
 int ym_unpack_masks(const uint64_t* bits, int n, int H, int W, float* masks, ym_stream_t s);
+
+/* ---- after_nms for a batch whose images differ in size ------------------------------------------------------------------------
+ * ym_after_nms_ragged[_packed]: ym_after_nms_batch[_packed] with img_h, img_w replaced by a HOST table of B entries, one per image:
+ * its output size and `offset`, the first element (float, or 64-bit word when packed) of its mask block in `masks`.  Image b's block
+ * is [max_det][img_h_b][img_w_b] floats (packed: [max_det][img_h_b][ceil(img_w_b / 64)] words) at masks + offset_b: exactly what the
+ * uniform entry writes for a batch of that one size, so every consumer of one image's padded rows takes the block as it is.  Rows
+ * at or past counts[b] are NOT written, and nothing outside the blocks is.  boxes are scaled in place and boxes_px written with
+ * S_b = max(img_h_b, img_w_b) per image.
+ *   The table is read during the call and travels to the kernels by value in their arguments: no copy to the device, no
+ * synchronisation, nothing to keep alive afterwards.  B <= YM_RAGGED_MAX_IMAGES.  Every block starts at a multiple of
+ * YM_RAGGED_ALIGN_BYTES bytes from `masks` (the dense kernel stores 16 bytes at a time when img_w % 4 == 0, and an odd max_det x odd
+ * height x odd width would leave the next block misaligned), `masks` itself is 16-byte aligned, blocks do not overlap: YM_EINVAL
+ * otherwise.  One fused launch covers every image whose scale fits the fused kernel (grid = largest tile count x max_det x B; tiles
+ * and slots an image does not have exit at once); images much smaller than the prototype map (max(h, w) under about 2.7x its side)
+ * take the uniform entry's two-kernel path one by one through `workspace` >= ym_after_nms_ragged_workspace_bytes(...) (0 when every
+ * image fits; also 0 for arguments the entries would refuse). */
+#define YM_RAGGED_MAX_IMAGES 32
+#define YM_RAGGED_ALIGN_BYTES 256
+typedef struct ym_ragged_image {
+    int32_t img_h, img_w;
+    int64_t offset; /* elements from `masks` to this image's block */
+} ym_ragged_image;
+size_t ym_after_nms_ragged_workspace_bytes(const ym_ragged_image* images, int B, int max_det, int Hp, int Wp);
+int ym_after_nms_ragged(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
+                        int Wp, int K, const ym_ragged_image* images, int do_crop, float* masks, int32_t* boxes_px, void* workspace,
+                        size_t workspace_bytes, ym_stream_t s);
+int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
+                               int Wp, int K, const ym_ragged_image* images, int do_crop, uint64_t* mask_bits, int32_t* boxes_px,
+                               void* workspace, size_t workspace_bytes, ym_stream_t s);
+
 /* ym_mask_iou on bit rows: bits_a [n][words], bits_b [g][words], words = H * Wq < 2^18.  Exact integers through the same
  * finalize step, so bit-identical to ym_mask_iou on the dense masks (0/0 -> NaN). */
 size_t ym_mask_iou_packed_workspace_bytes(int n, int g, int64_t words);

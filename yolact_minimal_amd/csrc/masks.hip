@@ -83,8 +83,9 @@ __device__ __forceinline__ void src_coord(int dst, float scale, int in_sz, int& 
     l1 = src - (float)i0;
 }
 
-__global__ __launch_bounds__(256) void k_mask_resize(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h,
-                                                      int img_w, float* __restrict__ out) {
+// (the body of k_mask_resize and of k_mask_resize_counted, whose n is the image's count on the device)
+__device__ __forceinline__ void resize_rows(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
+                                            float* __restrict__ out) {
     const int S = img_h > img_w ? img_h : img_w;
     const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
     const int wq = (img_w + 3) >> 2;
@@ -121,6 +122,23 @@ __global__ __launch_bounds__(256) void k_mask_resize(const float* __restrict__ m
     }
 }
 
+__global__ __launch_bounds__(256) void k_mask_resize(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h,
+                                                      int img_w, float* __restrict__ out) {
+    resize_rows(masks, n, Hp, Wp, img_h, img_w, out);
+}
+
+__device__ __forceinline__ int clamped_count(const int32_t* count, int max_det) {
+    const int n = *count;
+    return n < 0 ? 0 : (n > max_det ? max_det : n);
+}
+
+// the ragged entry's fallback: rows at or past the image's count are not written
+__global__ __launch_bounds__(256) void k_mask_resize_counted(const float* __restrict__ masks, const int32_t* __restrict__ count,
+                                                              int max_det, int Hp, int Wp, int img_h, int img_w,
+                                                              float* __restrict__ out) {
+    resize_rows(masks, clamped_count(count, max_det), Hp, Wp, img_h, img_w, out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // after_nms in ONE launch for a batch of images: assemble (coef x prototype, sigmoid, crop) -> bilinear resize to S x S ->
 // > 0.5 -> slice to img_h x img_w  (utils/output_utils.py:217-228), without the [n][Hp][Wp] soft masks ever reaching HBM.
@@ -135,26 +153,27 @@ __global__ __launch_bounds__(256) void k_mask_resize(const float* __restrict__ m
 constexpr int FT_W = 256, FT_H = 16;          // output tile: 64 lanes x float4 wide, 4 waves x 4 rows high
 constexpr int FP_W = 96, FP_H = 10;           // source patch capacity (floats): checked on the host against the scale
 
-__global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ proto, const float* __restrict__ coefs,
-                                                      const float* __restrict__ boxes, const int32_t* __restrict__ counts,
-                                                      int max_det, int Hp, int Wp, int img_h, int img_w, int do_crop,
-                                                      float* __restrict__ out) {
-    __shared__ float patch[FP_H * FP_W];
-    __shared__ __attribute__((aligned(16))) float cf[32];
-    const int b = blockIdx.z, d = blockIdx.y;
-    const int n = counts ? counts[b] : max_det;
-    if (d >= n) return;
+template <bool PACKED> struct mask_elem { typedef float type; };
+template <> struct mask_elem<true> { typedef unsigned long long type; };
+
+// One FT_H x FT_W output tile of ONE detection: the body of the uniform kernels and of the ragged one.  `pimg` is the image's
+// prototype map, `coef` / `box` the detection's 32 coefficients / 4 box floats, `obase` the detection's mask ([img_h][img_w] floats or
+// [img_h][wq] words), `patch` / `cf` the workgroup's LDS.  PACKED only changes the lane -> pixel map and the store (below).
+template <bool PACKED>
+__device__ __forceinline__ void fused_tile(float* patch, float* cf, const float* __restrict__ pimg, const float* __restrict__ coef,
+                                           const float* __restrict__ box, int tile, int Hp, int Wp, int img_h, int img_w, int do_crop,
+                                           typename mask_elem<PACKED>::type* __restrict__ obase) {
+    static_assert(FT_W == 256 && FT_H == 16, "4 words x (4 waves x 4 rows) per tile");
     const int tiles_x = (img_w + FT_W - 1) / FT_W;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int oy0 = ty * FT_H, ox0 = tx * FT_W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int S = img_h > img_w ? img_h : img_w;
     const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
-    const size_t slot = (size_t)b * max_det + d;
 
     float x1 = 0.f, x2 = (float)Wp, y1 = 0.f, y2 = (float)Hp;
     if (do_crop) {
-        const f32x4 bx = *reinterpret_cast<const f32x4*>(boxes + slot * 4);
+        const f32x4 bx = *reinterpret_cast<const f32x4*>(box);
         crop_span(bx[0], bx[2], (float)Wp, x1, x2);
         crop_span(bx[1], bx[3], (float)Hp, y1, y2);
     }
@@ -168,24 +187,31 @@ __global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ p
     const int ph = py1 - py0 + 1, pw = px1 - px0 + 1;
     // any source pixel of the patch inside the crop window [x1,x2) x [y1,y2)?  (float compares like the reference's crop)
     const bool active = (float)px1 >= x1 && (float)px0 < x2 && (float)py1 >= y1 && (float)py0 < y2;
-    float* obase = out + slot * (size_t)img_h * img_w;
+    // dense: a lane owns 4 consecutive pixels of its wave's four rows
     const bool vec = (img_w & 3) == 0;
     const int x = ox0 + lane * 4;
+    // packed: lane k < 16 stores word (k & 3) of row (k >> 2) of this wave's four rows
+    const int wq = (img_w + 63) >> 6;
+    const int my_y = oy0 + wave * (FT_H / 4) + (lane >> 2), my_j = (ox0 >> 6) + (lane & 3);
+    const bool stores = lane < 16 && my_y < img_h && my_j < wq;
     if (!active) {
+        if constexpr (PACKED) {
+            if (stores) obase[(size_t)my_y * wq + my_j] = 0ull;
+        } else {
 #pragma unroll
-        for (int r = 0; r < FT_H / 4; ++r) {
-            const int y = oy0 + wave * (FT_H / 4) + r;
-            if (y >= img_h || x >= img_w) continue;
-            float* dst = obase + (size_t)y * img_w + x;
-            if (vec) *reinterpret_cast<f32x4*>(dst) = f32x4{0.f, 0.f, 0.f, 0.f};
-            else
-                for (int e = 0; e < 4 && x + e < img_w; ++e) dst[e] = 0.f;
+            for (int r = 0; r < FT_H / 4; ++r) {
+                const int y = oy0 + wave * (FT_H / 4) + r;
+                if (y >= img_h || x >= img_w) continue;
+                float* dst = obase + (size_t)y * img_w + x;
+                if (vec) *reinterpret_cast<f32x4*>(dst) = f32x4{0.f, 0.f, 0.f, 0.f};
+                else
+                    for (int e = 0; e < 4 && x + e < img_w; ++e) dst[e] = 0.f;
+            }
         }
         return;
     }
-    if (tid < 32) cf[tid] = coefs[slot * 32 + tid];
+    if (tid < 32) cf[tid] = coef[tid];
     __syncthreads();
-    const float* pimg = proto + (size_t)b * Hp * Wp * 32;
     for (int i = tid; i < ph * pw; i += 256) {
         const int r = i / pw, c = i - r * pw;
         const int py = py0 + r, px = px0 + c;
@@ -208,133 +234,117 @@ __global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ p
         patch[r * FP_W + c] = v;
     }
     __syncthreads();
+    [[maybe_unused]] unsigned long long mine = 0ull;
 #pragma unroll
     for (int r = 0; r < FT_H / 4; ++r) {
         const int y = oy0 + wave * (FT_H / 4) + r;
-        if (y >= img_h || x >= img_w) continue;
+        if (y >= img_h) continue;                                // (wave-uniform: rows past the image own no patch rows)
+        if (!PACKED && x >= img_w) continue;
         int y0, y1i; float ly;
         src_coord(y, sy, Hp, y0, y1i, ly);
         const float hy = 1.f - ly;
         const float* r0 = patch + (y0 - py0) * FP_W - px0;
         const float* r1 = patch + (y1i - py0) * FP_W - px0;
-        float o[4];
+        if constexpr (PACKED) {
+            // a lane owns pixels ox0 + 64e + lane: one ballot per (row, e) IS one word, lane r * 4 + e keeps it
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            int x0, x1i; float lx;
-            src_coord(x + e < img_w ? x + e : img_w - 1, sx, Wp, x0, x1i, lx);
-            const float hx = 1.f - lx;
-            const float v = hy * (hx * r0[x0] + lx * r0[x1i]) + ly * (hx * r1[x0] + lx * r1[x1i]);
-            o[e] = v > 0.5f ? 1.f : 0.f;
+            for (int e = 0; e < 4; ++e) {
+                if (ox0 + 64 * e >= img_w) continue;             // (wave-uniform: this word does not exist)
+                const int xe = ox0 + 64 * e + lane;
+                int x0, x1i; float lx;
+                src_coord(xe < img_w ? xe : img_w - 1, sx, Wp, x0, x1i, lx);
+                const float hx = 1.f - lx;
+                const float v = hy * (hx * r0[x0] + lx * r0[x1i]) + ly * (hx * r1[x0] + lx * r1[x1i]);
+                const unsigned long long w = __ballot(xe < img_w && v > 0.5f);
+                mine = lane == r * 4 + e ? w : mine;
+            }
+        } else {
+            float o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                int x0, x1i; float lx;
+                src_coord(x + e < img_w ? x + e : img_w - 1, sx, Wp, x0, x1i, lx);
+                const float hx = 1.f - lx;
+                const float v = hy * (hx * r0[x0] + lx * r0[x1i]) + ly * (hx * r1[x0] + lx * r1[x1i]);
+                o[e] = v > 0.5f ? 1.f : 0.f;
+            }
+            float* dst = obase + (size_t)y * img_w + x;
+            if (vec) *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
+            else
+                for (int e = 0; e < 4 && x + e < img_w; ++e) dst[e] = o[e];
         }
-        float* dst = obase + (size_t)y * img_w + x;
-        if (vec) *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
-        else
-            for (int e = 0; e < 4 && x + e < img_w; ++e) dst[e] = o[e];
+    }
+    if constexpr (PACKED) {
+        if (stores) obase[(size_t)my_y * wq + my_j] = mine;
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// Bit-packed output (include/yolact_hip.h "bit-packed instance masks"): bits [slot][img_h][wq] uint64, wq = ceil(img_w / 64), bit k
-// of word j of row y = pixel (y, 64j + k), bits at x >= img_w zero.  k_masks_fused_packed is k_masks_fused with another lane ->
-// pixel map and another store: the tile, the LDS patch and every floating-point expression are the dense kernel's, so a bit equals
-// (dense value != 0).  A lane owns pixels ox0 + 64e + lane (e = 0..3) of its wave's four rows: one ballot per (row, e) IS one word,
-// lane k < 16 keeps word k and the wave's 16 words leave as one 8-byte store per lane (four 32-byte row pieces).  A tile outside
-// the crop window stores its 16 x 4 zero words (512 B) and exits; the dense [n][img_h][img_w] tensor exists nowhere.
-// ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_masks_fused_packed(const float* __restrict__ proto, const float* __restrict__ coefs,
-                                                             const float* __restrict__ boxes, const int32_t* __restrict__ counts,
-                                                             int max_det, int Hp, int Wp, int img_h, int img_w, int do_crop,
-                                                             unsigned long long* __restrict__ out) {
-    static_assert(FT_W == 256 && FT_H == 16, "4 words x (4 waves x 4 rows) per tile");
+__global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ proto, const float* __restrict__ coefs,
+                                                      const float* __restrict__ boxes, const int32_t* __restrict__ counts,
+                                                      int max_det, int Hp, int Wp, int img_h, int img_w, int do_crop,
+                                                      float* __restrict__ out) {
     __shared__ float patch[FP_H * FP_W];
     __shared__ __attribute__((aligned(16))) float cf[32];
     const int b = blockIdx.z, d = blockIdx.y;
     const int n = counts ? counts[b] : max_det;
     if (d >= n) return;
-    const int tiles_x = (img_w + FT_W - 1) / FT_W;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int oy0 = ty * FT_H, ox0 = tx * FT_W;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int S = img_h > img_w ? img_h : img_w;
-    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
     const size_t slot = (size_t)b * max_det + d;
+    fused_tile<false>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, img_h, img_w,
+                      do_crop, out + slot * (size_t)img_h * img_w);
+}
 
-    float x1 = 0.f, x2 = (float)Wp, y1 = 0.f, y2 = (float)Hp;
-    if (do_crop) {
-        const f32x4 bx = *reinterpret_cast<const f32x4*>(boxes + slot * 4);
-        crop_span(bx[0], bx[2], (float)Wp, x1, x2);
-        crop_span(bx[1], bx[3], (float)Hp, y1, y2);
-    }
-    int py0, py1, px0, px1, t0, t1; float l;
-    const int oy_last = min(oy0 + FT_H, img_h) - 1, ox_last = min(ox0 + FT_W, img_w) - 1;
-    src_coord(oy0, sy, Hp, py0, t1, l);
-    src_coord(oy_last, sy, Hp, t0, py1, l);
-    src_coord(ox0, sx, Wp, px0, t1, l);
-    src_coord(ox_last, sx, Wp, t0, px1, l);
-    const int ph = py1 - py0 + 1, pw = px1 - px0 + 1;
-    const bool active = (float)px1 >= x1 && (float)px0 < x2 && (float)py1 >= y1 && (float)py0 < y2;
-    const int wq = (img_w + 63) >> 6;
-    // lane k < 16 stores word (k & 3) of row (k >> 2) of this wave's four rows
-    const int my_y = oy0 + wave * (FT_H / 4) + (lane >> 2), my_j = (ox0 >> 6) + (lane & 3);
-    const bool stores = lane < 16 && my_y < img_h && my_j < wq;
-    unsigned long long* dst = out + (slot * (size_t)img_h + my_y) * wq + my_j;
-    if (!active) {
-        if (stores) *dst = 0ull;
-        return;
-    }
-    if (tid < 32) cf[tid] = coefs[slot * 32 + tid];
-    __syncthreads();
-    const float* pimg = proto + (size_t)b * Hp * Wp * 32;
-    for (int i = tid; i < ph * pw; i += 256) {
-        const int r = i / pw, c = i - r * pw;
-        const int py = py0 + r, px = px0 + c;
-        const float fx = (float)px, fy = (float)py;
-        float v = 0.f;
-        if (fx >= x1 && fx < x2 && fy >= y1 && fy < y2) {
-            const f32x4* pr = reinterpret_cast<const f32x4*>(pimg + ((size_t)py * Wp + px) * 32);
-            float acc = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const f32x4 pv = pr[q];
-                const f32x4 cv = *reinterpret_cast<const f32x4*>(cf + q * 4);
-                acc = __builtin_fmaf(cv[0], pv[0], acc);
-                acc = __builtin_fmaf(cv[1], pv[1], acc);
-                acc = __builtin_fmaf(cv[2], pv[2], acc);
-                acc = __builtin_fmaf(cv[3], pv[3], acc);
-            }
-            v = 1.f / (1.f + expf(-acc));
-        }
-        patch[r * FP_W + c] = v;
-    }
-    __syncthreads();
-    unsigned long long mine = 0ull;
-#pragma unroll
-    for (int r = 0; r < FT_H / 4; ++r) {
-        const int y = oy0 + wave * (FT_H / 4) + r;
-        if (y >= img_h) continue;                                // (wave-uniform: rows past the image own no patch rows)
-        int y0, y1i; float ly;
-        src_coord(y, sy, Hp, y0, y1i, ly);
-        const float hy = 1.f - ly;
-        const float* r0 = patch + (y0 - py0) * FP_W - px0;
-        const float* r1 = patch + (y1i - py0) * FP_W - px0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (ox0 + 64 * e >= img_w) continue;                 // (wave-uniform: this word does not exist)
-            const int x = ox0 + 64 * e + lane;
-            int x0, x1i; float lx;
-            src_coord(x < img_w ? x : img_w - 1, sx, Wp, x0, x1i, lx);
-            const float hx = 1.f - lx;
-            const float v = hy * (hx * r0[x0] + lx * r0[x1i]) + ly * (hx * r1[x0] + lx * r1[x1i]);
-            const unsigned long long w = __ballot(x < img_w && v > 0.5f);
-            mine = lane == r * 4 + e ? w : mine;
-        }
-    }
-    if (stores) *dst = mine;
+// ---------------------------------------------------------------------------------------------------------------------------
+// Bit-packed output (include/yolact_hip.h "bit-packed instance masks"): bits [slot][img_h][wq] uint64, wq = ceil(img_w / 64), bit k
+// of word j of row y = pixel (y, 64j + k), bits at x >= img_w zero.  k_masks_fused_packed is k_masks_fused with another lane ->
+// pixel map and another store (fused_tile<true>): the tile, the LDS patch and every floating-point expression are the dense kernel's,
+// so a bit equals (dense value != 0).  A lane owns pixels ox0 + 64e + lane (e = 0..3) of its wave's four rows: one ballot per (row, e)
+// IS one word, lane k < 16 keeps word k and the wave's 16 words leave as one 8-byte store per lane (four 32-byte row pieces).  A tile
+// outside the crop window stores its 16 x 4 zero words (512 B) and exits; the dense [n][img_h][img_w] tensor exists nowhere.
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_masks_fused_packed(const float* __restrict__ proto, const float* __restrict__ coefs,
+                                                             const float* __restrict__ boxes, const int32_t* __restrict__ counts,
+                                                             int max_det, int Hp, int Wp, int img_h, int img_w, int do_crop,
+                                                             unsigned long long* __restrict__ out) {
+    __shared__ float patch[FP_H * FP_W];
+    __shared__ __attribute__((aligned(16))) float cf[32];
+    const int b = blockIdx.z, d = blockIdx.y;
+    const int n = counts ? counts[b] : max_det;
+    if (d >= n) return;
+    const size_t slot = (size_t)b * max_det + d;
+    fused_tile<true>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, img_h, img_w,
+                     do_crop, out + slot * (size_t)img_h * ((img_w + 63) >> 6));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The same tiles for a batch whose images differ in size (ym_after_nms_ragged): the per-image {img_h, img_w, offset} table arrives BY
+// VALUE in the kernel arguments (no copy, no synchronisation per call) and is indexed by blockIdx.z, which is uniform, so the three
+// words come from the argument segment with scalar loads.  grid.x is the largest tile count of the batch: tiles past an image's own
+// count exit at once, like detection slots past its count and images that take the two-kernel path (bit b of `fused` clear).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct RaggedTable { ym_ragged_image img[YM_RAGGED_MAX_IMAGES]; };
+
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_masks_fused_ragged(const float* __restrict__ proto, const float* __restrict__ coefs,
+                                                             const float* __restrict__ boxes, const int32_t* __restrict__ counts,
+                                                             int max_det, int Hp, int Wp, const RaggedTable tab, unsigned fused, int do_crop,
+                                                             typename mask_elem<PACKED>::type* __restrict__ out) {
+    __shared__ float patch[FP_H * FP_W];
+    __shared__ __attribute__((aligned(16))) float cf[32];
+    const int b = blockIdx.z, d = blockIdx.y;
+    if (!((fused >> b) & 1u)) return;
+    const int img_h = tab.img[b].img_h, img_w = tab.img[b].img_w;
+    if ((int)blockIdx.x >= ((img_w + FT_W - 1) / FT_W) * ((img_h + FT_H - 1) / FT_H)) return;
+    const int n = counts ? counts[b] : max_det;
+    if (d >= n) return;
+    const size_t slot = (size_t)b * max_det + d;
+    const size_t row = PACKED ? (size_t)((img_w + 63) >> 6) : (size_t)img_w;
+    fused_tile<PACKED>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, img_h, img_w,
+                       do_crop, out + (size_t)tab.img[b].offset + (size_t)d * img_h * row);
 }
 
 // the two-kernel path's resize with packed output: a wave per word, lane = pixel (k_mask_resize's expression per pixel)
-__global__ __launch_bounds__(256) void k_mask_resize_packed(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
-                                                             unsigned long long* __restrict__ out) {
+__device__ __forceinline__ void resize_rows_packed(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
+                                                   unsigned long long* __restrict__ out) {
     const int S = img_h > img_w ? img_h : img_w;
     const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
     const int wq = (img_w + 63) >> 6, lane = threadIdx.x & 63;
@@ -357,6 +367,17 @@ __global__ __launch_bounds__(256) void k_mask_resize_packed(const float* __restr
         const unsigned long long w = __ballot(x < img_w && v > 0.5f);
         if (lane == 0) out[i] = w;
     }
+}
+
+__global__ __launch_bounds__(256) void k_mask_resize_packed(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
+                                                             unsigned long long* __restrict__ out) {
+    resize_rows_packed(masks, n, Hp, Wp, img_h, img_w, out);
+}
+
+__global__ __launch_bounds__(256) void k_mask_resize_packed_counted(const float* __restrict__ masks, const int32_t* __restrict__ count,
+                                                                     int max_det, int Hp, int Wp, int img_h, int img_w,
+                                                                     unsigned long long* __restrict__ out) {
+    resize_rows_packed(masks, clamped_count(count, max_det), Hp, Wp, img_h, img_w, out);
 }
 
 // dense {0, nonzero} rows -> words.  A wave takes PK consecutive words of the flat [rows][wq] output (PK row pieces of 64 pixels in
@@ -409,6 +430,18 @@ __global__ void k_boxes_to_pixels(float* boxes, int32_t* px, int count, float S)
         const float v = boxes[i] * S;
         boxes[i] = v;
         px[i] = (int32_t)v;   // trunc toward zero, like Tensor.int()
+    }
+}
+
+// grid.y = image: its own S = max(img_h, img_w)
+__global__ void k_boxes_to_pixels_ragged(float* boxes, int32_t* px, int per_image, const RaggedTable tab) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i < per_image) {
+        const int h = tab.img[b].img_h, w = tab.img[b].img_w;
+        const size_t at = (size_t)b * per_image + i;
+        const float v = boxes[at] * (float)(h > w ? h : w);
+        boxes[at] = v;
+        px[at] = (int32_t)v;
     }
 }
 
@@ -519,6 +552,99 @@ extern "C" int ym_after_nms_batch_packed(const float* proto, const float* coefs,
     const int cnt = B * max_det * 4;
     hipLaunchKernelGGL(k_boxes_to_pixels, dim3(ym_cdiv(cnt, 256)), dim3(256), 0, st, boxes, boxes_px, cnt, (float)S);
     return ym_check_launch("after_nms_batch_packed");
+}
+
+// ---- batches whose images differ in size -----------------------------------------------------------------------------------------
+// Checks the table; *fused = bit b set when image b takes the fused kernel.
+static int ragged_check(const char* what, const ym_ragged_image* images, int B, int max_det, int Hp, int Wp, bool packed, unsigned* fused) {
+    YM_REQUIRE(images, "%s: null image table", what);
+    YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
+    YM_REQUIRE(max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0, "%s: bad shape", what);
+    const int64_t esz = packed ? 8 : 4;
+    *fused = 0u;
+    for (int b = 0; b < B; ++b) {
+        const ym_ragged_image& im = images[b];
+        YM_REQUIRE(im.img_h > 0 && im.img_w > 0, "%s: image %d is %d x %d", what, b, im.img_h, im.img_w);
+        YM_REQUIRE(im.offset >= 0 && (im.offset * esz) % YM_RAGGED_ALIGN_BYTES == 0, "%s: image %d: block offset %lld is not a multiple of %d bytes",
+                   what, b, (long long)im.offset, YM_RAGGED_ALIGN_BYTES);
+        if (fused_fits(Hp, Wp, im.img_h, im.img_w)) *fused |= 1u << b;
+    }
+    for (int a = 0; a < B; ++a)          // blocks must not overlap (B <= 32: a few hundred compares)
+        for (int b = a + 1; b < B; ++b) {
+            const int64_t ea = images[a].offset + (int64_t)max_det * images[a].img_h * (packed ? ym_cdiv(images[a].img_w, 64) : images[a].img_w);
+            const int64_t eb = images[b].offset + (int64_t)max_det * images[b].img_h * (packed ? ym_cdiv(images[b].img_w, 64) : images[b].img_w);
+            YM_REQUIRE(ea <= images[b].offset || eb <= images[a].offset, "%s: the mask blocks of images %d and %d overlap", what, a, b);
+        }
+    return YM_OK;
+}
+
+extern "C" size_t ym_after_nms_ragged_workspace_bytes(const ym_ragged_image* images, int B, int max_det, int Hp, int Wp) {
+    if (!images || B < 1 || B > YM_RAGGED_MAX_IMAGES || max_det < 1 || Hp <= 0 || Wp <= 0) return 0;
+    for (int b = 0; b < B; ++b)
+        if (images[b].img_h > 0 && images[b].img_w > 0 && !fused_fits(Hp, Wp, images[b].img_h, images[b].img_w))
+            return (size_t)max_det * Hp * Wp * sizeof(float);
+    return 0;
+}
+
+template <bool PACKED>
+static int after_nms_ragged(const char* what, const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
+                            int Hp, int Wp, int K, const ym_ragged_image* images, int do_crop, typename mask_elem<PACKED>::type* masks,
+                            int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    YM_REQUIRE(K == 32, "%s: coefficient dim must be 32, got %d", what, K);
+    unsigned fused = 0u;
+    const int rc0 = ragged_check(what, images, B, max_det, Hp, Wp, PACKED, &fused);
+    if (rc0 != YM_OK) return rc0;
+    YM_REQUIRE(proto && coefs && boxes && masks && boxes_px, "%s: null pointer", what);
+    YM_REQUIRE(((uintptr_t)masks & 15) == 0, "%s: the mask buffer must be 16-byte aligned", what);
+    hipStream_t st = (hipStream_t)s;
+    RaggedTable tab = {};
+    int tiles = 0;
+    for (int b = 0; b < B; ++b) {
+        tab.img[b] = images[b];
+        const int t = ym_cdiv(images[b].img_w, FT_W) * ym_cdiv(images[b].img_h, FT_H);
+        if (((fused >> b) & 1u) && t > tiles) tiles = t;
+    }
+    if (tiles)
+        hipLaunchKernelGGL(k_masks_fused_ragged<PACKED>, dim3(tiles, max_det, B), dim3(256), 0, st, proto, coefs, boxes, counts, max_det, Hp, Wp,
+                           tab, fused, do_crop, masks);
+    for (int b = 0; b < B; ++b) {
+        if ((fused >> b) & 1u) continue;
+        // strong down-scaling: the two-kernel path of the uniform entry for this image, its resize bounded by the count on the device
+        const size_t soft_bytes = (size_t)max_det * Hp * Wp * sizeof(float);
+        if (!workspace || workspace_bytes < soft_bytes) { ym_set_error("%s: workspace %zu B < %zu B", what, workspace_bytes, soft_bytes); return YM_ENOSPC; }
+        const size_t slot = (size_t)b * max_det;
+        const int img_h = images[b].img_h, img_w = images[b].img_w;
+        const int rc = ym_mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, K, do_crop,
+                                        (float*)workspace, s);
+        if (rc != YM_OK) return rc;
+        const size_t items = PACKED ? ((size_t)max_det * img_h * ym_cdiv(img_w, 64) + 3) / 4      // a wave per word
+                                    : ((size_t)max_det * img_h * ((img_w + 3) / 4) + 255) / 256;  // a thread per 4 pixels
+        const int grid = (int)(items > 16384 ? 16384 : items);
+        typename mask_elem<PACKED>::type* dst = masks + images[b].offset;
+        if constexpr (PACKED) {
+            if (counts) hipLaunchKernelGGL(k_mask_resize_packed_counted, dim3(grid), dim3(256), 0, st, (const float*)workspace, counts + b, max_det, Hp, Wp, img_h, img_w, dst);
+            else hipLaunchKernelGGL(k_mask_resize_packed, dim3(grid), dim3(256), 0, st, (const float*)workspace, max_det, Hp, Wp, img_h, img_w, dst);
+        } else {
+            if (counts) hipLaunchKernelGGL(k_mask_resize_counted, dim3(grid), dim3(256), 0, st, (const float*)workspace, counts + b, max_det, Hp, Wp, img_h, img_w, dst);
+            else hipLaunchKernelGGL(k_mask_resize, dim3(grid), dim3(256), 0, st, (const float*)workspace, max_det, Hp, Wp, img_h, img_w, dst);
+        }
+    }
+    hipLaunchKernelGGL(k_boxes_to_pixels_ragged, dim3(ym_cdiv(max_det * 4, 256), B), dim3(256), 0, st, boxes, boxes_px, max_det * 4, tab);
+    return ym_check_launch(what);
+}
+
+extern "C" int ym_after_nms_ragged(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
+                                   int Wp, int K, const ym_ragged_image* images, int do_crop, float* masks, int32_t* boxes_px,
+                                   void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    return after_nms_ragged<false>("after_nms_ragged", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, images, do_crop, masks, boxes_px,
+                                   workspace, workspace_bytes, s);
+}
+
+extern "C" int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
+                                          int Hp, int Wp, int K, const ym_ragged_image* images, int do_crop, uint64_t* mask_bits,
+                                          int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    return after_nms_ragged<true>("after_nms_ragged_packed", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, images, do_crop,
+                                  reinterpret_cast<unsigned long long*>(mask_bits), boxes_px, workspace, workspace_bytes, s);
 }
 
 extern "C" int ym_pack_masks(const void* masks, int is_u8, int n, int H, int W, uint64_t* bits, ym_stream_t s) {

@@ -14,21 +14,73 @@ from .utils.device_metrics import DeviceAPData
 IOU_THRES = [x / 100 for x in range(50, 100, 5)]                              # eval.py:24
 
 
-def eval_pipeline(net, cfg, img, img_h, img_w, depth=4, packed_masks=True):
+def eval_pipeline(net, cfg, img, img_h, img_w, depth=4, packed_masks=True, batch=1):
     """The `RequestPipeline` `evaluate_pipelined` runs on, with its hipGraphs captured on `img`: build it once and hand it to several
-    calls (`pipe=`) where the same network evaluates more than one sample set -- four engines and their capture are no part of a set."""
+    calls (`pipe=`) where the same network evaluates more than one sample set -- four engines and their capture are no part of a set.
+    `batch` > 1: requests of `batch` images (`img` is one image, or already a batch of that many)."""
     device = next(net.parameters()).device
-    pipe = RequestPipeline(net, cfg, img.shape[2], img.shape[3], device, depth=depth, out_hw=(img_h, img_w), packed_masks=packed_masks)
-    pipe.warm_up(img.to(device), rounds=0)
+    pipe = RequestPipeline(net, cfg, img.shape[2], img.shape[3], device, depth=depth, out_hw=(img_h, img_w), packed_masks=packed_masks,
+                           batch=batch)
+    img = img.to(device)
+    if batch > 1 and img.shape[0] != batch:
+        img = img[:1].expand(batch, -1, -1, -1).contiguous()
+    pipe.warm_up(img, rounds=0)
     return pipe
 
 
-def evaluate_pipelined(net, cfg, samples, depth=4, packed_masks=True, step=None, pipe=None):
+def _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe):
+    """`batch` consecutive samples per request, every image at its own output size; a short last group is padded by repeating its
+    last image, and a padded entry is never added."""
+    device = acc.device
+    group = []
+
+    def flush(pipe):
+        first = group[0][0]
+        real = len(group)
+        entries = group + [group[-1]] * (batch - real)
+        imgs = torch.cat([e[1] for e in entries], 0)
+        sizes = [(e[4], e[5]) for e in entries]
+        if pipe is None:
+            pipe = eval_pipeline(net, cfg, imgs, sizes[0][0], sizes[0][1], depth, packed_masks, batch)
+        held = [t for e in group for t in e[1:4]] + [imgs]
+        gts = [(e[2], e[3]) for e in group]
+
+        def consume(ids, scores, boxes_px, masks, counts):
+            slot_stream = torch.cuda.current_stream(device)
+            for t in held:                                      # made on the caller's stream, read on the slot's
+                t.record_stream(slot_stream)
+            for b in range(real):                               # (one image's padded rows and its count: what `add` takes)
+                acc.add(ids[b], scores[b], boxes_px[b], masks[b], counts[b:b + 1], gts[b][0], gts[b][1], sizes[b][0], sizes[b][1],
+                        image_index=first + b)
+
+        pipe.submit(imgs, out_hw=sizes, consumer=consume)
+        del group[:]
+        return pipe
+
+    for i, (img, gt, gt_masks, img_h, img_w) in enumerate(samples):
+        group.append((i, img.to(device), gt.to(device), gt_masks.to(device), int(img_h), int(img_w)))
+        if len(group) == batch:
+            pipe = flush(pipe)
+    if group:
+        pipe = flush(pipe)
+    return pipe
+
+
+def evaluate_pipelined(net, cfg, samples, depth=4, packed_masks=True, step=None, pipe=None, batch=1):
     """`samples` yields eval.py's `(img [1,3,H,W], gt [g,5], gt_masks [g,h,w], img_h, img_w)`; all images share one input size.
-    `pipe`: an idle pipeline of `eval_pipeline` to run on (`depth` and `packed_masks` are then the pipeline's); by default one is
-    built on the first sample.  Returns ((table text, box row, mask row), the DeviceAPData)."""
+    `pipe`: an idle pipeline of `eval_pipeline` to run on (`depth`, `packed_masks` and `batch` are then the pipeline's); by default
+    one is built on the first sample.  `batch` > 1: `batch` consecutive samples form one request, each image post-processed at its own
+    `(img_h, img_w)` (`after_nms_batch` with per-image sizes) and added on the slot's stream image by image; a short last request is
+    padded with copies of its last image, which are not added.  Returns ((table text, box row, mask row), the DeviceAPData)."""
     device = next(net.parameters()).device
     acc = DeviceAPData(len(cfg.class_names), IOU_THRES, device, max_det=cfg.max_detections)
+    if pipe is not None:
+        batch = pipe.batch
+    if batch > 1:
+        pipe = _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe)
+        if pipe is not None:
+            pipe.drain()
+        return acc.calc_map(step), acc
     for i, (img, gt, gt_masks, img_h, img_w) in enumerate(samples):
         img, gt, gt_masks = img.to(device), gt.to(device), gt_masks.to(device)
         if pipe is None:

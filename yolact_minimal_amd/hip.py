@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     'ym_conv2d_bn_partial_rows', 'ym_conv2d_effective_plan', 'ym_bn_partials_finish', 'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes',
     'ym_eval_match_log', 'ym_eval_ap_workspace_bytes', 'ym_eval_ap',
     'ym_coco_iou_box', 'ym_coco_iou_mask_packed', 'ym_coco_match_log', 'ym_coco_accumulate_workspace_bytes', 'ym_coco_accumulate',
+    'ym_after_nms_ragged_workspace_bytes', 'ym_after_nms_ragged', 'ym_after_nms_ragged_packed',
 )
 
 
@@ -111,6 +112,14 @@ class NmsCfg(ctypes.Structure):
                 ('top_k', ctypes.c_int32), ('max_det', ctypes.c_int32), ('score_thre', ctypes.c_float),
                 ('iou_thre', ctypes.c_float), ('img_size', ctypes.c_float)]
 
+
+class RaggedImage(ctypes.Structure):
+    """ym_ragged_image: one image of `ym_after_nms_ragged`'s host table (output size, first element of its mask block)."""
+    _fields_ = [('img_h', ctypes.c_int32), ('img_w', ctypes.c_int32), ('offset', ctypes.c_int64)]
+
+
+RAGGED_MAX_IMAGES = 32          # YM_RAGGED_MAX_IMAGES
+RAGGED_ALIGN_BYTES = 256        # YM_RAGGED_ALIGN_BYTES
 
 _lib = None
 
@@ -238,6 +247,10 @@ def lib():
                                                ctypes.c_char_p, vp, vp, vp, sz, vp]
         L.ym_draw_cutout_objects.argtypes = [vp, vp, i32, i32, i32, vp, vp]
         L.ym_after_nms_batch_packed.argtypes = L.ym_after_nms_batch.argtypes
+        L.ym_after_nms_ragged_workspace_bytes.argtypes = [ctypes.POINTER(RaggedImage), i32, i32, i32, i32]
+        L.ym_after_nms_ragged_workspace_bytes.restype = sz
+        L.ym_after_nms_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(RaggedImage), i32, vp, vp, vp, sz, vp]
+        L.ym_after_nms_ragged_packed.argtypes = L.ym_after_nms_ragged.argtypes
         L.ym_pack_masks.argtypes = [vp, i32, i32, i32, i32, vp, vp]
         L.ym_unpack_masks.argtypes = [vp, i32, i32, i32, vp, vp]
         L.ym_mask_iou_packed_workspace_bytes.argtypes = [i32, i32, i64]

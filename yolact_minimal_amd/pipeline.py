@@ -9,6 +9,8 @@ but the read-only weights) and `depth` HIP streams, and runs request i on slot i
 `Yolact.forward` -> `nms` -> `after_nms` with ONE host read (its detection count, which `after_nms` needs to size what it returns);
 the count is copied to pinned host memory behind the request and read when the slot comes up again, so the host never waits on
 the request it has just enqueued.  `cfg.traditional_nms` is served the same way (`nms_batch` picks the batched greedy entry).
+With batch > 1 a request may give every image its own output size (`submit(out_hw=[(h, w), ...])`: `after_nms_batch` with per-image
+sizes, one launch set, the size table in the kernel arguments, so nothing is copied or synchronised per request).
 
 Measured mid-round 3 (res101_coco 544 px, MI355X, forward + nms + after_nms(480x640)): depth 1: 325 img/s, 2: 468, 3: 545, 4: 594, 5: 495,
 8: 479; with round 4's kernels 3: 580, 4: 603-617, 5: 499, 6: 527 -- the part schedules four compute pipes; GPU_MAX_HW_QUEUES must be >= depth + 1 (ROCm multiplexes HIP streams onto 4
@@ -142,7 +144,7 @@ class RequestPipeline:
         # the results were allocated on the slot's stream and are consumed on the caller's: tell the allocator, or the slot's next
         # request could be handed the block while a kernel of the caller still reads it
         cur = torch.cuda.current_stream(self.device)
-        for t in (ids, scores, box_px, masks):
+        for t in (ids, scores, box_px, masks[0] if isinstance(masks, list) else masks):   # (per-image views share one allocation)
             t.record_stream(cur)
         out = []
         for b, n in enumerate(self.counts_host[slot].tolist()):
@@ -162,8 +164,10 @@ class RequestPipeline:
         """Enqueue one request ([batch,3,H,W] images, device resident) on the next slot and return the finished result of the request
         that used this slot before (None the first `depth` times).  `head_outputs`: post-process these (class, box, coef, proto)
         tensors instead of the forward's own outputs (bench.py: a random-init network yields degenerate detections).
-        `out_hw`: this request's output size (default: the pipeline's).  `consumer`: a callable run ON THE SLOT'S STREAM, right
-        behind the post-processing, with the padded device tensors `(ids, scores, boxes_px, masks, counts)` of
+        `out_hw`: this request's output size (default: the pipeline's); with batch > 1 also a list of `batch` (h, w) pairs, one per
+        image: the results then come at those sizes (`after_nms_batch` with per-image sizes; a consumer's `masks` is its list of
+        per-image views), while a single pair keeps meaning "all images" through the uniform entry.
+        `consumer`: a callable run ON THE SLOT'S STREAM, right behind the post-processing, with the padded device tensors `(ids, scores, boxes_px, masks, counts)` of
         `after_nms_batch(sync=False)`; `finish` / `drain` then hand back ITS return value for the request instead of the detections,
         and no detection count is read on the host (`utils/device_metrics.DeviceAPData.add` is such a consumer).  What `finish` does
         with that count is therefore not done for such a request: `detections` is not advanced, and the `cfg.visual_thre` filter is
@@ -175,11 +179,17 @@ class RequestPipeline:
         if consumer is not None and self.vt > 0:
             raise RuntimeError(f'RequestPipeline.submit: cfg.visual_thre = {self.vt} is applied where the count is read on the host; '
                                'a consumer would be handed the unfiltered rows')
+        hw = self.out_hw if out_hw is None else out_hw
+        if len(hw) and hasattr(hw[0], '__len__'):         # one (h, w) pair per image
+            if self.batch == 1 or len(hw) != self.batch or any(len(p) != 2 for p in hw):
+                raise RuntimeError(f'RequestPipeline.submit: out_hw is one (h, w) pair, or with batch > 1 a list of {self.batch} pairs')
+            out_h, out_w = [int(p[0]) for p in hw], [int(p[1]) for p in hw]
+        else:
+            out_h, out_w = hw
         slot = self.submitted % self.depth
         self.submitted += 1
         done = self.finish(slot)
         ev = self.events[slot]
-        out_h, out_w = self.out_hw if out_hw is None else out_hw
         # `img` / `head_outputs` were produced on the caller's stream (an H2D copy, `val_aug`), and `finish` may have queued copies
         # of the slot's previous outputs there: the slot's stream starts behind that
         self.streams[slot].wait_stream(torch.cuda.current_stream(self.device))

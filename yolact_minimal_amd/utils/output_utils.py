@@ -239,11 +239,74 @@ def nms_batch(class_pred, box_pred, coef_pred, proto_out, anchors, cfg):
     return BatchDetections(counts, ids, scores, boxes, coefs, proto_out)
 
 
+def ragged_layout(sizes, max_det, packed=False):
+    """Where `ym_after_nms_ragged[_packed]` puts the masks of a batch whose images differ in size: `(offsets, total)` in elements
+    (floats, or 64-bit words when `packed`) of ONE flat buffer.  Image b's block is `[max_det, h_b, w_b]` floats (packed:
+    `[max_det, h_b, ceil(w_b / 64)]` words) at `offsets[b]`; every block starts at a multiple of 256 bytes (the dense kernel stores 16
+    bytes at a time, and an odd `max_det` x odd height x odd width would leave the next block misaligned); `total` ends the last
+    block.  Pure Python: no GPU, no library."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    max_det = int(max_det)
+    if not 1 <= len(sizes) <= hip.RAGGED_MAX_IMAGES:
+        raise RuntimeError(f'ragged_layout: 1 .. {hip.RAGGED_MAX_IMAGES} images per call, got {len(sizes)}')
+    if max_det < 1:
+        raise RuntimeError(f'ragged_layout: max_det = {max_det}')
+    step = hip.RAGGED_ALIGN_BYTES // (8 if packed else 4)
+    offsets, end = [], 0
+    for h, w in sizes:
+        if h <= 0 or w <= 0:
+            raise RuntimeError(f'ragged_layout: output size {h} x {w}')
+        at = -(-end // step) * step
+        offsets.append(at)
+        end = at + max_det * h * ((w + 63) // 64 if packed else w)
+    return offsets, end
+
+
+_ragged_plans = {}
+
+
+def _after_nms_ragged(dets, sizes, do_crop, packed):
+    """The masks (a list of per-image views of one flat allocation) and pixel boxes of `after_nms_batch` with per-image sizes."""
+    device = dets.proto.device
+    batch, md = dets.ids.shape
+    _, hp, wp, k = dets.proto.shape
+    L = hip.lib()
+    key = (tuple(sizes), md, hp, wp, packed)
+    plan = _ragged_plans.get(key)
+    if plan is None:
+        offsets, total = ragged_layout(sizes, md, packed)
+        table = (hip.RaggedImage * batch)(*[hip.RaggedImage(h, w, o) for (h, w), o in zip(sizes, offsets)])
+        if len(_ragged_plans) >= 1024:
+            _ragged_plans.clear()
+        plan = _ragged_plans[key] = (offsets, total, table, L.ym_after_nms_ragged_workspace_bytes(table, batch, md, hp, wp))
+    offsets, total, table, nbytes = plan
+    with torch.cuda.device(device):
+        flat = torch.empty(total, dtype=torch.int64 if packed else torch.float32, device=device)
+        box_px = torch.empty(batch, md, 4, dtype=torch.int32, device=device)
+        ws = _scratch(device, nbytes) if nbytes else None
+        fn = L.ym_after_nms_ragged_packed if packed else L.ym_after_nms_ragged
+        hip.check(fn(hip.ptr(dets.proto.contiguous()), hip.ptr(dets.coefs), hip.ptr(dets.boxes), hip.ptr(dets.counts, torch.int32), batch, md,
+                     hp, wp, k, table, int(do_crop), hip.ptr(flat, flat.dtype), hip.ptr(box_px, torch.int32),
+                     ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes, hip.stream_ptr()), 'ym_after_nms_ragged')
+    masks = []
+    for (h, w), o in zip(sizes, offsets):
+        if packed:
+            wq = (w + 63) // 64
+            masks.append(PackedMasks._wrap(flat[o:o + md * h * wq].view(md, h, wq), h, w))
+        else:
+            masks.append(flat[o:o + md * h * w].view(md, h, w))
+    return masks, box_px
+
+
 def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
-    """`after_nms` for every image of a `BatchDetections` in one launch set (all images resized to the same img_h x img_w, as in a
-    bench / fixed-size serving batch).  Returns a list of per-image 4-tuples like `after_nms` — or, with `sync=False`, the padded
-    device tensors (ids, scores, boxes_px, masks, counts) without any host read.  `packed=True` (or `cfg.packed_masks`): the masks
-    are `PackedMasks` (padded: `[B, max_det, img_h, ceil(img_w / 64)]` words)."""
+    """`after_nms` for every image of a `BatchDetections` in one launch set.  Returns a list of per-image 4-tuples like `after_nms`
+    -- or, with `sync=False`, the padded device tensors (ids, scores, boxes_px, masks, counts) without any host read.
+    `packed=True` (or `cfg.packed_masks`): the masks are `PackedMasks`.
+    Ints `img_h`, `img_w`: all images are resized to that one size (a bench / fixed-size serving batch); the padded masks are
+    `[B, max_det, img_h, img_w]` (packed: `[B, max_det, img_h, ceil(img_w / 64)]` words).
+    Sequences of B heights and B widths: every image at its OWN size (`ym_after_nms_ragged`, also when the sizes are all equal);
+    the padded `masks` is then a list of B per-image views `[max_det, h_b, w_b]` of one flat allocation (`ragged_layout`), each
+    what the consumers of one image's padded rows take (`DeviceAPData.add`, `rle_encode`, `draw_img`)."""
     packed = _want_packed(cfg, packed)
     device = dets.proto.device
     batch, md = dets.ids.shape
@@ -251,13 +314,23 @@ def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
     do_crop = not (cfg and getattr(cfg, 'no_crop', False))
     if cfg and getattr(cfg, 'save_lincomb', False):
         raise NotImplementedError('draw_lincomb (visualisation, reference output_utils.py:276-324) is out of scope')
-    with torch.cuda.device(device):
-        masks = _new_masks((batch, md), img_h, img_w, device, packed)
-        box_px = torch.empty(batch, md, 4, dtype=torch.int32, device=device)
-        _after_nms_launch(dets.proto.contiguous(), dets.coefs, dets.boxes, dets.counts, batch, md, hp, wp, k, img_h, img_w, do_crop,
-                          masks, box_px)
-    if packed:
-        masks = PackedMasks._wrap(masks, img_h, img_w)
+    ragged = hasattr(img_h, '__len__') or hasattr(img_w, '__len__')
+    if ragged:
+        if not (hasattr(img_h, '__len__') and hasattr(img_w, '__len__')) or len(img_h) != batch or len(img_w) != batch:
+            raise RuntimeError(f'after_nms_batch: {batch} heights and {batch} widths expected for a batch of {batch} images')
+        sizes = [(int(h), int(w)) for h, w in zip(img_h, img_w)]
+        ragged_layout(sizes, md, packed)                          # (size and batch-bound errors, before any launch)
+        if not dets.proto.is_cuda:
+            raise RuntimeError('yolact_minimal_amd.utils.output_utils.after_nms_batch needs CUDA (HIP) tensors; there is no CPU path.')
+        masks, box_px = _after_nms_ragged(dets, sizes, do_crop, packed)
+    else:
+        with torch.cuda.device(device):
+            masks = _new_masks((batch, md), img_h, img_w, device, packed)
+            box_px = torch.empty(batch, md, 4, dtype=torch.int32, device=device)
+            _after_nms_launch(dets.proto.contiguous(), dets.coefs, dets.boxes, dets.counts, batch, md, hp, wp, k, img_h, img_w, do_crop,
+                              masks, box_px)
+        if packed:
+            masks = PackedMasks._wrap(masks, img_h, img_w)
     if not sync:
         return dets.ids, dets.scores, box_px, masks, dets.counts
     out = []
