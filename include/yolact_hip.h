@@ -426,6 +426,11 @@ int ym_class_box_loss(const float* class_p, const float* box_p, const float* off
 int ym_select_positives(const int64_t* conf, const float* keys, int B, int N, int cap, const int32_t* num_pos, int64_t* idx,
                         ym_stream_t s);
 
+/* The gt masks at the size of a prediction map (modules/yolact.py:247-251, :302-304): out [n][out_h][out_w] =
+ * F.interpolate(masks [n][H][W], (out_h, out_w), bilinear, align_corners=False) > 0.5, exactly 0.0f / 1.0f, with one scale per
+ * axis.  For a square map it equals ym_mask_resize_binarize bit for bit; that one scales both axes by the longer side. */
+int ym_gt_masks_downsample(const float* masks, int n, int H, int W, int out_h, int out_w, float* out, ym_stream_t s);
+
 /* semantic_seg_loss (modules/yolact.py:293-313) for ONE image: seg_nhwc [P][pitch] logits (channels >= num_classes are
  * padding), gt_masks_ds [g][P] in {0,1} (down-sampled + binarised gt masks), gt_cls[j*gt_cls_stride] the class of gt j.
  * loss_accum += coeff * sum BCE-with-logits(seg, target) with target[c][pix] = max over gts of class c; dseg [P][pitch] =

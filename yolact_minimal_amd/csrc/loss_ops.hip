@@ -374,6 +374,57 @@ __global__ __launch_bounds__(256) void k_ce_loss(const float* __restrict__ cls, 
     if (lane == 0 && acc != 0.0) atomicAdd(loss, acc * (double)coeff);
 }
 
+// ---- gt masks at the size of a prediction map (:247-251, :302-304) --------------------------------------------------------------
+// F.interpolate(masks, (oh, ow), bilinear, align_corners=False) > 0.5 with ONE SCALE PER AXIS (H / oh, W / ow): ATen's source-index
+// maths.  ym_mask_resize_binarize is after_nms's resize (one scale, to the square of the longer side, then a crop), which equals
+// this one only when the map is square; there the two agree bit for bit (same expressions, no contraction in either file).
+// Thread = four neighbouring outputs of a row.
+__device__ __forceinline__ void ds_coord(int dst, float scale, int in_sz, int& i0, int& i1, float& l1) {
+    float src = scale * ((float)dst + 0.5f) - 0.5f;
+    if (src < 0.f) src = 0.f;
+    i0 = (int)src;
+    if (i0 > in_sz - 1) i0 = in_sz - 1;
+    i1 = i0 + ((i0 < in_sz - 1) ? 1 : 0);
+    l1 = src - (float)i0;
+}
+
+__global__ __launch_bounds__(256) void k_gt_masks_downsample(const float* __restrict__ masks, int n, int H, int W, int oh, int ow,
+                                                              float* __restrict__ out) {
+    const float sy = (float)H / (float)oh, sx = (float)W / (float)ow;
+    const int wq = (ow + 3) >> 2;
+    const size_t total = (size_t)n * oh * wq;
+    const bool vec = (ow & 3) == 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int xq = (int)(i % wq);
+        size_t t = i / wq;
+        const int y = (int)(t % oh);
+        const int d = (int)(t / oh);
+        int y0, y1; float ly;
+        ds_coord(y, sy, H, y0, y1, ly);
+        const float hy = 1.f - ly;
+        const float* r0 = masks + ((size_t)d * H + y0) * W;
+        const float* r1 = masks + ((size_t)d * H + y1) * W;
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int x = xq * 4 + e;
+            int x0, x1; float lx;
+            ds_coord(x < ow ? x : ow - 1, sx, W, x0, x1, lx);
+            const float hx = 1.f - lx;
+            const float v = hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
+            o[e] = v > 0.5f ? 1.f : 0.f;
+        }
+        float* dst = out + ((size_t)d * oh + y) * ow + xq * 4;
+        if (vec) {
+            *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (xq * 4 + e < ow) dst[e] = o[e];
+        }
+    }
+}
+
 // ---- semantic segmentation loss (:293-313), thread = (pixel, channel), blockIdx.y = image -----------------------------------
 // seg: NHWC [B][P][pitch] logits (first nc channels real), per image ds: [g][P] binarised down-sampled gt masks, cls: [g] class ids.
 __global__ __launch_bounds__(256) void k_semantic_loss(const float* __restrict__ seg, int P, int pitch, int nc, SemanticBatch sb,
@@ -479,6 +530,17 @@ extern "C" int ym_select_positives(const int64_t* conf, const float* keys, int B
     YM_REQUIRE(conf && keys && num_pos && idx && B > 0 && N > 0 && cap > 0, "select_positives: bad args");
     hipLaunchKernelGGL(k_select_positives, dim3(B), dim3(NT), 0, (hipStream_t)s, conf, keys, N, cap, num_pos, idx);
     return ym_check_launch("select_positives");
+}
+
+extern "C" int ym_gt_masks_downsample(const float* masks, int n, int H, int W, int out_h, int out_w, float* out, ym_stream_t s) {
+    YM_REQUIRE(n >= 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0, "gt_masks_downsample: bad shape");
+    if (n == 0) return YM_OK;
+    YM_REQUIRE(masks && out, "gt_masks_downsample: null pointer");
+    const size_t total = (size_t)n * out_h * ((out_w + 3) / 4);
+    size_t grid = (total + 255) / 256;
+    if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(k_gt_masks_downsample, dim3((int)grid), dim3(256), 0, (hipStream_t)s, masks, n, H, W, out_h, out_w, out);
+    return ym_check_launch("gt_masks_downsample");
 }
 
 extern "C" int ym_semantic_loss_batch(const float* seg_nhwc, int B, int P, int pitch, int num_classes,

@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     'ym_layernorm_bwd_workspace_bytes', 'ym_layernorm_bwd', 'ym_patch_merge_layernorm_bwd', 'ym_gelu_fwd', 'ym_gelu_bwd',
     'ym_swin_window_attention_bwd', 'ym_adamw_step', 'ym_drop_path_add', 'ym_drop_path_bwd', 'ym_select_positives',
     'ym_match_anchors', 'ym_match_anchors_batch', 'ym_loss_workspace_bytes', 'ym_class_box_loss', 'ym_semantic_loss',
-    'ym_semantic_loss_batch',
+    'ym_semantic_loss_batch', 'ym_gt_masks_downsample',
     'ym_draw_workspace_bytes', 'ym_draw_detections_batch', 'ym_draw_cutout_objects',
     'ym_after_nms_batch_packed', 'ym_pack_masks', 'ym_unpack_masks', 'ym_mask_iou_packed_workspace_bytes', 'ym_mask_iou_packed',
     'ym_rle_encode_packed', 'ym_draw_detections_batch_packed', 'ym_draw_cutout_objects_packed',
@@ -210,6 +210,7 @@ def lib():
         L.ym_gelu_bwd.argtypes = [vp, vp, vp, i64, vp]
         L.ym_swin_window_attention_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.ym_select_positives.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+        L.ym_gt_masks_downsample.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
         L.ym_drop_path_add.argtypes = [vp, vp, vp, ctypes.c_float, vp, i32, i64, vp]
         L.ym_drop_path_bwd.argtypes = [vp, vp, ctypes.c_float, vp, i32, i64, vp]
         L.ym_adamw_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]
@@ -409,6 +410,12 @@ def mask_resize_binarize(masks, img_h, img_w, out):
     n, hp, wp = masks.shape
     check(lib().ym_mask_resize_binarize(ptr(masks), n, hp, wp, img_h, img_w, ptr(out), stream_ptr()),
           'ym_mask_resize_binarize')
+
+
+def gt_masks_downsample(masks, out_h, out_w, out):
+    """F.interpolate(masks, (out_h, out_w), bilinear, align_corners=False) > 0.5 as floats: the losses' gt masks."""
+    n, h, w = masks.shape
+    check(lib().ym_gt_masks_downsample(ptr(masks), n, h, w, out_h, out_w, ptr(out), stream_ptr()), 'ym_gt_masks_downsample')
 
 
 def expf_cr(x):

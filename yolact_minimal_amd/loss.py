@@ -168,7 +168,7 @@ def lincomb_mask_loss(cfg, pos, anchor_gt, coef_p, proto_p, mask_gt, anchor_box,
     for i in range(b):
         g = mask_gt[i].shape[0]
         ds = torch.empty(g, ph, pw, device=dev, dtype=torch.float32)                 # bilinear(align_corners=False) then > 0.5
-        hip.mask_resize_binarize(mask_gt[i].contiguous().float(), ph, pw, ds)
+        hip.gt_masks_downsample(mask_gt[i].contiguous().float(), ph, pw, ds)
         ds_masks.append(ds.reshape(g, ph * pw))
     return _MaskLossFn.apply(proto_p, coef_p, anchor_box.contiguous().float(), anchor_gt.contiguous(), idx, ds_masks,
                              num_pos.contiguous(), cfg.mask_alpha / ph / pw)
@@ -191,7 +191,7 @@ class _SemanticLossFn(torch.autograd.Function):
         ds_i, cls_i, at = [], [], 0
         for i in range(b):
             if gs[i]:
-                hip.mask_resize_binarize(mask_gt[i].contiguous().float(), mh, mw, ds[at:at + gs[i]])
+                hip.gt_masks_downsample(mask_gt[i].contiguous().float(), mh, mw, ds[at:at + gs[i]])
             ds_i.append(ds[at:at + gs[i]] if gs[i] else ds[:0])
             cls_i.append(cls[at:at + gs[i]] if gs[i] else cls[:0])
             at += gs[i]
