@@ -597,7 +597,8 @@ int ym_boxes_to_pixels(float* boxes_f, int32_t* boxes_px, int n, float S, ym_str
  * crop, bilinear resize to S = max(img_h, img_w), > 0.5, slice — fused, the [n][Hp][Wp] soft masks never reach HBM — plus the
  * in-place box scaling + truncation.  proto [B][Hp][Wp][32]; coefs [B][max_det][32], boxes [B][max_det][4] (scaled IN PLACE),
  * counts int32[B] on the DEVICE (NULL = every image has max_det detections; B = 1 with max_det = n is the single-image call);
- * masks [B][max_det][img_h][img_w] (only slots < count are written), boxes_px int32 [B][max_det][4].
+ * masks [B][max_det][img_h][img_w] (only slots < count are written, on the fused and on the two-kernel path), boxes_px int32
+ * [B][max_det][4].
  * workspace >= ym_after_nms_batch_workspace_bytes(...) (0 unless the image is much smaller than the prototype map). */
 size_t ym_after_nms_batch_workspace_bytes(int max_det, int Hp, int Wp, int img_h, int img_w);
 int ym_after_nms_batch(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
@@ -676,8 +677,9 @@ int ym_unpack_masks(const uint64_t* bits, int n, int H, int W, float* masks, ym_
  * height x odd width would leave the next block misaligned), `masks` itself is 16-byte aligned, blocks do not overlap: YM_EINVAL
  * otherwise.  One fused launch covers every image whose scale fits the fused kernel (grid = largest tile count x max_det x B; tiles
  * and slots an image does not have exit at once); images much smaller than the prototype map (max(h, w) under about 2.7x its side)
- * take the uniform entry's two-kernel path one by one through `workspace` >= ym_after_nms_ragged_workspace_bytes(...) (0 when every
- * image fits; also 0 for arguments the entries would refuse). */
+ * take the two-kernel path (ym_mask_assemble, then the resize bounded by counts[b] on the device: the launch set all four entries
+ * share) one by one through `workspace` >= ym_after_nms_ragged_workspace_bytes(...) (0 when every image fits; also 0 for arguments
+ * the entries would refuse). */
 #define YM_RAGGED_MAX_IMAGES 32
 #define YM_RAGGED_ALIGN_BYTES 256
 typedef struct ym_ragged_image {

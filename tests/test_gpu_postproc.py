@@ -357,3 +357,46 @@ def test_fused_after_nms_matches_the_two_kernel_path():
             up = torch.nn.functional.interpolate(soft[None], (max(h, w), max(h, w)), mode='bilinear', align_corners=False)[0][:, :h, :w]
             assert float((up[diff] - 0.5).abs().max()) < 1e-5
         assert float(diff.float().mean()) < 1e-5
+
+
+@pytest.mark.parametrize('hw', [(48, 70), (97, 301)], ids=['two_kernel', 'fused'])
+@pytest.mark.parametrize('packed', [False, True], ids=['dense', 'packed'])
+def test_uniform_entry_writes_only_the_rows_below_the_count(packed, hw):
+    """`ym_after_nms_batch[_packed]` itself on buffers prefilled with 0xA5, device counts [5, 0, 2] of max_det = 5, at a 32 x 32
+    prototype map: 48 x 70 takes the two-kernel path (256 * 32 / 70 + 3 = 120 > 96 patch columns), 97 x 301 the fused kernel.
+    (1) every mask row at or past its image's count still holds the fill, (2) every row below it is bit-equal to `after_nms` on that
+    image alone, (3) with counts = NULL all 5 rows of every image are written.  Before the four entries shared one launch set the
+    48 x 70 case failed on (1): the uniform two-kernel path resized all max_det rows whatever the count."""
+    from yolact_minimal_amd import hip
+    from yolact_minimal_amd.utils.output_utils import after_nms
+    h, w = hw
+    B, md, counts = 3, 5, (5, 0, 2)
+    L = hip.lib()
+    nbytes = L.ym_after_nms_batch_workspace_bytes(md, 32, 32, h, w)
+    assert nbytes == (md * 32 * 32 * 4 if hw == (48, 70) else 0)              # the path this case is here for
+    g = torch.Generator().manual_seed(23)
+    proto = torch.relu(torch.randn(B, 32, 32, 32, generator=g)).to(DEV)
+    coef = torch.tanh(torch.randn(B, md, 32, generator=g)).to(DEV)
+    xy = torch.rand(B, md, 2, generator=g) * 0.5
+    boxes_in = torch.cat([xy, xy + 0.2 + torch.rand(B, md, 2, generator=g) * 0.3], 2).to(DEV)
+    cols, dtype = ((w + 63) // 64, torch.int64) if packed else (w, torch.float32)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
+    fn = L.ym_after_nms_batch_packed if packed else L.ym_after_nms_batch
+    ids, sc = torch.zeros(md, dtype=torch.int64, device=DEV), torch.ones(md, device=DEV)
+    want = [after_nms(ids, sc, boxes_in[b].clone(), coef[b], proto[b], h, w, packed=packed)[2:] for b in range(B)]
+    for cnt in (torch.tensor(counts, dtype=torch.int32, device=DEV), None):
+        boxes = boxes_in.clone()
+        buf = torch.full((B * md * h * cols * (8 if packed else 4),), 0xA5, dtype=torch.uint8, device=DEV)
+        px = torch.full((B * md * 4 * 4,), 0xA5, dtype=torch.uint8, device=DEV)
+        hip.check(fn(hip.ptr(proto), hip.ptr(coef), hip.ptr(boxes), hip.ptr(cnt, torch.int32), B, md, 32, 32, 32, h, w, 1,
+                     ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(px.data_ptr()), ctypes.c_void_p(ws.data_ptr()), nbytes,
+                     hip.stream_ptr()), 'ym_after_nms_batch')
+        torch.cuda.synchronize()
+        rows = buf.view(B, md, -1)                                             # the bytes of every mask row
+        masks, box_px = buf.view(dtype).view(B, md, h, cols), px.view(torch.int32).view(B, md, 4)
+        for b, n in enumerate(counts if cnt is not None else (md,) * B):
+            assert bool((rows[b, n:] == 0xA5).all()), f'image {b}: rows at or past its count {n} were written'
+            wpx, wm = want[b]
+            assert torch.equal(masks[b, :n], (wm.bits if packed else wm)[:n]), f'image {b}: rows below its count {n}'
+            assert torch.equal(box_px[b, :n], wpx[:n])
+        assert torch.equal(boxes, boxes_in * float(max(h, w))) and torch.equal(box_px, boxes.int())     # every slot's box, in place

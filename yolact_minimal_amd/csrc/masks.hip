@@ -6,12 +6,16 @@
 //                    Both operands are K-contiguous in HBM ([.][32] floats), so lane half h reads k = 8g+4h..+3
 //                    as one 16-byte global load per group g — no LDS staging at all (K = 32 fits in registers).
 //                    Algorithmic bytes: P*32*4 (proto, read once) + n*P*4 (masks, written once): HBM-bound.
-//  k_mask_resize   : bilinear (align_corners=False) to S x S, > 0.5, cropped to img_h x img_w; the output
-//                    (n*img_h*img_w*4 B) dominates, written with 16-byte stores.
-//  k_masks_fused    : after_nms in one launch (below);  k_masks_fused_packed / k_mask_resize_packed: the same pixels written as
-//                    1 bit each (one ballot = one 64-pixel word), k_pack_masks / k_unpack_masks: dense <-> bits.
+//  k_mask_resize<PACKED> : bilinear (align_corners=False) to S x S, > 0.5, cropped to img_h x img_w; the dense output
+//                    (n*img_h*img_w*4 B) dominates, written with 16-byte stores; PACKED: 1 bit per pixel (one ballot = one 64-pixel
+//                    word).  A device count, when given, bounds the rows.
+//  k_masks_fused<PACKED, Sizes> : after_nms in one launch (below), dense or bits, for one output size (UniformSizes) or one per image
+//                    (RaggedSizes); after_nms_launches<PACKED, Sizes> is the launch set of the four ym_after_nms_* entries, with
+//                    k_boxes_to_pixels_batch<Sizes> at its end.
+//  k_pack_masks / k_unpack_masks : dense <-> bits.
 #pragma clang fp contract(off)
 #include "ym_common.h"
+#include <algorithm>
 
 namespace {
 
@@ -83,48 +87,14 @@ __device__ __forceinline__ void src_coord(int dst, float scale, int in_sz, int& 
     l1 = src - (float)i0;
 }
 
-// (the body of k_mask_resize and of k_mask_resize_counted, whose n is the image's count on the device)
-__device__ __forceinline__ void resize_rows(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
-                                            float* __restrict__ out) {
-    const int S = img_h > img_w ? img_h : img_w;
-    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
-    const int wq = (img_w + 3) >> 2;
-    const size_t total = (size_t)n * img_h * wq;
-    const bool vec = (img_w & 3) == 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int xq = (int)(i % wq);
-        size_t t = i / wq;
-        const int y = (int)(t % img_h);
-        const int d = (int)(t / img_h);
-        int y0, y1; float ly;
-        src_coord(y, sy, Hp, y0, y1, ly);
-        const float hy = 1.f - ly;
-        const float* r0 = masks + ((size_t)d * Hp + y0) * Wp;
-        const float* r1 = masks + ((size_t)d * Hp + y1) * Wp;
-        float o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int x = xq * 4 + e;
-            int x0, x1; float lx;
-            src_coord(x < img_w ? x : img_w - 1, sx, Wp, x0, x1, lx);
-            const float hx = 1.f - lx;
-            const float v = hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
-            o[e] = v > 0.5f ? 1.f : 0.f;
-        }
-        float* dst = out + ((size_t)d * img_h + y) * img_w + xq * 4;
-        if (vec) {
-            *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (xq * 4 + e < img_w) dst[e] = o[e];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mask_resize(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h,
-                                                      int img_w, float* __restrict__ out) {
-    resize_rows(masks, n, Hp, Wp, img_h, img_w, out);
+// Is the soft mask, interpolated between source rows r0 / r1 (weights 1 - ly / ly) at output column x, foreground?  THE expression of
+// every resize below, dense or packed, from HBM or from the fused kernel's LDS patch: they agree bit for bit because it is written once.
+__device__ __forceinline__ bool fg_at(const float* r0, const float* r1, float ly, int x, int img_w, float sx, int Wp) {
+    int x0, x1; float lx;
+    src_coord(x < img_w ? x : img_w - 1, sx, Wp, x0, x1, lx);
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const float v = hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
+    return v > 0.5f;
 }
 
 __device__ __forceinline__ int clamped_count(const int32_t* count, int max_det) {
@@ -132,11 +102,50 @@ __device__ __forceinline__ int clamped_count(const int32_t* count, int max_det) 
     return n < 0 ? 0 : (n > max_det ? max_det : n);
 }
 
-// the ragged entry's fallback: rows at or past the image's count are not written
-__global__ __launch_bounds__(256) void k_mask_resize_counted(const float* __restrict__ masks, const int32_t* __restrict__ count,
-                                                              int max_det, int Hp, int Wp, int img_h, int img_w,
-                                                              float* __restrict__ out) {
-    resize_rows(masks, clamped_count(count, max_det), Hp, Wp, img_h, img_w, out);
+template <bool PACKED> struct mask_elem { typedef float type; };
+template <> struct mask_elem<true> { typedef unsigned long long type; };
+
+// The two-kernel path's resize of n soft masks.  An item is 4 consecutive pixels of a thread (dense: one 16-byte store) or the 64 of
+// a wave (PACKED: lane = pixel, one ballot = one word), grid-strided.  `count` (nullable): the image's count on the device bounds n,
+// so rows at or past it are not written.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_mask_resize(const float* __restrict__ masks, const int32_t* __restrict__ count, int n, int Hp,
+                                                      int Wp, int img_h, int img_w, typename mask_elem<PACKED>::type* __restrict__ out) {
+    n = count ? clamped_count(count, n) : n;
+    constexpr int LG = PACKED ? 6 : 2, PER_BLOCK = PACKED ? 4 : 256;
+    const int S = img_h > img_w ? img_h : img_w;
+    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
+    const int wq = (img_w + (1 << LG) - 1) >> LG;
+    const size_t total = (size_t)n * img_h * wq;
+    const size_t first = (size_t)blockIdx.x * PER_BLOCK + (PACKED ? threadIdx.x >> 6 : threadIdx.x);
+    for (size_t i = first; i < total; i += (size_t)gridDim.x * PER_BLOCK) {
+        const int xq = (int)(i % wq);
+        size_t t = i / wq;
+        const int y = (int)(t % img_h);
+        const int d = (int)(t / img_h);
+        int y0, y1; float ly;
+        src_coord(y, sy, Hp, y0, y1, ly);
+        const float* r0 = masks + ((size_t)d * Hp + y0) * Wp;
+        const float* r1 = masks + ((size_t)d * Hp + y1) * Wp;
+        if constexpr (PACKED) {
+            const int lane = threadIdx.x & 63, x = xq * 64 + lane;
+            const bool fg = fg_at(r0, r1, ly, x, img_w, sx, Wp);
+            const unsigned long long w = __ballot(x < img_w && fg);
+            if (lane == 0) out[i] = w;
+        } else {
+            float o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = fg_at(r0, r1, ly, xq * 4 + e, img_w, sx, Wp) ? 1.f : 0.f;
+            float* dst = out + ((size_t)d * img_h + y) * img_w + xq * 4;
+            if ((img_w & 3) == 0) {
+                *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (xq * 4 + e < img_w) dst[e] = o[e];
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -153,10 +162,7 @@ __global__ __launch_bounds__(256) void k_mask_resize_counted(const float* __rest
 constexpr int FT_W = 256, FT_H = 16;          // output tile: 64 lanes x float4 wide, 4 waves x 4 rows high
 constexpr int FP_W = 96, FP_H = 10;           // source patch capacity (floats): checked on the host against the scale
 
-template <bool PACKED> struct mask_elem { typedef float type; };
-template <> struct mask_elem<true> { typedef unsigned long long type; };
-
-// One FT_H x FT_W output tile of ONE detection: the body of the uniform kernels and of the ragged one.  `pimg` is the image's
+// One FT_H x FT_W output tile of ONE detection: the body of every instantiation of k_masks_fused.  `pimg` is the image's
 // prototype map, `coef` / `box` the detection's 32 coefficients / 4 box floats, `obase` the detection's mask ([img_h][img_w] floats or
 // [img_h][wq] words), `patch` / `cf` the workgroup's LDS.  PACKED only changes the lane -> pixel map and the store (below).
 template <bool PACKED>
@@ -242,7 +248,6 @@ __device__ __forceinline__ void fused_tile(float* patch, float* cf, const float*
         if (!PACKED && x >= img_w) continue;
         int y0, y1i; float ly;
         src_coord(y, sy, Hp, y0, y1i, ly);
-        const float hy = 1.f - ly;
         const float* r0 = patch + (y0 - py0) * FP_W - px0;
         const float* r1 = patch + (y1i - py0) * FP_W - px0;
         if constexpr (PACKED) {
@@ -251,23 +256,14 @@ __device__ __forceinline__ void fused_tile(float* patch, float* cf, const float*
             for (int e = 0; e < 4; ++e) {
                 if (ox0 + 64 * e >= img_w) continue;             // (wave-uniform: this word does not exist)
                 const int xe = ox0 + 64 * e + lane;
-                int x0, x1i; float lx;
-                src_coord(xe < img_w ? xe : img_w - 1, sx, Wp, x0, x1i, lx);
-                const float hx = 1.f - lx;
-                const float v = hy * (hx * r0[x0] + lx * r0[x1i]) + ly * (hx * r1[x0] + lx * r1[x1i]);
-                const unsigned long long w = __ballot(xe < img_w && v > 0.5f);
+                const bool fg = fg_at(r0, r1, ly, xe, img_w, sx, Wp);
+                const unsigned long long w = __ballot(xe < img_w && fg);
                 mine = lane == r * 4 + e ? w : mine;
             }
         } else {
             float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int x0, x1i; float lx;
-                src_coord(x + e < img_w ? x + e : img_w - 1, sx, Wp, x0, x1i, lx);
-                const float hx = 1.f - lx;
-                const float v = hy * (hx * r0[x0] + lx * r0[x1i]) + ly * (hx * r1[x0] + lx * r1[x1i]);
-                o[e] = v > 0.5f ? 1.f : 0.f;
-            }
+            for (int e = 0; e < 4; ++e) o[e] = fg_at(r0, r1, ly, x + e, img_w, sx, Wp) ? 1.f : 0.f;
             float* dst = obase + (size_t)y * img_w + x;
             if (vec) *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
             else
@@ -279,105 +275,70 @@ __device__ __forceinline__ void fused_tile(float* patch, float* cf, const float*
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Where a launch set's output sizes come from: a small object that travels to the kernels BY VALUE in their arguments (no copy, no
+// synchronisation per call) and is indexed by blockIdx.z, which is uniform, so its words come from the argument segment with scalar
+// loads.  The host asks it the same questions: image b's size, the first element of slot d of its mask block (`base`), whether it takes
+// the fused kernel.
+//   UniformSizes: one img_h x img_w for every image, block b right behind block b - 1; any B up to the grid's 65535.
+//   RaggedSizes : ym_after_nms_ragged's per-image {img_h, img_w, offset} table (B <= YM_RAGGED_MAX_IMAGES) and the images that fit the
+//                 fused kernel (bit b of `fused_bits`).  grid.x is the largest tile count of the batch: an image that takes the
+//                 two-kernel path, and tiles past an image's own count, have nothing to do.
+// Bit-packed output (include/yolact_hip.h "bit-packed instance masks"): a row is wq = ceil(img_w / 64) uint64 instead of img_w floats.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <bool PACKED> __host__ __device__ inline size_t mask_row(int img_w) { return PACKED ? (size_t)((img_w + 63) >> 6) : (size_t)img_w; }
+__host__ __device__ inline int fused_tiles(int img_h, int img_w) { return ((img_w + FT_W - 1) / FT_W) * ((img_h + FT_H - 1) / FT_H); }
+
+// Does the fused kernel's LDS patch hold the source pixels of one output tile at this scale?
+bool fused_fits(int Hp, int Wp, int img_h, int img_w) {
+    const int S = img_h > img_w ? img_h : img_w;
+    const double sy = (double)Hp / S, sx = (double)Wp / S;
+    return (int)(FT_H * sy) + 3 <= FP_H && (int)(FT_W * sx) + 3 <= FP_W;
+}
+
+struct UniformSizes {
+    // (one vector, not two ints: the optimiser reads an 8-byte struct of two ints from the argument segment as ONE 64-bit integer and
+    // then no longer sees two sign-extended 32-bit values, which costs the dense kernel ~60 instructions of 64-bit address multiplies)
+    typedef int i32x2 __attribute__((ext_vector_type(2)));
+    i32x2 hw;                                  // {img_h, img_w}
+    __host__ __device__ int h(int) const { return hw[0]; }
+    __host__ __device__ int w(int) const { return hw[1]; }
+    template <bool PACKED> __host__ __device__ size_t base(int b, int max_det, int d = 0) const { return ((size_t)b * max_det + d) * (size_t)hw[0] * mask_row<PACKED>(hw[1]); }
+    bool fused(int, int Hp, int Wp) const { return fused_fits(Hp, Wp, hw[0], hw[1]); }
+    __device__ bool nothing_to_do(int, int) const { return false; }
+};
+
+struct RaggedTable { ym_ragged_image img[YM_RAGGED_MAX_IMAGES]; };
+struct RaggedSizes {
+    RaggedTable tab;
+    unsigned fused_bits;
+    __host__ __device__ int h(int b) const { return tab.img[b].img_h; }
+    __host__ __device__ int w(int b) const { return tab.img[b].img_w; }
+    template <bool PACKED> __host__ __device__ size_t base(int b, int, int d = 0) const { return (size_t)tab.img[b].offset + (size_t)d * h(b) * mask_row<PACKED>(w(b)); }
+    __host__ __device__ bool fused(int b, int = 0, int = 0) const { return (fused_bits >> b) & 1u; }
+    __device__ bool nothing_to_do(int b, int tile) const { return !fused(b) || tile >= fused_tiles(h(b), w(b)); }
+};
+
+// The same pixels as bits are the same kernel with another lane -> pixel map and another store (fused_tile<true>): the tile, the LDS
+// patch and every floating-point expression are the dense kernel's, so a bit equals (dense value != 0).  A lane owns pixels ox0 + 64e +
+// lane (e = 0..3) of its wave's four rows: one ballot per (row, e) IS one word, lane k < 16 keeps word k and the wave's 16 words leave
+// as one 8-byte store per lane (four 32-byte row pieces).  A tile outside the crop window stores its 16 x 4 zero words (512 B) and
+// exits; the dense [n][img_h][img_w] tensor exists nowhere.
+template <bool PACKED, class Sizes>
 __global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ proto, const float* __restrict__ coefs,
                                                       const float* __restrict__ boxes, const int32_t* __restrict__ counts,
-                                                      int max_det, int Hp, int Wp, int img_h, int img_w, int do_crop,
-                                                      float* __restrict__ out) {
+                                                      int max_det, int Hp, int Wp, const Sizes sz, int do_crop,
+                                                      typename mask_elem<PACKED>::type* __restrict__ out) {
     __shared__ float patch[FP_H * FP_W];
     __shared__ __attribute__((aligned(16))) float cf[32];
     const int b = blockIdx.z, d = blockIdx.y;
+    if (sz.nothing_to_do(b, blockIdx.x)) return;
+    const int img_h = sz.h(b), img_w = sz.w(b);
     const int n = counts ? counts[b] : max_det;
     if (d >= n) return;
     const size_t slot = (size_t)b * max_det + d;
-    fused_tile<false>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, img_h, img_w,
-                      do_crop, out + slot * (size_t)img_h * img_w);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Bit-packed output (include/yolact_hip.h "bit-packed instance masks"): bits [slot][img_h][wq] uint64, wq = ceil(img_w / 64), bit k
-// of word j of row y = pixel (y, 64j + k), bits at x >= img_w zero.  k_masks_fused_packed is k_masks_fused with another lane ->
-// pixel map and another store (fused_tile<true>): the tile, the LDS patch and every floating-point expression are the dense kernel's,
-// so a bit equals (dense value != 0).  A lane owns pixels ox0 + 64e + lane (e = 0..3) of its wave's four rows: one ballot per (row, e)
-// IS one word, lane k < 16 keeps word k and the wave's 16 words leave as one 8-byte store per lane (four 32-byte row pieces).  A tile
-// outside the crop window stores its 16 x 4 zero words (512 B) and exits; the dense [n][img_h][img_w] tensor exists nowhere.
-// ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_masks_fused_packed(const float* __restrict__ proto, const float* __restrict__ coefs,
-                                                             const float* __restrict__ boxes, const int32_t* __restrict__ counts,
-                                                             int max_det, int Hp, int Wp, int img_h, int img_w, int do_crop,
-                                                             unsigned long long* __restrict__ out) {
-    __shared__ float patch[FP_H * FP_W];
-    __shared__ __attribute__((aligned(16))) float cf[32];
-    const int b = blockIdx.z, d = blockIdx.y;
-    const int n = counts ? counts[b] : max_det;
-    if (d >= n) return;
-    const size_t slot = (size_t)b * max_det + d;
-    fused_tile<true>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, img_h, img_w,
-                     do_crop, out + slot * (size_t)img_h * ((img_w + 63) >> 6));
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The same tiles for a batch whose images differ in size (ym_after_nms_ragged): the per-image {img_h, img_w, offset} table arrives BY
-// VALUE in the kernel arguments (no copy, no synchronisation per call) and is indexed by blockIdx.z, which is uniform, so the three
-// words come from the argument segment with scalar loads.  grid.x is the largest tile count of the batch: tiles past an image's own
-// count exit at once, like detection slots past its count and images that take the two-kernel path (bit b of `fused` clear).
-// ---------------------------------------------------------------------------------------------------------------------------
-struct RaggedTable { ym_ragged_image img[YM_RAGGED_MAX_IMAGES]; };
-
-template <bool PACKED>
-__global__ __launch_bounds__(256) void k_masks_fused_ragged(const float* __restrict__ proto, const float* __restrict__ coefs,
-                                                             const float* __restrict__ boxes, const int32_t* __restrict__ counts,
-                                                             int max_det, int Hp, int Wp, const RaggedTable tab, unsigned fused, int do_crop,
-                                                             typename mask_elem<PACKED>::type* __restrict__ out) {
-    __shared__ float patch[FP_H * FP_W];
-    __shared__ __attribute__((aligned(16))) float cf[32];
-    const int b = blockIdx.z, d = blockIdx.y;
-    if (!((fused >> b) & 1u)) return;
-    const int img_h = tab.img[b].img_h, img_w = tab.img[b].img_w;
-    if ((int)blockIdx.x >= ((img_w + FT_W - 1) / FT_W) * ((img_h + FT_H - 1) / FT_H)) return;
-    const int n = counts ? counts[b] : max_det;
-    if (d >= n) return;
-    const size_t slot = (size_t)b * max_det + d;
-    const size_t row = PACKED ? (size_t)((img_w + 63) >> 6) : (size_t)img_w;
     fused_tile<PACKED>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, img_h, img_w,
-                       do_crop, out + (size_t)tab.img[b].offset + (size_t)d * img_h * row);
-}
-
-// the two-kernel path's resize with packed output: a wave per word, lane = pixel (k_mask_resize's expression per pixel)
-__device__ __forceinline__ void resize_rows_packed(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
-                                                   unsigned long long* __restrict__ out) {
-    const int S = img_h > img_w ? img_h : img_w;
-    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
-    const int wq = (img_w + 63) >> 6, lane = threadIdx.x & 63;
-    const size_t total = (size_t)n * img_h * wq;
-    for (size_t i = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < total; i += (size_t)gridDim.x * 4) {
-        const int j = (int)(i % wq);
-        size_t t = i / wq;
-        const int y = (int)(t % img_h);
-        const int d = (int)(t / img_h);
-        int y0, y1; float ly;
-        src_coord(y, sy, Hp, y0, y1, ly);
-        const float hy = 1.f - ly;
-        const float* r0 = masks + ((size_t)d * Hp + y0) * Wp;
-        const float* r1 = masks + ((size_t)d * Hp + y1) * Wp;
-        const int x = j * 64 + lane;
-        int x0, x1; float lx;
-        src_coord(x < img_w ? x : img_w - 1, sx, Wp, x0, x1, lx);
-        const float hx = 1.f - lx;
-        const float v = hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
-        const unsigned long long w = __ballot(x < img_w && v > 0.5f);
-        if (lane == 0) out[i] = w;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mask_resize_packed(const float* __restrict__ masks, int n, int Hp, int Wp, int img_h, int img_w,
-                                                             unsigned long long* __restrict__ out) {
-    resize_rows_packed(masks, n, Hp, Wp, img_h, img_w, out);
-}
-
-__global__ __launch_bounds__(256) void k_mask_resize_packed_counted(const float* __restrict__ masks, const int32_t* __restrict__ count,
-                                                                     int max_det, int Hp, int Wp, int img_h, int img_w,
-                                                                     unsigned long long* __restrict__ out) {
-    resize_rows_packed(masks, clamped_count(count, max_det), Hp, Wp, img_h, img_w, out);
+                       do_crop, out + sz.template base<PACKED>(b, max_det, d));
 }
 
 // dense {0, nonzero} rows -> words.  A wave takes PK consecutive words of the flat [rows][wq] output (PK row pieces of 64 pixels in
@@ -433,11 +394,12 @@ __global__ void k_boxes_to_pixels(float* boxes, int32_t* px, int count, float S)
     }
 }
 
-// grid.y = image: its own S = max(img_h, img_w)
-__global__ void k_boxes_to_pixels_ragged(float* boxes, int32_t* px, int per_image, const RaggedTable tab) {
+// the four after_nms entries: grid.y = image, scaled by its own S = max(img_h, img_w)
+template <class Sizes>
+__global__ void k_boxes_to_pixels_batch(float* boxes, int32_t* px, int per_image, const Sizes sz) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (i < per_image) {
-        const int h = tab.img[b].img_h, w = tab.img[b].img_w;
+        const int h = sz.h(b), w = sz.w(b);
         const size_t at = (size_t)b * per_image + i;
         const float v = boxes[at] * (float)(h > w ? h : w);
         boxes[at] = v;
@@ -460,15 +422,22 @@ extern "C" int ym_mask_assemble(const float* proto, const float* coefs, const fl
     return ym_check_launch("mask_assemble");
 }
 
+// n soft masks (the device count, when given, bounds n) -> img_h x img_w binary masks, dense or packed
+template <bool PACKED>
+static void launch_resize(const float* masks, const int32_t* count, int n, int Hp, int Wp, int img_h, int img_w,
+                          typename mask_elem<PACKED>::type* out, hipStream_t st) {
+    const size_t items = PACKED ? ((size_t)n * img_h * ym_cdiv(img_w, 64) + 3) / 4       // a wave per word
+                                : ((size_t)n * img_h * ((img_w + 3) / 4) + 255) / 256;   // a thread per 4 pixels
+    hipLaunchKernelGGL(k_mask_resize<PACKED>, dim3((int)(items > 16384 ? 16384 : items)), dim3(256), 0, st, masks, count, n, Hp, Wp,
+                       img_h, img_w, out);
+}
+
 extern "C" int ym_mask_resize_binarize(const float* masks, int n, int Hp, int Wp, int img_h, int img_w, float* out,
                                        ym_stream_t s) {
     YM_REQUIRE(n >= 0 && Hp > 0 && Wp > 0 && img_h > 0 && img_w > 0, "mask_resize: bad shape");
     if (n == 0) return YM_OK;
     YM_REQUIRE(masks && out, "mask_resize: null pointer");
-    const size_t total = (size_t)n * img_h * ((img_w + 3) / 4);
-    size_t grid = (total + 255) / 256;
-    if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(k_mask_resize, dim3((int)grid), dim3(256), 0, (hipStream_t)s, masks, n, Hp, Wp, img_h, img_w, out);
+    launch_resize<false>(masks, nullptr, n, Hp, Wp, img_h, img_w, out, (hipStream_t)s);
     return ym_check_launch("mask_resize");
 }
 
@@ -480,11 +449,38 @@ extern "C" int ym_boxes_to_pixels(float* boxes_f, int32_t* boxes_px, int n, floa
     return ym_check_launch("boxes_to_pixels");
 }
 
-// Does the fused kernel's LDS patch hold the source pixels of one output tile at this scale?
-static bool fused_fits(int Hp, int Wp, int img_h, int img_w) {
-    const int S = img_h > img_w ? img_h : img_w;
-    const double sy = (double)Hp / S, sx = (double)Wp / S;
-    return (int)(FT_H * sy) + 3 <= FP_H && (int)(FT_W * sx) + 3 <= FP_W;
+// The launch set of the four after_nms entries (arguments checked by the caller; `what` names the entry in errors): ONE fused launch
+// over every image whose scale fits it, then image by image the strongly down-scaled ones (image smaller than ~2.7x the prototype
+// map) on the two-kernel path through a soft-mask scratch, then the box scaling.  Either way only the rows below counts[b] are
+// written (all max_det without counts): the fused kernel's slots past the count exit, and the resize reads the count on the device.
+template <bool PACKED, class Sizes>
+static int after_nms_launches(const char* what, const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B,
+                              int max_det, int Hp, int Wp, int K, const Sizes& sz, int do_crop, typename mask_elem<PACKED>::type* masks,
+                              int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    hipStream_t st = (hipStream_t)s;
+    int tiles = 0;
+    for (int b = 0; b < B; ++b)
+        if (sz.fused(b, Hp, Wp)) tiles = std::max(tiles, fused_tiles(sz.h(b), sz.w(b)));
+    if (tiles)
+        hipLaunchKernelGGL((k_masks_fused<PACKED, Sizes>), dim3(tiles, max_det, B), dim3(256), 0, st, proto, coefs, boxes, counts, max_det,
+                           Hp, Wp, sz, do_crop, masks);
+    for (int b = 0; b < B; ++b) {
+        if (sz.fused(b, Hp, Wp)) continue;
+        const size_t soft_bytes = (size_t)max_det * Hp * Wp * sizeof(float);
+        if (!workspace || workspace_bytes < soft_bytes) { ym_set_error("%s: workspace %zu B < %zu B", what, workspace_bytes, soft_bytes); return YM_ENOSPC; }
+        const size_t slot = (size_t)b * max_det;
+        const int rc = ym_mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, K, do_crop,
+                                        (float*)workspace, s);
+        if (rc != YM_OK) return rc;
+        launch_resize<PACKED>((const float*)workspace, counts ? counts + b : nullptr, max_det, Hp, Wp, sz.h(b), sz.w(b),
+                              masks + sz.template base<PACKED>(b, max_det), st);
+    }
+    hipLaunchKernelGGL(k_boxes_to_pixels_batch<Sizes>, dim3(ym_cdiv(max_det * 4, 256), B), dim3(256), 0, st, boxes, boxes_px, max_det * 4, sz);
+    return ym_check_launch(what);
+}
+
+extern "C" size_t ym_after_nms_batch_workspace_bytes(int max_det, int Hp, int Wp, int img_h, int img_w) {
+    return fused_fits(Hp, Wp, img_h, img_w) ? 0 : (size_t)max_det * Hp * Wp * sizeof(float);
 }
 
 extern "C" int ym_after_nms_batch(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
@@ -493,32 +489,8 @@ extern "C" int ym_after_nms_batch(const float* proto, const float* coefs, float*
     YM_REQUIRE(K == 32, "after_nms: coefficient dim must be 32, got %d", K);
     YM_REQUIRE(B >= 1 && B <= 65535 && max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0 && img_h > 0 && img_w > 0, "after_nms: bad shape");
     YM_REQUIRE(proto && coefs && boxes && masks && boxes_px, "after_nms: null pointer");
-    hipStream_t st = (hipStream_t)s;
-    if (fused_fits(Hp, Wp, img_h, img_w)) {
-        const int tiles = ym_cdiv(img_w, FT_W) * ym_cdiv(img_h, FT_H);
-        hipLaunchKernelGGL(k_masks_fused, dim3(tiles, max_det, B), dim3(256), 0, st, proto, coefs, boxes, counts, max_det, Hp, Wp,
-                           img_h, img_w, do_crop, masks);
-    } else {
-        // strong down-scaling (image smaller than ~2.7x the prototype map): the two-kernel path through a soft-mask scratch
-        const size_t soft_bytes = (size_t)max_det * Hp * Wp * sizeof(float);
-        if (!workspace || workspace_bytes < soft_bytes) { ym_set_error("after_nms: workspace %zu B < %zu B", workspace_bytes, soft_bytes); return YM_ENOSPC; }
-        for (int b = 0; b < B; ++b) {   // (all max_det slots: rows past the count are garbage the caller never reads)
-            const size_t slot = (size_t)b * max_det;
-            int rc = ym_mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, K, do_crop,
-                                      (float*)workspace, s);
-            if (rc != YM_OK) return rc;
-            rc = ym_mask_resize_binarize((const float*)workspace, max_det, Hp, Wp, img_h, img_w, masks + slot * (size_t)img_h * img_w, s);
-            if (rc != YM_OK) return rc;
-        }
-    }
-    const int S = img_h > img_w ? img_h : img_w;
-    const int cnt = B * max_det * 4;
-    hipLaunchKernelGGL(k_boxes_to_pixels, dim3(ym_cdiv(cnt, 256)), dim3(256), 0, st, boxes, boxes_px, cnt, (float)S);
-    return ym_check_launch("after_nms_batch");
-}
-
-extern "C" size_t ym_after_nms_batch_workspace_bytes(int max_det, int Hp, int Wp, int img_h, int img_w) {
-    return fused_fits(Hp, Wp, img_h, img_w) ? 0 : (size_t)max_det * Hp * Wp * sizeof(float);
+    return after_nms_launches<false>("after_nms", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, UniformSizes{{img_h, img_w}}, do_crop, masks,
+                                     boxes_px, workspace, workspace_bytes, s);
 }
 
 extern "C" int ym_after_nms_batch_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
@@ -527,31 +499,8 @@ extern "C" int ym_after_nms_batch_packed(const float* proto, const float* coefs,
     YM_REQUIRE(K == 32, "after_nms_packed: coefficient dim must be 32, got %d", K);
     YM_REQUIRE(B >= 1 && B <= 65535 && max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0 && img_h > 0 && img_w > 0, "after_nms_packed: bad shape");
     YM_REQUIRE(proto && coefs && boxes && mask_bits && boxes_px, "after_nms_packed: null pointer");
-    hipStream_t st = (hipStream_t)s;
-    unsigned long long* bits = reinterpret_cast<unsigned long long*>(mask_bits);
-    const int wq = ym_cdiv(img_w, 64);
-    if (fused_fits(Hp, Wp, img_h, img_w)) {
-        const int tiles = ym_cdiv(img_w, FT_W) * ym_cdiv(img_h, FT_H);
-        hipLaunchKernelGGL(k_masks_fused_packed, dim3(tiles, max_det, B), dim3(256), 0, st, proto, coefs, boxes, counts, max_det, Hp, Wp,
-                           img_h, img_w, do_crop, bits);
-    } else {
-        const size_t soft_bytes = (size_t)max_det * Hp * Wp * sizeof(float);
-        if (!workspace || workspace_bytes < soft_bytes) { ym_set_error("after_nms_packed: workspace %zu B < %zu B", workspace_bytes, soft_bytes); return YM_ENOSPC; }
-        const size_t words = (size_t)max_det * img_h * wq;
-        const int grid = (int)((words + 3) / 4 > 16384 ? 16384 : (words + 3) / 4);     // a wave per word, grid-strided
-        for (int b = 0; b < B; ++b) {
-            const size_t slot = (size_t)b * max_det;
-            int rc = ym_mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, K, do_crop,
-                                      (float*)workspace, s);
-            if (rc != YM_OK) return rc;
-            hipLaunchKernelGGL(k_mask_resize_packed, dim3(grid), dim3(256), 0, st, (const float*)workspace, max_det, Hp, Wp, img_h, img_w,
-                               bits + slot * (size_t)img_h * wq);
-        }
-    }
-    const int S = img_h > img_w ? img_h : img_w;
-    const int cnt = B * max_det * 4;
-    hipLaunchKernelGGL(k_boxes_to_pixels, dim3(ym_cdiv(cnt, 256)), dim3(256), 0, st, boxes, boxes_px, cnt, (float)S);
-    return ym_check_launch("after_nms_batch_packed");
+    return after_nms_launches<true>("after_nms_packed", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, UniformSizes{{img_h, img_w}}, do_crop,
+                                    reinterpret_cast<unsigned long long*>(mask_bits), boxes_px, workspace, workspace_bytes, s);
 }
 
 // ---- batches whose images differ in size -----------------------------------------------------------------------------------------
@@ -591,46 +540,14 @@ static int after_nms_ragged(const char* what, const float* proto, const float* c
                             int Hp, int Wp, int K, const ym_ragged_image* images, int do_crop, typename mask_elem<PACKED>::type* masks,
                             int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
     YM_REQUIRE(K == 32, "%s: coefficient dim must be 32, got %d", what, K);
-    unsigned fused = 0u;
-    const int rc0 = ragged_check(what, images, B, max_det, Hp, Wp, PACKED, &fused);
-    if (rc0 != YM_OK) return rc0;
+    RaggedSizes sz = {};
+    const int rc = ragged_check(what, images, B, max_det, Hp, Wp, PACKED, &sz.fused_bits);
+    if (rc != YM_OK) return rc;
     YM_REQUIRE(proto && coefs && boxes && masks && boxes_px, "%s: null pointer", what);
     YM_REQUIRE(((uintptr_t)masks & 15) == 0, "%s: the mask buffer must be 16-byte aligned", what);
-    hipStream_t st = (hipStream_t)s;
-    RaggedTable tab = {};
-    int tiles = 0;
-    for (int b = 0; b < B; ++b) {
-        tab.img[b] = images[b];
-        const int t = ym_cdiv(images[b].img_w, FT_W) * ym_cdiv(images[b].img_h, FT_H);
-        if (((fused >> b) & 1u) && t > tiles) tiles = t;
-    }
-    if (tiles)
-        hipLaunchKernelGGL(k_masks_fused_ragged<PACKED>, dim3(tiles, max_det, B), dim3(256), 0, st, proto, coefs, boxes, counts, max_det, Hp, Wp,
-                           tab, fused, do_crop, masks);
-    for (int b = 0; b < B; ++b) {
-        if ((fused >> b) & 1u) continue;
-        // strong down-scaling: the two-kernel path of the uniform entry for this image, its resize bounded by the count on the device
-        const size_t soft_bytes = (size_t)max_det * Hp * Wp * sizeof(float);
-        if (!workspace || workspace_bytes < soft_bytes) { ym_set_error("%s: workspace %zu B < %zu B", what, workspace_bytes, soft_bytes); return YM_ENOSPC; }
-        const size_t slot = (size_t)b * max_det;
-        const int img_h = images[b].img_h, img_w = images[b].img_w;
-        const int rc = ym_mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, K, do_crop,
-                                        (float*)workspace, s);
-        if (rc != YM_OK) return rc;
-        const size_t items = PACKED ? ((size_t)max_det * img_h * ym_cdiv(img_w, 64) + 3) / 4      // a wave per word
-                                    : ((size_t)max_det * img_h * ((img_w + 3) / 4) + 255) / 256;  // a thread per 4 pixels
-        const int grid = (int)(items > 16384 ? 16384 : items);
-        typename mask_elem<PACKED>::type* dst = masks + images[b].offset;
-        if constexpr (PACKED) {
-            if (counts) hipLaunchKernelGGL(k_mask_resize_packed_counted, dim3(grid), dim3(256), 0, st, (const float*)workspace, counts + b, max_det, Hp, Wp, img_h, img_w, dst);
-            else hipLaunchKernelGGL(k_mask_resize_packed, dim3(grid), dim3(256), 0, st, (const float*)workspace, max_det, Hp, Wp, img_h, img_w, dst);
-        } else {
-            if (counts) hipLaunchKernelGGL(k_mask_resize_counted, dim3(grid), dim3(256), 0, st, (const float*)workspace, counts + b, max_det, Hp, Wp, img_h, img_w, dst);
-            else hipLaunchKernelGGL(k_mask_resize, dim3(grid), dim3(256), 0, st, (const float*)workspace, max_det, Hp, Wp, img_h, img_w, dst);
-        }
-    }
-    hipLaunchKernelGGL(k_boxes_to_pixels_ragged, dim3(ym_cdiv(max_det * 4, 256), B), dim3(256), 0, st, boxes, boxes_px, max_det * 4, tab);
-    return ym_check_launch(what);
+    std::copy(images, images + B, sz.tab.img);
+    return after_nms_launches<PACKED>(what, proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, sz, do_crop, masks, boxes_px, workspace,
+                                      workspace_bytes, s);
 }
 
 extern "C" int ym_after_nms_ragged(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,

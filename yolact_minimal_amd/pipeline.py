@@ -23,7 +23,7 @@ import warnings
 import torch
 
 from .engine import InferEngine
-from .utils.output_utils import nms_batch, after_nms_batch
+from .utils.output_utils import nms_batch, after_nms_batch, unpad_detections
 
 _streams = {}
 
@@ -146,18 +146,8 @@ class RequestPipeline:
         cur = torch.cuda.current_stream(self.device)
         for t in (ids, scores, box_px, masks[0] if isinstance(masks, list) else masks):   # (per-image views share one allocation)
             t.record_stream(cur)
-        out = []
-        for b, n in enumerate(self.counts_host[slot].tolist()):
-            if n == 0:
-                out.append((None, None, None, None))
-                continue
-            r = (ids[b, :n], scores[b, :n], box_px[b, :n], masks[b][:n])
-            if self.vt > 0:                               # detect.py's score filter, as in `after_nms` / `after_nms_batch(sync=True)`
-                keep = r[1] >= self.vt
-                r = tuple(t[keep] for t in r) if bool(keep.any()) else (None, None, None, None)
-            if r[0] is not None:
-                self.detections += int(r[0].shape[0])
-            out.append(r)
+        out = unpad_detections(ids, scores, box_px, masks, self.counts_host[slot].tolist(), self.vt)
+        self.detections += sum(int(r[0].shape[0]) for r in out if r[0] is not None)
         return out[0] if self.batch == 1 else out
 
     def submit(self, img, head_outputs=None, out_hw=None, consumer=None):

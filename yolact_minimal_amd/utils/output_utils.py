@@ -16,6 +16,7 @@ The only host<->device synchronisation is one 4-byte read of the detection count
 
 `draw_img` (`:327-369`), `draw_batch` and `cutout_mattes` are the device renderer of `utils/draw.py`, re-exported here.
 """
+import contextlib
 import ctypes
 import os
 
@@ -100,12 +101,6 @@ def _want_packed(cfg, packed):
     return bool(packed) or bool(cfg and getattr(cfg, 'packed_masks', False))
 
 
-def _new_masks(lead, img_h, img_w, device, packed):
-    if packed:
-        return torch.empty(*lead, img_h, (img_w + 63) // 64, dtype=torch.int64, device=device)
-    return torch.empty(*lead, img_h, img_w, dtype=torch.float32, device=device)
-
-
 def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, img_name=None, packed=False):
     if ids_p is None:
         return None, None, None, None
@@ -122,36 +117,60 @@ def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, im
     if cfg and getattr(cfg, 'save_lincomb', False):
         raise NotImplementedError('draw_lincomb (visualisation, reference output_utils.py:276-324) is out of scope')
 
-    device = proto_p.device
-    n = coef_p.shape[0]
-    hp, wp, k = proto_p.shape
     do_crop = not (cfg and getattr(cfg, 'no_crop', False))
     box_c = box_p if box_p.is_contiguous() else box_p.contiguous()
-    if packed and device.index == torch.cuda.current_device():
-        # (the tensors live on the current device: no device switch around the launch, as in nms_batch)
-        masks = torch.empty(n, img_h, (img_w + 63) >> 6, dtype=torch.int64, device=device)
-        box_px = torch.empty(n, 4, dtype=torch.int32, device=device)
-        _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, 1, n, hp, wp, k, img_h, img_w, do_crop, masks, box_px)
-    else:
-        with torch.cuda.device(device):
-            masks = _new_masks((n,), img_h, img_w, device, packed)
-            box_px = torch.empty(n, 4, dtype=torch.int32, device=device)
-            _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, 1, n, hp, wp, k, img_h, img_w, do_crop, masks, box_px)
+    masks, box_px = _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, (img_h, img_w), do_crop, packed)
     if box_c is not box_p:
         box_p.copy_(box_c)              # keep the reference's in-place scaling visible to the caller
-    return ids_p, class_p, box_px, PackedMasks._wrap(masks, img_h, img_w) if packed else masks
+    return ids_p, class_p, box_px, masks
 
 
-def _after_nms_launch(proto, coefs, boxes, counts, batch, max_det, hp, wp, k, img_h, img_w, do_crop, masks, box_px):
+_ragged_plans = {}
+_NO_SWITCH = contextlib.nullcontext()
+
+
+def _after_nms_launch(proto, coefs, boxes, counts, sizes, do_crop, packed):
+    """The launch set behind `after_nms` and both arms of `after_nms_batch`: allocates and returns `(masks, box_px)` for the
+    detections `coefs` [B, max_det, 32] / `boxes` (scaled in place) of `proto` [B, Hp, Wp, 32], or of ONE image without the
+    leading B.  `sizes` is one `(h, w)` for every image -- the uniform entries, masks `[B, max_det, h, w]` (packed: the words
+    `[B, max_det, h, ceil(w / 64)]`) -- or a LIST of B pairs -- `ym_after_nms_ragged[_packed]`, masks = a list of B views
+    `[max_det, h_b, w_b]` of one flat allocation (`ragged_layout`).  Packed masks come wrapped as `PackedMasks`."""
     L = hip.lib()
-    nbytes = L.ym_after_nms_batch_workspace_bytes(max_det, hp, wp, img_h, img_w)
-    ws = _scratch(proto.device, nbytes) if nbytes else None
-    # (int64 masks = the words of PackedMasks: the packed kernel, same arguments otherwise)
-    fn = L.ym_after_nms_batch_packed if masks.dtype == torch.int64 else L.ym_after_nms_batch
-    hip.check(fn(hip.ptr(proto), hip.ptr(coefs), hip.ptr(boxes), hip.ptr(counts, torch.int32) if counts is not None else None,
-                 batch, max_det, hp, wp, k, img_h, img_w, int(do_crop), hip.ptr(masks, masks.dtype), hip.ptr(box_px, torch.int32),
-                 ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes, hip.stream_ptr()),
-              'ym_after_nms_batch')
+    device = proto.device
+    *lead, k = coefs.shape
+    batch, md = lead if len(lead) == 2 else (1, lead[0])
+    *_, hp, wp, _ = proto.shape
+    ragged = isinstance(sizes, list)
+    if ragged:
+        key = (tuple(sizes), md, hp, wp, packed)
+        plan = _ragged_plans.get(key)
+        if plan is None:
+            offsets, total = ragged_layout(sizes, md, packed)
+            table = (hip.RaggedImage * batch)(*[hip.RaggedImage(h, w, o) for (h, w), o in zip(sizes, offsets)])
+            if len(_ragged_plans) >= 1024:
+                _ragged_plans.clear()
+            plan = _ragged_plans[key] = (offsets, total, table, L.ym_after_nms_ragged_workspace_bytes(table, batch, md, hp, wp))
+        offsets, total, table, nbytes = plan
+        shape, where = (total,), (table,)
+        fn, name = (L.ym_after_nms_ragged_packed if packed else L.ym_after_nms_ragged), 'ym_after_nms_ragged'
+    else:
+        img_h, img_w = sizes
+        nbytes = L.ym_after_nms_batch_workspace_bytes(md, hp, wp, img_h, img_w)
+        shape, where = (*lead, img_h, (img_w + 63) // 64 if packed else img_w), (img_h, img_w)     # (int64 words of PackedMasks)
+        fn, name = (L.ym_after_nms_batch_packed if packed else L.ym_after_nms_batch), 'ym_after_nms_batch'
+    # (tensors on the current device: no device switch around the launch, as in nms_batch)
+    with _NO_SWITCH if device.index == torch.cuda.current_device() else torch.cuda.device(device):
+        masks = torch.empty(*shape, dtype=torch.int64 if packed else torch.float32, device=device)
+        box_px = torch.empty(*lead, 4, dtype=torch.int32, device=device)
+        ws = _scratch(device, nbytes) if nbytes else None
+        hip.check(fn(hip.ptr(proto), hip.ptr(coefs), hip.ptr(boxes), hip.ptr(counts, torch.int32), batch, md, hp, wp, k, *where,
+                     int(do_crop), hip.ptr(masks, masks.dtype), hip.ptr(box_px, torch.int32),
+                     ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes, hip.stream_ptr()), name)
+    if not ragged:
+        return (PackedMasks._wrap(masks, img_h, img_w) if packed else masks), box_px
+    if packed:
+        return [PackedMasks._wrap(masks[o:o + md * h * ((w + 63) // 64)].view(md, h, -1), h, w) for (h, w), o in zip(sizes, offsets)], box_px
+    return [masks[o:o + md * h * w].view(md, h, w) for (h, w), o in zip(sizes, offsets)], box_px
 
 
 _scratch_bufs = {}
@@ -262,42 +281,6 @@ def ragged_layout(sizes, max_det, packed=False):
     return offsets, end
 
 
-_ragged_plans = {}
-
-
-def _after_nms_ragged(dets, sizes, do_crop, packed):
-    """The masks (a list of per-image views of one flat allocation) and pixel boxes of `after_nms_batch` with per-image sizes."""
-    device = dets.proto.device
-    batch, md = dets.ids.shape
-    _, hp, wp, k = dets.proto.shape
-    L = hip.lib()
-    key = (tuple(sizes), md, hp, wp, packed)
-    plan = _ragged_plans.get(key)
-    if plan is None:
-        offsets, total = ragged_layout(sizes, md, packed)
-        table = (hip.RaggedImage * batch)(*[hip.RaggedImage(h, w, o) for (h, w), o in zip(sizes, offsets)])
-        if len(_ragged_plans) >= 1024:
-            _ragged_plans.clear()
-        plan = _ragged_plans[key] = (offsets, total, table, L.ym_after_nms_ragged_workspace_bytes(table, batch, md, hp, wp))
-    offsets, total, table, nbytes = plan
-    with torch.cuda.device(device):
-        flat = torch.empty(total, dtype=torch.int64 if packed else torch.float32, device=device)
-        box_px = torch.empty(batch, md, 4, dtype=torch.int32, device=device)
-        ws = _scratch(device, nbytes) if nbytes else None
-        fn = L.ym_after_nms_ragged_packed if packed else L.ym_after_nms_ragged
-        hip.check(fn(hip.ptr(dets.proto.contiguous()), hip.ptr(dets.coefs), hip.ptr(dets.boxes), hip.ptr(dets.counts, torch.int32), batch, md,
-                     hp, wp, k, table, int(do_crop), hip.ptr(flat, flat.dtype), hip.ptr(box_px, torch.int32),
-                     ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes, hip.stream_ptr()), 'ym_after_nms_ragged')
-    masks = []
-    for (h, w), o in zip(sizes, offsets):
-        if packed:
-            wq = (w + 63) // 64
-            masks.append(PackedMasks._wrap(flat[o:o + md * h * wq].view(md, h, wq), h, w))
-        else:
-            masks.append(flat[o:o + md * h * w].view(md, h, w))
-    return masks, box_px
-
-
 def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
     """`after_nms` for every image of a `BatchDetections` in one launch set.  Returns a list of per-image 4-tuples like `after_nms`
     -- or, with `sync=False`, the padded device tensors (ids, scores, boxes_px, masks, counts) without any host read.
@@ -308,41 +291,40 @@ def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
     the padded `masks` is then a list of B per-image views `[max_det, h_b, w_b]` of one flat allocation (`ragged_layout`), each
     what the consumers of one image's padded rows take (`DeviceAPData.add`, `rle_encode`, `draw_img`)."""
     packed = _want_packed(cfg, packed)
-    device = dets.proto.device
     batch, md = dets.ids.shape
-    _, hp, wp, k = dets.proto.shape
     do_crop = not (cfg and getattr(cfg, 'no_crop', False))
     if cfg and getattr(cfg, 'save_lincomb', False):
         raise NotImplementedError('draw_lincomb (visualisation, reference output_utils.py:276-324) is out of scope')
-    ragged = hasattr(img_h, '__len__') or hasattr(img_w, '__len__')
-    if ragged:
+    if hasattr(img_h, '__len__') or hasattr(img_w, '__len__'):
         if not (hasattr(img_h, '__len__') and hasattr(img_w, '__len__')) or len(img_h) != batch or len(img_w) != batch:
             raise RuntimeError(f'after_nms_batch: {batch} heights and {batch} widths expected for a batch of {batch} images')
         sizes = [(int(h), int(w)) for h, w in zip(img_h, img_w)]
         ragged_layout(sizes, md, packed)                          # (size and batch-bound errors, before any launch)
         if not dets.proto.is_cuda:
             raise RuntimeError('yolact_minimal_amd.utils.output_utils.after_nms_batch needs CUDA (HIP) tensors; there is no CPU path.')
-        masks, box_px = _after_nms_ragged(dets, sizes, do_crop, packed)
     else:
-        with torch.cuda.device(device):
-            masks = _new_masks((batch, md), img_h, img_w, device, packed)
-            box_px = torch.empty(batch, md, 4, dtype=torch.int32, device=device)
-            _after_nms_launch(dets.proto.contiguous(), dets.coefs, dets.boxes, dets.counts, batch, md, hp, wp, k, img_h, img_w, do_crop,
-                              masks, box_px)
-        if packed:
-            masks = PackedMasks._wrap(masks, img_h, img_w)
+        sizes = (img_h, img_w)
+    masks, box_px = _after_nms_launch(dets.proto.contiguous(), dets.coefs, dets.boxes, dets.counts, sizes, do_crop, packed)
     if not sync:
         return dets.ids, dets.scores, box_px, masks, dets.counts
-    out = []
     vt = float(getattr(cfg, 'visual_thre', 0) or 0) if cfg else 0.0
-    for b, n in enumerate(dets.counts.tolist()):                  # the ONE host read of the whole batch
+    return unpad_detections(dets.ids, dets.scores, box_px, masks, dets.counts.tolist(), vt)     # the ONE host read of the whole batch
+
+
+def unpad_detections(ids, scores, box_px, masks, counts_list, visual_thre=0.0):
+    """The padded rows of `after_nms_batch(sync=False)` and the counts as a HOST list -> per-image 4-tuples like `after_nms`:
+    `(None,) * 4` for an image without detections, also when `visual_thre` (detect.py's score filter: per detection, so it
+    commutes with the post-processing) removes all of them.  `masks`: the padded tensor, a `PackedMasks`, or the list of per-image
+    views.  Plain indexing, so it runs on CPU tensors too."""
+    out = []
+    for b, n in enumerate(counts_list):
         if n == 0:
-            out.append((None, None, None, None))
+            out.append((None,) * 4)
             continue
-        r = (dets.ids[b, :n], dets.scores[b, :n], box_px[b, :n], masks[b][:n])
-        if vt > 0:                                               # detect.py's score filter (per detection, so it commutes)
-            keep = r[1] >= vt
-            r = tuple(t[keep] for t in r) if bool(keep.any()) else (None, None, None, None)
+        r = (ids[b, :n], scores[b, :n], box_px[b, :n], masks[b][:n])
+        if visual_thre > 0:
+            keep = r[1] >= visual_thre
+            r = tuple(t[keep] for t in r) if bool(keep.any()) else (None,) * 4
         out.append(r)
     return out
 

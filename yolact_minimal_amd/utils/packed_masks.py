@@ -89,7 +89,7 @@ class PackedMasks:
             raise IndexError('PackedMasks: index the leading (detection) axis only')
         if self.bits.dim() < 3:
             raise IndexError('PackedMasks: a single mask has no detection axis')
-        return PackedMasks(self.bits[idx], self.height, self.width)
+        return PackedMasks._wrap(self.bits[idx], self.height, self.width)    # (rows of valid words are valid words)
 
     def contiguous(self):
         return self if self.bits.is_contiguous() else PackedMasks(self.bits.contiguous(), self.height, self.width)
