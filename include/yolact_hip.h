@@ -497,6 +497,7 @@ int ym_swin_window_attention(const float* qkv, const float* qkv_bias, const floa
  * out [3][S][S] float32 RGB, (x - mean) / std.  mean_bgr / std_bgr are HOST pointers to 3 floats (config.py:66-67). */
 int ym_val_preprocess(const void* img_hwc_bgr, int is_uint8, int H, int W, int S, const float* mean_bgr,
                       const float* std_bgr, float* out_chw_rgb, ym_stream_t s);
+/* ym_val_preprocess_batch (declared with the ragged tables below): B frames of different sizes in one launch. */
 
 /* ---- detection post-processing (utils/output_utils.py) ---------------------------------------------- */
 
@@ -684,7 +685,7 @@ int ym_unpack_masks(const uint64_t* bits, int n, int H, int W, float* masks, ym_
 #define YM_RAGGED_ALIGN_BYTES 256
 typedef struct ym_ragged_image {
     int32_t img_h, img_w;
-    int64_t offset; /* elements from `masks` to this image's block */
+    int64_t offset; /* elements from `masks` to this image's block (for a table of frames: from the frame buffer to this frame) */
 } ym_ragged_image;
 size_t ym_after_nms_ragged_workspace_bytes(const ym_ragged_image* images, int B, int max_det, int Hp, int Wp);
 int ym_after_nms_ragged(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
@@ -693,6 +694,37 @@ int ym_after_nms_ragged(const float* proto, const float* coefs, float* boxes, co
 int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
                                int Wp, int K, const ym_ragged_image* images, int do_crop, uint64_t* mask_bits, int32_t* boxes_px,
                                void* workspace, size_t workspace_bytes, ym_stream_t s);
+
+/* ---- frames of different sizes: the two ends of a mixed-size request ----------------------------------------------------------
+ * The same table type describes a batch of FRAMES: entry b = {img_h_b, img_w_b, offset_b}, frame b is HWC BGR [img_h_b][img_w_b][3]
+ * at `frames + offset_b`, offset counted in elements of the frame buffer (bytes for uint8, floats for float32).  The rules are the
+ * mask blocks': 1 .. YM_RAGGED_MAX_IMAGES entries, positive sizes, every frame at a multiple of YM_RAGGED_ALIGN_BYTES bytes, no two
+ * frames overlapping (YM_EINVAL otherwise); the table is read during the call and travels by value in the kernel arguments.
+ *
+ * ym_val_preprocess_batch: ym_val_preprocess for B frames in ONE launch (grid = ceil(S * S / 256) x B), out [B][3][S][S].  It is the
+ * same kernel as ym_val_preprocess (that entry is its B = 1 instance), so frame b of a batch equals the single call bit for bit.
+ *
+ * ym_draw_detections_ragged[_packed]: ym_draw_detections_batch[_packed] with `H, W` replaced by two tables and no cutout_total.
+ * `frames[b]` is frame b's size and its first BYTE in both `img` and `out` (one layout for the two buffers; out == img is legal);
+ * `mask_blocks` is the table that was given to ym_after_nms_ragged[_packed] (offsets in floats / 64-bit words from `masks`), its
+ * sizes must equal `frames`' (YM_EINVAL); it may be NULL with YM_DRAW_HIDE_MASK.  B <= YM_RAGGED_MAX_IMAGES.  Output bytes per
+ * frame are those of the uniform entry called on that frame alone.  At most two frame launches: the images whose rows are whole
+ * 4-pixel groups at aligned addresses take the 16-byte path, the others the element-wise one; the grid is the largest tile count of
+ * a launch's images x B, workgroups of other images or past an image's own tiles exit before touching memory.  Nothing outside
+ * the frames is written.  Workspace: ym_draw_workspace_bytes(B, max_det), as for the uniform entries. */
+int ym_val_preprocess_batch(const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S, const float* mean_bgr,
+                            const float* std_bgr, float* out, ym_stream_t s);
+int ym_draw_detections_ragged(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores, const int32_t* boxes_px,
+                              const int32_t* counts, int B, int max_det, const ym_ragged_image* frames,
+                              const ym_ragged_image* mask_blocks, const uint8_t* palette, int palette_n, int num_classes,
+                              const char* names, int num_names, const uint16_t* font, int flags, float visual_thre,
+                              const char* fps_text, uint8_t* out, void* workspace, size_t workspace_bytes, ym_stream_t s);
+int ym_draw_detections_ragged_packed(const uint8_t* img, const uint64_t* mask_bits, const int64_t* ids, const float* scores,
+                                     const int32_t* boxes_px, const int32_t* counts, int B, int max_det,
+                                     const ym_ragged_image* frames, const ym_ragged_image* mask_blocks, const uint8_t* palette,
+                                     int palette_n, int num_classes, const char* names, int num_names, const uint16_t* font,
+                                     int flags, float visual_thre, const char* fps_text, uint8_t* out, void* workspace,
+                                     size_t workspace_bytes, ym_stream_t s);
 
 /* ym_mask_iou on bit rows: bits_a [n][words], bits_b [g][words], words = H * Wq < 2^18.  Exact integers through the same
  * finalize step, so bit-identical to ym_mask_iou on the dense masks (0/0 -> NaN). */

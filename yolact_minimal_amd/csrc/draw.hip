@@ -11,7 +11,13 @@
 //  k_cutout_object: per-detection matte (img where mask != 0 else 255), full frame; the caller slices the box window.
 //  k_draw_frame<VEC, true> / k_cutout_object_packed: the mask term read from bit-packed masks (one 8-byte word serves 64 pixels
 //                   of a detection), same bytes out.
+//  k_draw_frame<VEC, PACKED, Sizes>: where frame b and its mask block lie comes from a small object in the kernel arguments, like
+//                   k_masks_fused's (masks.hip): UniformSizes = one H x W, frame b right behind frame b - 1 (ym_draw_detections_batch);
+//                   RaggedSizes = ym_draw_detections_ragged's two per-image tables.  grid.x is then the largest tile count of the
+//                   batch, workgroups past an image's own count return at once, and VEC is decided per image: one launch for the
+//                   images that take <true>, one for the others (bit b of `set_bits` = image b belongs to this launch).
 // All arithmetic is integer; results are exact (tests compare with tolerance 0).
+#include <algorithm>
 #include "ym_common.h"
 
 namespace {
@@ -226,9 +232,36 @@ __device__ __forceinline__ void bits_batch(const int* recs, const unsigned long 
     }
 }
 
-template <bool VEC, bool PACKED>
+__host__ __device__ inline size_t mask_row(bool packed, int W) { return packed ? (size_t)((W + 63) >> 6) : (size_t)W; }
+__host__ __device__ inline int frame_tiles(int H, int W) { return (H * ((W + 3) >> 2) + FRAME_THREADS - 1) / FRAME_THREADS; }
+
+// first_byte(b, y, x): where pixel (y, x) of frame b starts in img / out / cut_total; masks(b): first element (float, or word when
+// packed) of its mask block.
+struct UniformSizes {
+    typedef int i32x2 __attribute__((ext_vector_type(2)));      // (one vector, not two ints: see masks.hip's UniformSizes)
+    i32x2 hw;                                                   // {H, W}
+    __host__ __device__ int h(int) const { return hw[0]; }
+    __host__ __device__ int w(int) const { return hw[1]; }
+    __device__ size_t first_byte(int b, int y, int x) const { return (((size_t)b * hw[0] + y) * hw[1] + x) * 3; }
+    __device__ size_t masks(int b, int max_det, bool packed) const { return (size_t)b * max_det * hw[0] * mask_row(packed, hw[1]); }
+    __device__ bool nothing_to_do(int, int) const { return false; }
+};
+
+struct RaggedSizes {
+    YmRaggedTable frames, blocks;
+    unsigned set_bits;
+    __host__ __device__ int h(int b) const { return frames.img[b].img_h; }
+    __host__ __device__ int w(int b) const { return frames.img[b].img_w; }
+    __device__ size_t first_byte(int b, int y, int x) const { return (size_t)frames.img[b].offset + ((size_t)y * w(b) + x) * 3; }
+    __device__ size_t masks(int b, int, bool) const { return (size_t)blocks.img[b].offset; }
+    __device__ bool nothing_to_do(int b, int tile) const { return !((set_bits >> b) & 1u) || tile >= frame_tiles(h(b), w(b)); }
+};
+
+// (`sz` BEFORE `max_det`: UniformSizes' two ints then lie where `H, W` always lay and come in with the first scalar load; behind
+// `max_det` the 8-byte aligned struct leaves a hole, and the frame size is fetched by a load of its own in front of the barrier)
+template <bool VEC, bool PACKED, class Sizes>
 __global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __restrict__ img, const void* __restrict__ masks_v,
-                                                              const int* __restrict__ ws, int max_det, int H, int W,
+                                                              const int* __restrict__ ws, const Sizes sz, int max_det,
                                                               const uint8_t* __restrict__ palette, int palette_n, int modulus,
                                                               const uint16_t* __restrict__ font, int flags, uint8_t* out,
                                                               uint8_t* cut_total) {
@@ -237,6 +270,8 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __r
     int* hdr = lds + PAL;           // [HDR]
     int* recs = hdr + HDR;          // [n][REC]
     const int b = blockIdx.y, tid = threadIdx.x;
+    if (sz.nothing_to_do(b, blockIdx.x)) return;            // (uniform over the workgroup: nobody is left at the barrier)
+    const int H = sz.h(b), W = sz.w(b);
     const int* wsb = ws + (size_t)b * (HDR + (size_t)max_det * REC);
     const int n = max(0, min(wsb[0], max_det));
     for (int j = tid; j < palette_n; j += FRAME_THREADS) pal[j] = (int)pack_bgr(palette + j * 3);
@@ -265,14 +300,14 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __r
     if (q >= H * Q) return;
     const int y = q / Q, x0 = (q - y * Q) * 4;
     const int npx = min(4, W - x0);
-    const size_t pix = ((size_t)b * H + y) * W + x0;
+    const size_t pix = sz.first_byte(b, y, x0);                         // first byte of this thread's pixels
     unsigned px[4];
-    load_px<VEC>(img + pix * 3, npx, px);
+    load_px<VEC>(img + pix, npx, px);
     if (n == 0) {                                            // no detection: the frame comes back unchanged (draw_img's early return)
-        store_px<VEC>(out + pix * 3, npx, px);
+        store_px<VEC>(out + pix, npx, px);
         if (cut_total) {
             const unsigned white[4] = {0xffffffu, 0xffffffu, 0xffffffu, 0xffffffu};
-            store_px<VEC>(cut_total + pix * 3, npx, white);
+            store_px<VEC>(cut_total + pix, npx, white);
         }
         return;
     }
@@ -283,13 +318,13 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __r
         if (PACKED) {
             const int wq = (W + 63) >> 6, sh = x0 & 63;
             const size_t HWq = (size_t)H * wq;
-            const unsigned long long* bp = static_cast<const unsigned long long*>(masks_v) + (size_t)b * max_det * HWq + (size_t)y * wq + (x0 >> 6);
+            const unsigned long long* bp = static_cast<const unsigned long long*>(masks_v) + sz.masks(b, max_det, true) + (size_t)y * wq + (x0 >> 6);
             for (; i + 16 <= n; i += 16) bits_batch<16>(recs + i * REC, bp, HWq, sh, s);
             for (; i + 4 <= n; i += 4) bits_batch<4>(recs + i * REC, bp, HWq, sh, s);
             for (; i < n; ++i) bits_batch<1>(recs + i * REC, bp, HWq, sh, s);
         }
         const size_t HW = (size_t)H * W;
-        const float* mp = static_cast<const float*>(masks_v) + (size_t)b * max_det * HW + (size_t)y * W + x0;
+        const float* mp = static_cast<const float*>(masks_v) + (PACKED ? 0 : sz.masks(b, max_det, false)) + (size_t)y * W + x0;
         if (VEC && !PACKED) {
             for (; i + 16 <= n; i += 16) mask_batch<16>(recs + i * REC, mp, HW, s);
             for (; i + 4 <= n; i += 4) mask_batch<4>(recs + i * REC, mp, HW, s);
@@ -315,7 +350,7 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __r
             cut[k] = sm != 0 ? px[k] : 0xffffffu;
             px[k] = blend((unsigned)pal[sm], px[k]);
         }
-        if (cut_total) store_px<VEC>(cut_total + pix * 3, npx, cut);
+        if (cut_total) store_px<VEC>(cut_total + pix, npx, cut);
     }
 
     if (!(flags & YM_DRAW_HIDE_BBOX)) {
@@ -355,7 +390,7 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_draw_frame(const uint8_t* __r
             }
         }
     }
-    store_px<VEC>(out + pix * 3, npx, px);
+    store_px<VEC>(out + pix, npx, px);
 }
 
 __global__ __launch_bounds__(256) void k_cutout_object(const uint8_t* __restrict__ img, const float* __restrict__ masks, int HW,
@@ -391,56 +426,138 @@ extern "C" size_t ym_draw_workspace_bytes(int B, int max_det) {
     return (size_t)B * (HDR + (size_t)max_det * REC) * sizeof(int);
 }
 
+// What every draw entry checks besides its frame sizes; *fps_len / f: the fps text packed for k_draw_prep.
+static int draw_check(const char* what, const uint8_t* img, const void* masks, bool packed, const int64_t* ids, const float* scores,
+                      const int32_t* boxes_px, int B, int max_B, int max_det, const uint8_t* palette, int palette_n, int num_classes,
+                      const char* names, int num_names, const uint16_t* font, int flags, float visual_thre, const char* fps_text,
+                      const uint8_t* out, const uint8_t* cutout_total, const void* workspace, size_t workspace_bytes,
+                      unsigned long long (&f)[4], int* fps_len) {
+    YM_REQUIRE(B >= 1 && B <= max_B && max_det >= 0 && max_det <= YM_DRAW_MAX_DET, "%s: 1 <= B <= %d and 0 <= max_det <= %d required (B=%d max_det=%d)",
+               what, max_B, YM_DRAW_MAX_DET, B, max_det);
+    YM_REQUIRE(img && out && palette && font && workspace, "%s: null img / out / palette / font / workspace", what);
+    YM_REQUIRE(max_det == 0 || (ids && boxes_px && names), "%s: null ids / boxes_px / names", what);
+    YM_REQUIRE(((uintptr_t)names & 3) == 0, "%s: the class-name table must be 4-byte aligned", what);
+    const bool hide_mask = flags & YM_DRAW_HIDE_MASK;
+    YM_REQUIRE(hide_mask || max_det == 0 || masks, "%s: masks are needed unless YM_DRAW_HIDE_MASK is set", what);
+    YM_REQUIRE(!cutout_total || !hide_mask, "%s: the cutout matte needs the masks (YM_DRAW_HIDE_MASK is set)", what);
+    YM_REQUIRE(scores || ((flags & YM_DRAW_HIDE_SCORE) && !(visual_thre > 0.f)) || max_det == 0,
+               "%s: scores are needed for the labels and for visual_thre", what);
+    YM_REQUIRE(num_classes >= 2 && palette_n >= 1 && palette_n <= PAL && num_classes - 1 <= palette_n && num_names >= 0,
+               "%s: num_classes=%d needs a palette of at least num_classes-1 (<= %d) colours, got %d", what, num_classes, PAL, palette_n);
+    const size_t need = ym_draw_workspace_bytes(B, max_det);
+    YM_REQUIRE(workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, "%s: workspace of %zu bytes (16-byte aligned) needed, got %zu",
+               what, need, workspace_bytes);
+    YM_REQUIRE(!packed || (uintptr_t)masks % 8 == 0, "%s: the mask words must be 8-byte aligned", what);
+    *fps_len = 0;
+    if (flags & YM_DRAW_REAL_TIME) {
+        YM_REQUIRE(fps_text, "%s: YM_DRAW_REAL_TIME needs the fps text", what);
+        for (; *fps_len < 32 && fps_text[*fps_len]; ++*fps_len) {
+            const unsigned char c = (unsigned char)fps_text[*fps_len];
+            f[*fps_len >> 3] |= (unsigned long long)((c < 0x20 || c > 0x7E) ? '?' : c) << ((*fps_len & 7) * 8);
+        }
+    }
+    return YM_OK;
+}
+
+// may a frame / mask block that starts at these addresses take k_draw_frame<true>?
+static bool draw_vec_ok(int W, const uint8_t* img, const uint8_t* out, const uint8_t* cutout_total, const void* masks, bool packed,
+                        bool hide_mask) {
+    return (W % 4 == 0) && ((uintptr_t)img % 4 == 0) && ((uintptr_t)out % 4 == 0) && (!cutout_total || (uintptr_t)cutout_total % 4 == 0) &&
+           (hide_mask || (uintptr_t)masks % 16 == 0 || (packed && (uintptr_t)masks % 8 == 0));
+}
+
+#define YM_DRAW_FRAME(V, P, S)                                                                                                      \
+    k_draw_frame<V, P, S><<<grid, FRAME_THREADS, lds, st>>>(img, masks, (const int*)workspace, sz, max_det, palette, palette_n,    \
+                                                            num_classes - 1, font, flags, out, cutout_total)
+
 // `masks`: float [B][max_det][H][W], or (packed) the bit rows uint64 [B][max_det][H][ceil(W / 64)]
 static int draw_detections(const uint8_t* img, const void* masks, bool packed, const int64_t* ids, const float* scores,
                            const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
                            const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
                            const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
                            uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    YM_REQUIRE(B >= 1 && B <= 65535 && max_det >= 0 && max_det <= YM_DRAW_MAX_DET, "ym_draw_detections_batch: 1 <= B <= 65535 and 0 <= max_det <= %d required (B=%d max_det=%d)",
-               YM_DRAW_MAX_DET, B, max_det);
-    YM_REQUIRE(frame_dims_ok(H, W), "ym_draw_detections_batch: frame %dx%d out of range (1..16384)", H, W);
-    YM_REQUIRE(img && out && palette && font && workspace, "ym_draw_detections_batch: null img / out / palette / font / workspace");
-    YM_REQUIRE(max_det == 0 || (ids && boxes_px && names), "ym_draw_detections_batch: null ids / boxes_px / names");
-    YM_REQUIRE(((uintptr_t)names & 3) == 0, "ym_draw_detections_batch: the class-name table must be 4-byte aligned");
-    const bool hide_mask = flags & YM_DRAW_HIDE_MASK;
-    YM_REQUIRE(hide_mask || max_det == 0 || masks, "ym_draw_detections_batch: masks are needed unless YM_DRAW_HIDE_MASK is set");
-    YM_REQUIRE(!cutout_total || !hide_mask, "ym_draw_detections_batch: the cutout matte needs the masks (YM_DRAW_HIDE_MASK is set)");
-    YM_REQUIRE(scores || ((flags & YM_DRAW_HIDE_SCORE) && !(visual_thre > 0.f)) || max_det == 0,
-               "ym_draw_detections_batch: scores are needed for the labels and for visual_thre");
-    YM_REQUIRE(num_classes >= 2 && palette_n >= 1 && palette_n <= PAL && num_classes - 1 <= palette_n && num_names >= 0,
-               "ym_draw_detections_batch: num_classes=%d needs a palette of at least num_classes-1 (<= %d) colours, got %d", num_classes,
-               PAL, palette_n);
-    const size_t need = ym_draw_workspace_bytes(B, max_det);
-    YM_REQUIRE(workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, "ym_draw_detections_batch: workspace of %zu bytes (16-byte aligned) needed, got %zu",
-               need, workspace_bytes);
+    const char* what = packed ? "ym_draw_detections_batch_packed" : "ym_draw_detections_batch";
     unsigned long long f[4] = {0, 0, 0, 0};
     int fps_len = 0;
-    if (flags & YM_DRAW_REAL_TIME) {
-        YM_REQUIRE(fps_text, "ym_draw_detections_batch: YM_DRAW_REAL_TIME needs the fps text");
-        for (; fps_len < 32 && fps_text[fps_len]; ++fps_len) {
-            const unsigned char c = (unsigned char)fps_text[fps_len];
-            f[fps_len >> 3] |= (unsigned long long)((c < 0x20 || c > 0x7E) ? '?' : c) << ((fps_len & 7) * 8);
-        }
+    YM_REQUIRE(frame_dims_ok(H, W), "%s: frame %dx%d out of range (1..16384)", what, H, W);
+    int rc = draw_check(what, img, masks, packed, ids, scores, boxes_px, B, 65535, max_det, palette, palette_n, num_classes, names, num_names,
+                        font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, f, &fps_len);
+    if (rc != YM_OK) return rc;
+    hipStream_t st = (hipStream_t)s;
+    k_draw_prep<<<B, 64, 0, st>>>(ids, scores, boxes_px, counts, max_det, palette, palette_n, names, num_names, flags, visual_thre, f[0],
+                                  f[1], f[2], f[3], fps_len, (int*)workspace);
+    rc = ym_check_launch("k_draw_prep");
+    if (rc != YM_OK) return rc;
+    const size_t lds = (size_t)(PAL + HDR + max_det * REC) * sizeof(int);
+    const dim3 grid(frame_tiles(H, W), B);
+    const bool vec = draw_vec_ok(W, img, out, cutout_total, masks, packed, flags & YM_DRAW_HIDE_MASK);
+    const UniformSizes sz = {{H, W}};
+    if (packed) { if (vec) YM_DRAW_FRAME(true, true, UniformSizes); else YM_DRAW_FRAME(false, true, UniformSizes); }
+    else { if (vec) YM_DRAW_FRAME(true, false, UniformSizes); else YM_DRAW_FRAME(false, false, UniformSizes); }
+    return ym_check_launch("k_draw_frame");
+}
+
+// `frames`: frame b's size and its first byte in img AND out; `mask_blocks`: ym_after_nms_ragged[_packed]'s table (NULL with
+// YM_DRAW_HIDE_MASK: the masks are not read)
+static int draw_detections_ragged(const uint8_t* img, const void* masks, bool packed, const int64_t* ids, const float* scores,
+                                  const int32_t* boxes_px, const int32_t* counts, int B, int max_det, const ym_ragged_image* frames,
+                                  const ym_ragged_image* mask_blocks, const uint8_t* palette, int palette_n, int num_classes,
+                                  const char* names, int num_names, const uint16_t* font, int flags, float visual_thre,
+                                  const char* fps_text, uint8_t* out, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    const char* what = packed ? "ym_draw_detections_ragged_packed" : "ym_draw_detections_ragged";
+    unsigned long long f[4] = {0, 0, 0, 0};
+    int fps_len = 0;
+    uint8_t* const cutout_total = nullptr;
+    int rc = ym_check_ragged_table(what, frames, B, 1, [](const ym_ragged_image& im) { return (int64_t)im.img_h * im.img_w * 3; });
+    if (rc != YM_OK) return rc;
+    for (int b = 0; b < B; ++b)
+        YM_REQUIRE(frame_dims_ok(frames[b].img_h, frames[b].img_w), "%s: frame %d is %dx%d, out of range (1..16384)", what, b,
+                   frames[b].img_h, frames[b].img_w);
+    rc = draw_check(what, img, masks, packed, ids, scores, boxes_px, B, YM_RAGGED_MAX_IMAGES, max_det, palette, palette_n, num_classes, names,
+                    num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, f, &fps_len);
+    if (rc != YM_OK) return rc;
+    const bool hide_mask = flags & YM_DRAW_HIDE_MASK, read_masks = !hide_mask && max_det > 0;
+    YM_REQUIRE(mask_blocks || !read_masks, "%s: the mask block table is needed unless YM_DRAW_HIDE_MASK is set", what);
+    RaggedSizes sz = {};
+    std::copy(frames, frames + B, sz.frames.img);
+    if (mask_blocks && read_masks) {
+        rc = ym_check_ragged_table(what, mask_blocks, B, packed ? 8 : 4, [=](const ym_ragged_image& im) {
+            return (int64_t)max_det * im.img_h * (int64_t)mask_row(packed, im.img_w);
+        });
+        if (rc != YM_OK) return rc;
+        for (int b = 0; b < B; ++b)
+            YM_REQUIRE(mask_blocks[b].img_h == frames[b].img_h && mask_blocks[b].img_w == frames[b].img_w,
+                       "%s: image %d: masks of %d x %d for a frame of %d x %d", what, b, mask_blocks[b].img_h, mask_blocks[b].img_w,
+                       frames[b].img_h, frames[b].img_w);
+        std::copy(mask_blocks, mask_blocks + B, sz.blocks.img);
     }
     hipStream_t st = (hipStream_t)s;
     k_draw_prep<<<B, 64, 0, st>>>(ids, scores, boxes_px, counts, max_det, palette, palette_n, names, num_names, flags, visual_thre, f[0],
                                   f[1], f[2], f[3], fps_len, (int*)workspace);
-    int rc = ym_check_launch("k_draw_prep");
+    rc = ym_check_launch("k_draw_prep");
     if (rc != YM_OK) return rc;
     const size_t lds = (size_t)(PAL + HDR + max_det * REC) * sizeof(int);
-    const dim3 grid(ym_cdiv(H * ((W + 3) / 4), FRAME_THREADS), B);
-    const bool vec = (W % 4 == 0) && ((uintptr_t)img % 4 == 0) && ((uintptr_t)out % 4 == 0) && (!cutout_total || (uintptr_t)cutout_total % 4 == 0) &&
-                     (hide_mask || (uintptr_t)masks % 16 == 0 || (packed && (uintptr_t)masks % 8 == 0));
-    YM_REQUIRE(!packed || (uintptr_t)masks % 8 == 0, "ym_draw_detections_batch_packed: the mask words must be 8-byte aligned");
-#define YM_DRAW_FRAME(V, P)                                                                                                         \
-    k_draw_frame<V, P><<<grid, FRAME_THREADS, lds, st>>>(img, masks, (const int*)workspace, max_det, H, W, palette, palette_n,     \
-                                                         num_classes - 1, font, flags, out, cutout_total)
-    if (packed) { if (vec) YM_DRAW_FRAME(true, true); else YM_DRAW_FRAME(false, true); }
-    else { if (vec) YM_DRAW_FRAME(true, false); else YM_DRAW_FRAME(false, false); }
-#undef YM_DRAW_FRAME
+    // the images that take <true> in one launch, the others in a second; an empty set is not launched
+    unsigned vec_bits = 0u, all_bits = 0u;
+    const size_t esz = packed ? 8 : 4;
+    for (int b = 0; b < B; ++b) {
+        all_bits |= 1u << b;
+        const void* mb = read_masks ? (const void*)((const char*)masks + (size_t)sz.blocks.img[b].offset * esz) : nullptr;
+        if (draw_vec_ok(frames[b].img_w, img + frames[b].offset, out + frames[b].offset, nullptr, mb, packed, !read_masks)) vec_bits |= 1u << b;
+    }
+    for (int pass = 0; pass < 2; ++pass) {
+        sz.set_bits = pass == 0 ? vec_bits : (all_bits & ~vec_bits);
+        if (!sz.set_bits) continue;
+        int tiles = 0;
+        for (int b = 0; b < B; ++b)
+            if ((sz.set_bits >> b) & 1u) tiles = std::max(tiles, frame_tiles(frames[b].img_h, frames[b].img_w));
+        const dim3 grid(tiles, B);
+        if (packed) { if (pass == 0) YM_DRAW_FRAME(true, true, RaggedSizes); else YM_DRAW_FRAME(false, true, RaggedSizes); }
+        else { if (pass == 0) YM_DRAW_FRAME(true, false, RaggedSizes); else YM_DRAW_FRAME(false, false, RaggedSizes); }
+    }
     return ym_check_launch("k_draw_frame");
 }
+#undef YM_DRAW_FRAME
 
 extern "C" int ym_draw_detections_batch(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores,
                                         const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
@@ -458,6 +575,27 @@ extern "C" int ym_draw_detections_batch_packed(const uint8_t* img, const uint64_
                                                uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
     return draw_detections(img, mask_bits, true, ids, scores, boxes_px, counts, B, max_det, H, W, palette, palette_n, num_classes, names,
                            num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, s);
+}
+
+extern "C" int ym_draw_detections_ragged(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores,
+                                         const int32_t* boxes_px, const int32_t* counts, int B, int max_det,
+                                         const ym_ragged_image* frames, const ym_ragged_image* mask_blocks, const uint8_t* palette,
+                                         int palette_n, int num_classes, const char* names, int num_names, const uint16_t* font,
+                                         int flags, float visual_thre, const char* fps_text, uint8_t* out, void* workspace,
+                                         size_t workspace_bytes, ym_stream_t s) {
+    return draw_detections_ragged(img, masks, false, ids, scores, boxes_px, counts, B, max_det, frames, mask_blocks, palette, palette_n,
+                                  num_classes, names, num_names, font, flags, visual_thre, fps_text, out, workspace, workspace_bytes, s);
+}
+
+extern "C" int ym_draw_detections_ragged_packed(const uint8_t* img, const uint64_t* mask_bits, const int64_t* ids, const float* scores,
+                                                const int32_t* boxes_px, const int32_t* counts, int B, int max_det,
+                                                const ym_ragged_image* frames, const ym_ragged_image* mask_blocks,
+                                                const uint8_t* palette, int palette_n, int num_classes, const char* names,
+                                                int num_names, const uint16_t* font, int flags, float visual_thre,
+                                                const char* fps_text, uint8_t* out, void* workspace, size_t workspace_bytes,
+                                                ym_stream_t s) {
+    return draw_detections_ragged(img, mask_bits, true, ids, scores, boxes_px, counts, B, max_det, frames, mask_blocks, palette, palette_n,
+                                  num_classes, names, num_names, font, flags, visual_thre, fps_text, out, workspace, workspace_bytes, s);
 }
 
 extern "C" int ym_draw_cutout_objects(const uint8_t* img, const float* masks, int n, int H, int W, uint8_t* out, ym_stream_t s) {

@@ -1,6 +1,7 @@
 // HBM-bound NHWC helpers: layout conversion, weight packing, BN folding, max-pool, bilinear x2, row softmax.
 // All of these move each byte once; they are written for coalesced 16-byte accesses along C.
 #include <stdarg.h>
+#include <algorithm>
 #include "ym_common.h"
 
 // ---- error plumbing (shared by every translation unit) ---------------------------------------------
@@ -245,45 +246,74 @@ extern "C" int ym_softmax_rows(const float* in, float* out, int64_t rows, int C,
 // (cv2.resize INTER_LINEAR on float32 == half-pixel centres, source index clamped at 0, i1 = min(i0+1, n-1)) ->
 // (x - mean) / std -> BGR->RGB -> CHW.  The padded square is never materialised: a source pixel outside the image
 // simply evaluates to norm_mean.  One thread per output pixel, 3 channels.
+// ym_val_preprocess and ym_val_preprocess_batch are ONE kernel (grid.y = frame, the {img_h, img_w, offset} table by value in the
+// kernel arguments, indexed by the uniform blockIdx.y: no device copy, no synchronisation); the single-image entry is its B = 1
+// instance, so a frame of a batch and the same frame alone run the same instructions and agree bit for bit.
 namespace {
+// output pixel i (= oy * S + ox) of one H x W frame, all three channels
 template <typename T>
-__global__ __launch_bounds__(256) void k_val_preprocess(const T* __restrict__ img, int H, int W, int S, f32x4 mean, f32x4 stdv,
-                                                         float* __restrict__ out) {
+__device__ __forceinline__ void val_preprocess_pixel(const T* __restrict__ img, int H, int W, int S, int i, f32x4 mean, f32x4 stdv,
+                                                     float* __restrict__ out) {
     const int P = H > W ? H : W;
     const float scale = (float)P / (float)S;
     const int total = S * S;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int oy = i / S, ox = i - oy * S;
-        float sy = scale * ((float)oy + 0.5f) - 0.5f, sx = scale * ((float)ox + 0.5f) - 0.5f;
-        if (sy < 0.f) sy = 0.f;
-        if (sx < 0.f) sx = 0.f;
-        int y0 = (int)sy, x0 = (int)sx;
-        if (y0 > P - 1) y0 = P - 1;
-        if (x0 > P - 1) x0 = P - 1;
-        const int y1 = y0 + (y0 < P - 1 ? 1 : 0), x1 = x0 + (x0 < P - 1 ? 1 : 0);
-        const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-        auto px = [&](int y, int x, int c) -> float {
-            return (y < H && x < W) ? (float)img[((size_t)y * W + x) * 3 + c] : mean[c];
-        };
+    const int oy = i / S, ox = i - oy * S;
+    float sy = scale * ((float)oy + 0.5f) - 0.5f, sx = scale * ((float)ox + 0.5f) - 0.5f;
+    if (sy < 0.f) sy = 0.f;
+    if (sx < 0.f) sx = 0.f;
+    int y0 = (int)sy, x0 = (int)sx;
+    if (y0 > P - 1) y0 = P - 1;
+    if (x0 > P - 1) x0 = P - 1;
+    const int y1 = y0 + (y0 < P - 1 ? 1 : 0), x1 = x0 + (x0 < P - 1 ? 1 : 0);
+    const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+    auto px = [&](int y, int x, int c) -> float {
+        return (y < H && x < W) ? (float)img[((size_t)y * W + x) * 3 + c] : mean[c];
+    };
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = hy * (hx * px(y0, x0, c) + lx * px(y0, x1, c)) + ly * (hx * px(y1, x0, c) + lx * px(y1, x1, c));
-            out[(size_t)(2 - c) * total + i] = (v - mean[c]) / stdv[c];          // BGR -> RGB plane order
-        }
+    for (int c = 0; c < 3; ++c) {
+        const float v = hy * (hx * px(y0, x0, c) + lx * px(y0, x1, c)) + ly * (hx * px(y1, x0, c) + lx * px(y1, x1, c));
+        out[(size_t)(2 - c) * total + i] = (v - mean[c]) / stdv[c];          // BGR -> RGB plane order
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_val_preprocess(const T* __restrict__ frames, const YmRaggedTable tab, int S, f32x4 mean,
+                                                         f32x4 stdv, float* __restrict__ out) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * S) return;
+    val_preprocess_pixel<T>(frames + tab.img[b].offset, tab.img[b].img_h, tab.img[b].img_w, S, i, mean, stdv,
+                            out + (size_t)b * 3 * S * S);
+}
+
+int val_preprocess_launch(const void* frames, int is_uint8, const YmRaggedTable& tab, int B, int S, const float* mean_bgr,
+                          const float* std_bgr, float* out, ym_stream_t s) {
+    const f32x4 mean = {mean_bgr[0], mean_bgr[1], mean_bgr[2], 0.f}, stdv = {std_bgr[0], std_bgr[1], std_bgr[2], 1.f};
+    const dim3 grid((S * S + 255) / 256, B);
+    if (is_uint8)
+        hipLaunchKernelGGL(k_val_preprocess<unsigned char>, grid, dim3(256), 0, (hipStream_t)s, (const unsigned char*)frames, tab, S,
+                           mean, stdv, out);
+    else
+        hipLaunchKernelGGL(k_val_preprocess<float>, grid, dim3(256), 0, (hipStream_t)s, (const float*)frames, tab, S, mean, stdv, out);
+    return ym_check_launch("val_preprocess");
 }
 }  // namespace
 
 extern "C" int ym_val_preprocess(const void* img_hwc_bgr, int is_uint8, int H, int W, int S, const float* mean_bgr,
                                  const float* std_bgr, float* out_chw_rgb, ym_stream_t s) {
     YM_REQUIRE(img_hwc_bgr && out_chw_rgb && mean_bgr && std_bgr && H > 0 && W > 0 && S > 0, "val_preprocess: bad args");
-    const f32x4 mean = {mean_bgr[0], mean_bgr[1], mean_bgr[2], 0.f}, stdv = {std_bgr[0], std_bgr[1], std_bgr[2], 1.f};
-    const int grid = (S * S + 255) / 256;
-    if (is_uint8)
-        hipLaunchKernelGGL(k_val_preprocess<unsigned char>, dim3(grid), dim3(256), 0, (hipStream_t)s,
-                           (const unsigned char*)img_hwc_bgr, H, W, S, mean, stdv, out_chw_rgb);
-    else
-        hipLaunchKernelGGL(k_val_preprocess<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)img_hwc_bgr, H, W, S,
-                           mean, stdv, out_chw_rgb);
-    return ym_check_launch("val_preprocess");
+    YmRaggedTable tab = {};
+    tab.img[0] = ym_ragged_image{H, W, 0};
+    return val_preprocess_launch(img_hwc_bgr, is_uint8, tab, 1, S, mean_bgr, std_bgr, out_chw_rgb, s);
+}
+
+extern "C" int ym_val_preprocess_batch(const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S,
+                                       const float* mean_bgr, const float* std_bgr, float* out, ym_stream_t s) {
+    YM_REQUIRE(frames && out && mean_bgr && std_bgr, "val_preprocess_batch: null pointer");
+    YM_REQUIRE(S > 0 && S <= 32768, "val_preprocess_batch: output size %d out of range (1..32768)", S);
+    const int rc = ym_check_ragged_table("val_preprocess_batch", images, B, is_uint8 ? 1 : 4,
+                                         [](const ym_ragged_image& im) { return (int64_t)im.img_h * im.img_w * 3; });
+    if (rc != YM_OK) return rc;
+    YmRaggedTable tab = {};
+    std::copy(images, images + B, tab.img);
+    return val_preprocess_launch(frames, is_uint8, tab, B, S, mean_bgr, std_bgr, out, s);
 }

@@ -30,6 +30,29 @@ static inline int ym_check_launch(const char* what) {
 
 static inline int ym_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// A host table of per-image {img_h, img_w, offset} entries (ym_ragged_image) as it travels to a kernel: BY VALUE in the kernel
+// arguments, indexed by a uniform block index (masks.hip "Where a launch set's output sizes come from").
+struct YmRaggedTable { ym_ragged_image img[YM_RAGGED_MAX_IMAGES]; };
+
+// The checks every such table gets: 1..YM_RAGGED_MAX_IMAGES entries, positive sizes, every block at a multiple of
+// YM_RAGGED_ALIGN_BYTES bytes (`esz` = bytes per element of `offset`), no two blocks overlapping; `extent(entry)` = elements per block.
+template <class Extent>
+static inline int ym_check_ragged_table(const char* what, const ym_ragged_image* images, int B, int64_t esz, Extent extent) {
+    YM_REQUIRE(images, "%s: null image table", what);
+    YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
+    for (int b = 0; b < B; ++b) {
+        const ym_ragged_image& im = images[b];
+        YM_REQUIRE(im.img_h > 0 && im.img_w > 0, "%s: image %d is %d x %d", what, b, im.img_h, im.img_w);
+        YM_REQUIRE(im.offset >= 0 && (im.offset * esz) % YM_RAGGED_ALIGN_BYTES == 0, "%s: image %d: block offset %lld is not a multiple of %d bytes",
+                   what, b, (long long)im.offset, YM_RAGGED_ALIGN_BYTES);
+    }
+    for (int a = 0; a < B; ++a)          // (B <= 32: a few hundred compares)
+        for (int b = a + 1; b < B; ++b)
+            YM_REQUIRE(images[a].offset + extent(images[a]) <= images[b].offset || images[b].offset + extent(images[b]) <= images[a].offset,
+                       "%s: the blocks of images %d and %d overlap", what, a, b);
+    return YM_OK;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to ONE DEVICE's copy of a kernel: a process that drives a second GPU (nms_batch
 // and the request pipeline accept tensors on a non-current device) must raise it there as well.  One slot per (call site, device),
 // raised when a launch asks for more than was granted; a refusal is reported instead of surfacing as an opaque launch failure.

@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     'ym_eval_match_log', 'ym_eval_ap_workspace_bytes', 'ym_eval_ap',
     'ym_coco_iou_box', 'ym_coco_iou_mask_packed', 'ym_coco_match_log', 'ym_coco_accumulate_workspace_bytes', 'ym_coco_accumulate',
     'ym_after_nms_ragged_workspace_bytes', 'ym_after_nms_ragged', 'ym_after_nms_ragged_packed',
+    'ym_val_preprocess_batch', 'ym_draw_detections_ragged', 'ym_draw_detections_ragged_packed',
 )
 
 
@@ -114,7 +115,8 @@ class NmsCfg(ctypes.Structure):
 
 
 class RaggedImage(ctypes.Structure):
-    """ym_ragged_image: one image of `ym_after_nms_ragged`'s host table (output size, first element of its mask block)."""
+    """ym_ragged_image: one image of `ym_after_nms_ragged`'s host table (output size, first element of its mask block), or one frame
+    of `ym_val_preprocess_batch` / `ym_draw_detections_ragged` (frame size, first element of the frame in the frame buffer)."""
     _fields_ = [('img_h', ctypes.c_int32), ('img_w', ctypes.c_int32), ('offset', ctypes.c_int64)]
 
 
@@ -252,6 +254,11 @@ def lib():
         L.ym_after_nms_ragged_workspace_bytes.restype = sz
         L.ym_after_nms_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(RaggedImage), i32, vp, vp, vp, sz, vp]
         L.ym_after_nms_ragged_packed.argtypes = L.ym_after_nms_ragged.argtypes
+        L.ym_val_preprocess_batch.argtypes = [vp, i32, ctypes.POINTER(RaggedImage), i32, i32, ctypes.POINTER(ctypes.c_float),
+                                              ctypes.POINTER(ctypes.c_float), vp, vp]
+        L.ym_draw_detections_ragged.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(RaggedImage), ctypes.POINTER(RaggedImage),
+                                                vp, i32, i32, vp, i32, vp, i32, f32, ctypes.c_char_p, vp, vp, sz, vp]
+        L.ym_draw_detections_ragged_packed.argtypes = L.ym_draw_detections_ragged.argtypes
         L.ym_pack_masks.argtypes = [vp, i32, i32, i32, i32, vp, vp]
         L.ym_unpack_masks.argtypes = [vp, i32, i32, i32, vp, vp]
         L.ym_mask_iou_packed_workspace_bytes.argtypes = [i32, i32, i64]

@@ -11,6 +11,8 @@ the count is copied to pinned host memory behind the request and read when the s
 the request it has just enqueued.  `cfg.traditional_nms` is served the same way (`nms_batch` picks the batched greedy entry).
 With batch > 1 a request may give every image its own output size (`submit(out_hw=[(h, w), ...])`: `after_nms_batch` with per-image
 sizes, one launch set, the size table in the kernel arguments, so nothing is copied or synchronised per request).
+`submit_frames(FrameBatch)` is the whole request for frames of different sizes: uint8 frames in (`val_aug_batch` on the slot's
+stream), and with `draw=True` drawn uint8 frames of those sizes out (the ragged `draw_batch`), no host read in between.
 
 Measured mid-round 3 (res101_coco 544 px, MI355X, forward + nms + after_nms(480x640)): depth 1: 325 img/s, 2: 468, 3: 545, 4: 594, 5: 495,
 8: 479; with round 4's kernels 3: 580, 4: 603-617, 5: 499, 6: 527 -- the part schedules four compute pipes; GPU_MAX_HW_QUEUES must be >= depth + 1 (ROCm multiplexes HIP streams onto 4
@@ -23,6 +25,9 @@ import warnings
 import torch
 
 from .engine import InferEngine
+from .utils.augmentations import val_aug_batch
+from .utils.draw import draw_batch
+from .utils.frames import FrameBatch
 from .utils.output_utils import nms_batch, after_nms_batch, unpad_detections
 
 _streams = {}
@@ -82,6 +87,7 @@ class RequestPipeline:
         self.t1 = [torch.cuda.Event(enable_timing=True) for _ in range(depth)] if timed else None
         self.latencies_ms = []
         self.pending = [None] * depth
+        self.frame_inputs = [None] * depth              # submit_frames: a slot's input before its engine's graph exists
         self.anchors = torch.tensor(net.anchors, dtype=torch.float32).reshape(-1, 4).to(device) \
             if not torch.is_tensor(net.anchors) else net.anchors.to(device)
         self.vt = float(getattr(cfg, 'visual_thre', 0) or 0)
@@ -136,6 +142,8 @@ class RequestPipeline:
             pend.event.synchronize()
             if self.timed:
                 self.latencies_ms.append(self.t0[slot].elapsed_time(self.t1[slot]))
+            if isinstance(pend.value, FrameBatch):        # (drawn on the slot's stream, read on the caller's: as for the detections below)
+                pend.value.record_stream(torch.cuda.current_stream(self.device))
             return pend.value
         ids, scores, box_px, masks, counts, ev = pend
         ev.synchronize()                                  # THIS request only
@@ -176,6 +184,11 @@ class RequestPipeline:
             out_h, out_w = [int(p[0]) for p in hw], [int(p[1]) for p in hw]
         else:
             out_h, out_w = hw
+        return self._enqueue(img, head_outputs, out_h, out_w, consumer)
+
+    def _enqueue(self, img, head_outputs, out_h, out_w, consumer, frames=None):
+        """The request itself, behind `submit` and `submit_frames` (arguments checked there).  `frames`: the slot's input is
+        `val_aug_batch(frames)`, made on the slot's stream."""
         slot = self.submitted % self.depth
         self.submitted += 1
         done = self.finish(slot)
@@ -187,6 +200,12 @@ class RequestPipeline:
             eng = self.engines[slot]
             if self.timed:
                 self.t0[slot].record()
+            if frames is not None:
+                # straight into the buffer the engine's graph reads (its `copy_` of a tensor onto itself is then a no-op); before
+                # the graph exists, into a buffer of the slot's own
+                buf = eng.static_img if getattr(eng, 'graph', None) is not None else self._frame_input(slot)
+                img = val_aug_batch(frames, eng.H, out=buf)
+                frames.record_stream(self.streams[slot])       # the caller may drop `frames` while the slot still reads them
             eng.run(img)
             if self.with_post:
                 cls, box, coef, proto = head_outputs if head_outputs is not None else eng.outputs()
@@ -206,6 +225,50 @@ class RequestPipeline:
                 ev.record()
                 self.pending[slot] = ev
         return done
+
+    def _frame_input(self, slot):
+        if self.frame_inputs[slot] is None:
+            eng = self.engines[slot]
+            self.frame_inputs[slot] = torch.empty(self.batch, 3, eng.H, eng.W, dtype=torch.float32, device=self.device)
+        return self.frame_inputs[slot]
+
+    def submit_frames(self, frames, head_outputs=None, draw=False, consumer=None):
+        """The whole request for `batch` frames of their own sizes, from the uint8 frames on: `frames` is a `FrameBatch`
+        (utils/frames.py; `len(frames) == batch`, also for batch 1).  On the slot's stream: `val_aug_batch` into the slot's input
+        buffer -> forward -> `nms_batch` -> `after_nms_batch` at the frames' own sizes (the ragged entries).  The result, handed
+        back like `submit`'s when the slot comes up again:
+          `draw=True`: the drawn frames, a new `FrameBatch` (the ragged `draw_batch`).  No count is read on the host, and because
+              `draw_batch` applies `cfg.visual_thre` on the device this is allowed with `visual_thre > 0`;
+          `consumer`: its return value, exactly as for `submit` (per-image mask views; refused with `visual_thre > 0`);
+          neither: what `submit(val_aug_batch(frames), out_hw=frames.sizes)` returns.
+        Without post-processing (`with_post=False`) only the input path differs from `submit`.  `head_outputs` as for `submit`.
+        The caller may drop `frames` right away (the allocator is told that the slot's stream reads them) but must not overwrite
+        them before the request has finished."""
+        if not isinstance(frames, FrameBatch):
+            raise RuntimeError('RequestPipeline.submit_frames: frames is a FrameBatch (yolact_minimal_amd.utils.frames)')
+        if len(frames) != self.batch:
+            raise RuntimeError(f'RequestPipeline.submit_frames: {len(frames)} frames for a pipeline of batch {self.batch}')
+        frames.need_cuda('pipeline.RequestPipeline.submit_frames')
+        if (draw or consumer is not None) and not self.with_post:
+            raise RuntimeError('RequestPipeline.submit_frames: drawing / a consumer takes the post-processed detections (with_post=True)')
+        if draw and consumer is not None:
+            raise RuntimeError('RequestPipeline.submit_frames: draw=True or a consumer, not both')
+        if draw and frames.dtype != torch.uint8:
+            raise RuntimeError('RequestPipeline.submit_frames: draw=True needs uint8 frames')
+        if consumer is not None and self.vt > 0:
+            raise RuntimeError(f'RequestPipeline.submit_frames: cfg.visual_thre = {self.vt} is applied where the count is read on the '
+                               'host; a consumer would be handed the unfiltered rows')
+        if self.device.index is not None and frames.device != self.device:
+            raise RuntimeError(f'RequestPipeline.submit_frames: frames on {frames.device}, pipeline on {self.device}')
+        eng = self.engines[0]
+        if eng.H != eng.W:
+            raise RuntimeError(f'RequestPipeline.submit_frames: val_aug makes square inputs, the pipeline was built for {eng.H} x {eng.W}')
+        if draw:
+            cfg = self.cfg
+
+            def consumer(*r):
+                return draw_batch(r, frames, cfg)
+        return self._enqueue(None, head_outputs, [h for h, _ in frames.sizes], [w for _, w in frames.sizes], consumer, frames=frames)
 
     def drain(self):
         """Finish everything in flight, oldest first."""

@@ -6,6 +6,8 @@ but `img` is a CUDA tensor (uint8 or float32) and the result is a CUDA float32 t
 padded square is never materialised.  cv2 is not present in the build image, so this row is pinned against a torch
 restatement (pad + `F.interpolate(align_corners=False)`, the equivalence the reference itself notes at
 `utils/output_utils.py:225`), not against cv2 — "parity unpinned by the reference".
+`val_aug_batch(frames, val_size)` is the same for a batch of frames of different sizes (a `FrameBatch`, utils/frames.py) in one launch
+of the same kernel: `[B, 3, S, S]`, row b bit for bit `val_aug(frame_b, val_size)`.
 """
 import ctypes
 
@@ -30,6 +32,32 @@ def val_aug(img, val_size):
         hip.check(hip.lib().ym_val_preprocess(ctypes.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), h, w, val_size, _MEAN,
                                               _STD, hip.ptr(out), hip.stream_ptr()), 'ym_val_preprocess')
     return out
+
+
+def val_aug_batch(frames, val_size, out=None):
+    """`val_aug` for B frames of different sizes in ONE launch (`ym_val_preprocess_batch`) -> float32 `[B, 3, S, S]`.
+    `frames`: a `FrameBatch` (utils/frames.py), or a list of device HWC BGR tensors (all uint8 or all float32), which is packed
+    through `FrameBatch.from_tensors` first.  `out`: a contiguous float32 device tensor whose first B rows `[3, S, S]` are written
+    (a pipeline slot's own input buffer); the result is then `out[:B]`.  Row b equals `val_aug(frame_b, val_size)` bit for bit: the
+    two entries are one kernel.  No host synchronisation."""
+    from .frames import FrameBatch
+    val_size = int(val_size)
+    if not isinstance(frames, FrameBatch):
+        frames = FrameBatch.from_tensors(frames)
+    frames.need_cuda('utils.augmentations.val_aug_batch')
+    batch = len(frames)
+    if val_size < 1:
+        raise RuntimeError(f'val_aug_batch: val_size = {val_size}')
+    if out is None:
+        out = torch.empty(batch, 3, val_size, val_size, dtype=torch.float32, device=frames.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.device != frames.device or out.dtype != torch.float32 or out.dim() != 4 or \
+            out.shape[0] < batch or tuple(out.shape[1:]) != (3, val_size, val_size) or not out.is_contiguous():
+        raise RuntimeError(f'val_aug_batch: out is a contiguous float32 [>= {batch}, 3, {val_size}, {val_size}] tensor on the device of the frames')
+    with torch.cuda.device(frames.device):
+        hip.check(hip.lib().ym_val_preprocess_batch(ctypes.c_void_p(frames.data.data_ptr()), int(frames.dtype == torch.uint8),
+                                                    frames.table(), batch, val_size, _MEAN, _STD, hip.ptr(out), hip.stream_ptr()),
+                  'ym_val_preprocess_batch')
+    return out[:batch]
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@ with cv2 on the host; here the masks, ids, scores and boxes stay where `after_nm
     cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg) -> (total, [obj_0, ...])      what cfg.cutout writes to disk
     draw_batch(dets_padded, imgs, cfg, fps=None) -> uint8 [B, H, W, 3]
         for `after_nms_batch(..., sync=False)`: counts, scores and cfg.visual_thre are consumed on the device, no host read.
+        With `imgs` a `FrameBatch` (frames of different sizes) and the per-image mask views of the ragged `after_nms_batch`:
+        -> a new `FrameBatch`, still one launch set.
 
 Mask colours, blend, outline / plate geometry, draw order and the score formatting are the reference's, exactly (integer arithmetic
 throughout).  The label PIXELS are this package's own fixed-cell bitmap font (`utils/font.py`), not cv2's anti-aliased Hershey Duplex.
@@ -174,12 +176,100 @@ def cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg):
     return total[0], objs
 
 
-def draw_batch(dets_padded, imgs, cfg, fps=None):
+def _ragged_mask_table(masks, sizes, max_det):
+    """The list of per-image mask views of the ragged `after_nms_batch` -> (view 0, packed, the `ym_after_nms_ragged` table rebuilt
+    from the views' data pointers relative to view 0).  Raises unless the views are `[max_det, h_b, w_b]` blocks of ONE allocation in
+    `ragged_layout` order."""
+    from .output_utils import ragged_layout
+    if not isinstance(masks, (list, tuple)) or len(masks) != len(sizes):
+        raise RuntimeError(f'draw_batch: with a FrameBatch the masks are the list of {len(sizes)} per-image views that '
+                           f'after_nms_batch(dets, hs, ws, ..., sync=False) returns')
+    packed = isinstance(masks[0], PackedMasks)
+    words = []
+    for b, (m, (h, w)) in enumerate(zip(masks, sizes)):
+        if isinstance(m, PackedMasks) != packed:
+            raise RuntimeError('draw_batch: dense and packed mask views in one batch')
+        t = m.bits if packed else m
+        if not torch.is_tensor(t) or tuple(m.shape) != (max_det, h, w) or t.dtype != (torch.int64 if packed else torch.float32) or \
+                not t.is_contiguous():
+            raise RuntimeError(f'draw_batch: image {b}: masks {tuple(m.shape)} do not fit {max_det} rows on a {h} x {w} frame')
+        words.append(t)
+    offsets, _ = ragged_layout(sizes, max_det, packed)
+    esz = 8 if packed else 4
+    base = words[0].data_ptr()
+    for b, t in enumerate(words):
+        if t.device != words[0].device or t.data_ptr() - base != offsets[b] * esz:
+            raise RuntimeError(f'draw_batch: the mask view of image {b} is not at its place in one ragged_layout allocation')
+    table = (hip.RaggedImage * len(sizes))(*[hip.RaggedImage(h, w, o) for (h, w), o in zip(sizes, offsets)])
+    return words[0], packed, table
+
+
+def _draw_batch_ragged(dets_padded, imgs, cfg, fps, out):
+    from .frames import FrameBatch
+    from .output_utils import _scratch
+    ids, scores, boxes, masks, counts = dets_padded
+    imgs.need_cuda('utils.draw.draw_batch')
+    if imgs.dtype != torch.uint8:
+        raise RuntimeError('draw_batch: the frames are uint8')
+    for t in (ids, scores, boxes, counts):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise RuntimeError('yolact_minimal_amd.utils.draw.draw_batch needs the detections as CUDA (HIP) tensors, as after_nms_batch '
+                               'returns them; there is no CPU path.')
+    device = _device_of(ids, 'draw_batch')
+    if ids.dim() != 2 or imgs.device != device:
+        raise RuntimeError('draw_batch: ids [B, max_det] on the device of the frames expected')
+    batch, max_det = ids.shape
+    if len(imgs) != batch or max_det > hip.DRAW_MAX_DET:
+        raise RuntimeError(f'draw_batch: {len(imgs)} frames for {batch} detection sets of {max_det} rows (at most {hip.DRAW_MAX_DET})')
+    flags = _flags(cfg)
+    mask0, packed, mask_table = None, False, None
+    if not flags & hip.DRAW_HIDE_MASK and max_det:
+        mask0, packed, mask_table = _ragged_mask_table(masks, imgs.sizes, max_det)
+        if mask0.device != device:
+            raise RuntimeError(f'draw_batch: masks on {mask0.device}, detections on {device}')
+    if out is None:
+        out = FrameBatch.empty_like(imgs)
+    elif not isinstance(out, FrameBatch) or out.sizes != imgs.sizes or out.dtype != torch.uint8 or out.device != device:
+        raise RuntimeError('draw_batch: the destination is a uint8 FrameBatch of the same sizes on the same device')
+    fps_text = None
+    if flags & hip.DRAW_REAL_TIME:
+        if fps is None:
+            raise RuntimeError('draw_img: cfg.real_time needs the fps value')
+        fps_text = f'fps: {fps:.2f}'.encode('ascii', 'replace')
+    res = _resources(device, cfg)
+    L = hip.lib()
+    with torch.cuda.device(device):
+        nbytes = L.ym_draw_workspace_bytes(batch, max_det)
+        if nbytes == 0:
+            raise RuntimeError('ym_draw_workspace_bytes: ' + L.ym_last_error().decode())
+        ws = _scratch(device, nbytes)
+        draw = L.ym_draw_detections_ragged_packed if packed else L.ym_draw_detections_ragged
+        hip.check(draw(
+            hip.ptr(imgs.data, torch.uint8), hip.ptr(mask0, mask0.dtype) if mask0 is not None else None,
+            hip.ptr(ids.contiguous(), torch.int64), hip.ptr(scores.contiguous()) if scores is not None else None,
+            hip.ptr(boxes.contiguous(), torch.int32), hip.ptr(counts.contiguous(), torch.int32) if counts is not None else None,
+            batch, max_det, imgs.table(), mask_table, hip.ptr(res['palette'], torch.uint8), res['palette_n'], int(cfg.num_classes),
+            hip.ptr(res['names'], torch.uint8), res['num_names'], hip.ptr(res['font'], torch.int16), flags,
+            float(getattr(cfg, 'visual_thre', 0) or 0), fps_text, hip.ptr(out.data, torch.uint8),
+            ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()), 'ym_draw_detections_ragged')
+    return out
+
+
+def draw_batch(dets_padded, imgs, cfg, fps=None, _out=None):
     """Render B frames from `after_nms_batch(dets, img_h, img_w, cfg, sync=False)` = (ids, scores, boxes_px, masks, counts), all
     padded to max_detections rows, in one launch set.  `imgs` is a device uint8 [B, H, W, 3] tensor; so is the result.  Frame b
     equals `draw_img` on `after_nms`'s result for image b: rows past counts[b] and rows under cfg.visual_thre are dropped ON THE
     DEVICE, a frame left without detections comes back unchanged.  No host synchronisation and no device-to-host copy (the palette /
-    class-name / font tables are uploaded by the first call for a (device, class names) pair)."""
+    class-name / font tables are uploaded by the first call for a (device, class names) pair).
+    Frames of DIFFERENT sizes: `imgs` is a `FrameBatch` (utils/frames.py) and `masks` the list of per-image views that
+    `after_nms_batch(dets, hs, ws, cfg, sync=False)` returns (dense or `PackedMasks`; ignored with `cfg.hide_mask`); the result is a
+    new `FrameBatch` of the same sizes (`ym_draw_detections_ragged`: one prep launch and at most two frame launches for the batch).
+    (`_out`: the destination `FrameBatch`, for the tests' guard bytes; `_out is imgs` draws in place.)"""
+    from .frames import FrameBatch
+    if isinstance(imgs, FrameBatch):
+        return _draw_batch_ragged(dets_padded, imgs, cfg, fps, _out)
+    if _out is not None:
+        raise RuntimeError('draw_batch: a destination is taken with a FrameBatch only')
     ids, scores, boxes, masks, counts = dets_padded
     device = _device_of(ids, 'draw_batch')
     if not torch.is_tensor(imgs) or not imgs.is_cuda or imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3 or \
