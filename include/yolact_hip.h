@@ -711,7 +711,9 @@ int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* bo
  * frame are those of the uniform entry called on that frame alone.  At most two frame launches: the images whose rows are whole
  * 4-pixel groups at aligned addresses take the 16-byte path, the others the element-wise one; the grid is the largest tile count of
  * a launch's images x B, workgroups of other images or past an image's own tiles exit before touching memory.  Nothing outside
- * the frames is written.  Workspace: ym_draw_workspace_bytes(B, max_det), as for the uniform entries. */
+ * the frames is written.  Workspace: ym_draw_workspace_bytes(B, max_det), as for the uniform entries.  The four ym_draw_detections_*
+ * entries share one launch path (draw.hip, draw_launches): only the limits differ -- B <= 65535 and the cutout matte for one frame
+ * size, B <= YM_RAGGED_MAX_IMAGES and no matte for the tables -- and each entry reports errors under its own name. */
 int ym_val_preprocess_batch(const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S, const float* mean_bgr,
                             const float* std_bgr, float* out, ym_stream_t s);
 int ym_draw_detections_ragged(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores, const int32_t* boxes_px,

@@ -221,3 +221,28 @@ def test_draw_detections_ragged_refuses_bad_tables(packed):
         assert rc == -1 and text in err, (bad_blocks, rc, err)
     rc, err = _draw_ragged_rc([(4, 4, 256 * i) for i in range(33)], None, packed, flags=hip.DRAW_HIDE_MASK)
     assert rc == -1 and '1 .. 32 images per call' in err, (rc, err)
+
+
+def _draw_uniform_rc(packed, batch, max_det, palette_n=100):
+    lib = hip.lib()
+    mem = torch.zeros(1 << 16, dtype=torch.uint8)
+    p = ctypes.c_void_p(mem.data_ptr())
+    fn = lib.ym_draw_detections_batch_packed if packed else lib.ym_draw_detections_batch
+    rc = fn(p, p, p, p, p, p, batch, max_det, 4, 8, p, palette_n, 81, p, 80, p, 0, 0.0, None, p, None, p, 1 << 16, None)
+    return rc, lib.ym_last_error().decode()
+
+
+def test_uniform_draw_entries_take_33_frames_and_every_entry_names_itself():
+    """The uniform entries share their launch path with the ragged ones but not their limit of 32 images: a batch of 33 gets past the
+    batch check (here it is refused for a LATER argument, an empty palette), and each of the four entries reports under its own name."""
+    rc, err = _draw_uniform_rc(False, 33, 1, palette_n=0)
+    assert rc == -1 and err.startswith('ym_draw_detections_batch: num_classes=81 needs a palette'), (rc, err)
+    rc, err = _draw_uniform_rc(False, 33, -1)
+    assert rc == -1 and err.startswith('ym_draw_detections_batch: 1 <= B <= 65535 and 0 <= max_det'), (rc, err)
+    rc, err = _draw_uniform_rc(True, 33, -1)
+    assert rc == -1 and err.startswith('ym_draw_detections_batch_packed: 1 <= B <= 65535 and 0 <= max_det'), (rc, err)
+    for packed, name in ((False, 'ym_draw_detections_ragged'), (True, 'ym_draw_detections_ragged_packed')):
+        rc, err = _draw_ragged_rc([(8, 8, 0), (5, 7, 256)], None, packed, flags=hip.DRAW_HIDE_MASK, max_det=-1)
+        assert rc == -1 and err.startswith(name + ': 1 <= B <= 32 and 0 <= max_det'), (rc, err)
+        rc, err = _draw_ragged_rc([(4, 4, 256 * i) for i in range(33)], None, packed, flags=hip.DRAW_HIDE_MASK)
+        assert rc == -1 and err.startswith(name + ': 1 .. 32 images per call'), (rc, err)

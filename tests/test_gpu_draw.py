@@ -227,6 +227,59 @@ def test_draw_batch_equals_per_image_without_host_reads():
     assert torch.equal(out[2], imgs[2]) and torch.equal(out[3], imgs[3]) and not torch.equal(out[0], imgs[0])
 
 
+def _uniform_batch(hw, counts, max_det, seed):
+    """-> (per-image numpy inputs of tests.draw_ref.synth, the padded device tensors ids / scores / boxes / masks [B, max_det, H, W] /
+    counts, the frames [B, H, W, 3]).  Rows past counts[b] hold garbage: NaN scores, huge boxes, all-ones masks."""
+    h, w = hw
+    batch = len(counts)
+    per_image = [R.synth(n, h, w, seed=seed + b) for b, n in enumerate(counts)]
+    ids = torch.full((batch, max_det), 1 << 40, dtype=torch.int64)
+    scores = torch.full((batch, max_det), float('nan'))
+    boxes = torch.full((batch, max_det, 4), 1 << 30, dtype=torch.int32)
+    boxes[:, :, :2] = -(1 << 30)
+    masks = torch.ones(batch, max_det, h, w)
+    for b, n in enumerate(counts):
+        i, s, bx, m, _ = per_image[b]
+        if n:
+            ids[b, :n], scores[b, :n], boxes[b, :n], masks[b, :n] = (torch.from_numpy(a) for a in (i, s, bx, m))
+    imgs = torch.from_numpy(np.stack([p[4] for p in per_image]))
+    return per_image, [t.to(DEV) for t in (ids, scores, boxes, masks, torch.tensor(counts, dtype=torch.int32))], imgs.to(DEV)
+
+
+def _check_uniform_batch(hw, counts, max_det, seed, packed):
+    """`draw_batch` on a uniform batch, byte for byte against the host oracle and against `draw_img` per image -> the oracle's frames."""
+    from yolact_minimal_amd.utils.draw import draw_batch, draw_img
+    from yolact_minimal_amd.utils.packed_masks import PackedMasks
+    cfg = R.make_cfg()
+    per_image, (ids, scores, boxes, masks, cnt), imgs = _uniform_batch(hw, counts, max_det, seed)
+    before = imgs.clone()
+    out = draw_batch((ids, scores, boxes, PackedMasks.pack(masks) if packed else masks, cnt), imgs, cfg)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.shape == imgs.shape and torch.equal(imgs, before)
+    want = []
+    for b, n in enumerate(counts):
+        i, s, bx, m, img = per_image[b]
+        want.append(R.draw_ref(i, s, bx, m, img, cfg) if n else img)
+        single = draw_img(ids[b, :n], scores[b, :n], boxes[b, :n], masks[b, :n], imgs[b], cfg) if n else imgs[b]
+        assert np.array_equal(out[b].cpu().numpy(), want[b]), f'frame {b} differs from the oracle'
+        assert torch.equal(out[b], single), f'frame {b} differs from draw_img'
+        assert n or torch.equal(out[b], imgs[b]), f'frame {b} has no detection and must come back unchanged'
+    return want, [p[4] for p in per_image]
+
+
+@pytest.mark.parametrize('packed', [False, True], ids=['dense', 'packed'])
+@pytest.mark.parametrize('hw', [(6, 7), (8, 8)], ids=['6x7_elementwise', '8x8_16byte'])
+def test_uniform_draw_batch_drops_the_rows_past_the_counts(hw, packed):
+    want, frames = _check_uniform_batch(hw, [3, 0, 1], 3, 71, packed)
+    assert not np.array_equal(want[0], frames[0]) and not np.array_equal(want[2], frames[2])
+
+
+def test_uniform_draw_batch_of_33_frames():
+    """One frame more than a ragged batch may hold (and than the bits of its per-launch image set): every frame is drawn."""
+    want, frames = _check_uniform_batch((4, 8), [1] * 33, 1, 83, False)
+    assert all(not np.array_equal(w, f) for w, f in zip(want, frames)), 'a frame came back undrawn'
+    assert len({w.tobytes() for w in want}) == 33, 'the 33 frames differ in content'
+
+
 def test_dropin_draw_img_draws_without_a_checkout(tmp_path):
     code = textwrap.dedent('''
         import numpy as np, torch

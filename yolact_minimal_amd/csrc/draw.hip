@@ -13,9 +13,12 @@
 //                   of a detection), same bytes out.
 //  k_draw_frame<VEC, PACKED, Sizes>: where frame b and its mask block lie comes from a small object in the kernel arguments, like
 //                   k_masks_fused's (masks.hip): UniformSizes = one H x W, frame b right behind frame b - 1 (ym_draw_detections_batch);
-//                   RaggedSizes = ym_draw_detections_ragged's two per-image tables.  grid.x is then the largest tile count of the
-//                   batch, workgroups past an image's own count return at once, and VEC is decided per image: one launch for the
-//                   images that take <true>, one for the others (bit b of `set_bits` = image b belongs to this launch).
+//                   RaggedSizes = ym_draw_detections_ragged's two per-image tables.
+//  Host side: the four ym_draw_detections_* entries check what is their own, build their Sizes and share ONE launch path,
+//                   draw_launches<Sizes>, over their common arguments (DrawArgs).  It asks the Sizes which images take VEC = true and
+//                   which VEC = false and launches each non-empty set once: a uniform batch is one set (any B up to 65535); a ragged
+//                   batch decides per image (bit b of `set_bits` = image b belongs to this launch, B <= YM_RAGGED_MAX_IMAGES), grid.x
+//                   is the set's largest tile count and workgroups past an image's own count return at once.
 // All arithmetic is integer; results are exact (tests compare with tolerance 0).
 #include <algorithm>
 #include "ym_common.h"
@@ -232,19 +235,38 @@ __device__ __forceinline__ void bits_batch(const int* recs, const unsigned long 
     }
 }
 
-__host__ __device__ inline size_t mask_row(bool packed, int W) { return packed ? (size_t)((W + 63) >> 6) : (size_t)W; }
 __host__ __device__ inline int frame_tiles(int H, int W) { return (H * ((W + 3) >> 2) + FRAME_THREADS - 1) / FRAME_THREADS; }
 
+// What the four ym_draw_detections_* entries share: their arguments as one plain host struct (`masks`: float [max_det][H][W] per
+// image, or -- `packed` -- the bit rows uint64 [max_det][H][ceil(W / 64)]; `cutout_total`: the uniform entries only).
+struct DrawArgs {
+    const uint8_t* img; const void* masks; bool packed; const int64_t* ids; const float* scores; const int32_t* boxes_px;
+    const int32_t* counts; int B, max_det; const uint8_t* palette; int palette_n, num_classes; const char* names; int num_names;
+    const uint16_t* font; int flags; float visual_thre; const char* fps_text; uint8_t* out; uint8_t* cutout_total; void* workspace;
+    size_t workspace_bytes; ym_stream_t s;
+    bool reads_masks() const { return !(flags & YM_DRAW_HIDE_MASK) && max_det > 0; }
+    // may a W pixels wide frame `at` bytes into img / out, its mask block `block` elements into masks, take k_draw_frame<true>?
+    bool vec_ok(int W, size_t at, size_t block) const {
+        const uintptr_t m = (uintptr_t)masks + block * (packed ? 8 : 4);
+        return W % 4 == 0 && ((uintptr_t)img + at) % 4 == 0 && ((uintptr_t)out + at) % 4 == 0 && (uintptr_t)cutout_total % 4 == 0 &&
+               (!reads_masks() || m % 16 == 0 || (packed && m % 8 == 0));
+    }
+};
+
 // first_byte(b, y, x): where pixel (y, x) of frame b starts in img / out / cut_total; masks(b): first element (float, or word when
-// packed) of its mask block.
+// packed) of its mask block.  The host asks select(vec, a): the largest tile count among the images that take k_draw_frame<vec>
+// (0 = no launch).
 struct UniformSizes {
     typedef int i32x2 __attribute__((ext_vector_type(2)));      // (one vector, not two ints: see masks.hip's UniformSizes)
     i32x2 hw;                                                   // {H, W}
     __host__ __device__ int h(int) const { return hw[0]; }
     __host__ __device__ int w(int) const { return hw[1]; }
     __device__ size_t first_byte(int b, int y, int x) const { return (((size_t)b * hw[0] + y) * hw[1] + x) * 3; }
-    __device__ size_t masks(int b, int max_det, bool packed) const { return (size_t)b * max_det * hw[0] * mask_row(packed, hw[1]); }
+    __device__ size_t masks(int b, int max_det, bool packed) const { return (size_t)b * max_det * hw[0] * ym_mask_row(packed, hw[1]); }
     __device__ bool nothing_to_do(int, int) const { return false; }
+    // all images or none: image 0's answer holds for every image, since with W % 4 == 0 every frame stride H * W * 3 is a multiple of
+    // 4, every dense mask stride one of 16 bytes and every packed one of 8
+    int select(bool vec, const DrawArgs& a) const { return vec == a.vec_ok(hw[1], 0, 0) ? frame_tiles(hw[0], hw[1]) : 0; }
 };
 
 struct RaggedSizes {
@@ -255,6 +277,17 @@ struct RaggedSizes {
     __device__ size_t first_byte(int b, int y, int x) const { return (size_t)frames.img[b].offset + ((size_t)y * w(b) + x) * 3; }
     __device__ size_t masks(int b, int, bool) const { return (size_t)blocks.img[b].offset; }
     __device__ bool nothing_to_do(int b, int tile) const { return !((set_bits >> b) & 1u) || tile >= frame_tiles(h(b), w(b)); }
+    // image by image (a.B <= YM_RAGGED_MAX_IMAGES = the bits of `set_bits`), which it records for the kernel
+    int select(bool vec, const DrawArgs& a) {
+        int tiles = 0;
+        set_bits = 0u;
+        for (int b = 0; b < a.B; ++b)
+            if (vec == a.vec_ok(w(b), frames.img[b].offset, blocks.img[b].offset)) {
+                set_bits |= 1u << b;
+                tiles = std::max(tiles, frame_tiles(h(b), w(b)));
+            }
+        return tiles;
+    }
 };
 
 // (`sz` BEFORE `max_det`: UniformSizes' two ints then lie where `H, W` always lay and come in with the first scalar load; behind
@@ -426,103 +459,85 @@ extern "C" size_t ym_draw_workspace_bytes(int B, int max_det) {
     return (size_t)B * (HDR + (size_t)max_det * REC) * sizeof(int);
 }
 
-// What every draw entry checks besides its frame sizes; *fps_len / f: the fps text packed for k_draw_prep.
-static int draw_check(const char* what, const uint8_t* img, const void* masks, bool packed, const int64_t* ids, const float* scores,
-                      const int32_t* boxes_px, int B, int max_B, int max_det, const uint8_t* palette, int palette_n, int num_classes,
-                      const char* names, int num_names, const uint16_t* font, int flags, float visual_thre, const char* fps_text,
-                      const uint8_t* out, const uint8_t* cutout_total, const void* workspace, size_t workspace_bytes,
-                      unsigned long long (&f)[4], int* fps_len) {
-    YM_REQUIRE(B >= 1 && B <= max_B && max_det >= 0 && max_det <= YM_DRAW_MAX_DET, "%s: 1 <= B <= %d and 0 <= max_det <= %d required (B=%d max_det=%d)",
-               what, max_B, YM_DRAW_MAX_DET, B, max_det);
-    YM_REQUIRE(img && out && palette && font && workspace, "%s: null img / out / palette / font / workspace", what);
-    YM_REQUIRE(max_det == 0 || (ids && boxes_px && names), "%s: null ids / boxes_px / names", what);
-    YM_REQUIRE(((uintptr_t)names & 3) == 0, "%s: the class-name table must be 4-byte aligned", what);
-    const bool hide_mask = flags & YM_DRAW_HIDE_MASK;
-    YM_REQUIRE(hide_mask || max_det == 0 || masks, "%s: masks are needed unless YM_DRAW_HIDE_MASK is set", what);
-    YM_REQUIRE(!cutout_total || !hide_mask, "%s: the cutout matte needs the masks (YM_DRAW_HIDE_MASK is set)", what);
-    YM_REQUIRE(scores || ((flags & YM_DRAW_HIDE_SCORE) && !(visual_thre > 0.f)) || max_det == 0,
+// What every draw entry checks besides its frame sizes (`what` names the entry in errors).
+static int draw_check(const char* what, const DrawArgs& a, int max_B) {
+    YM_REQUIRE(a.B >= 1 && a.B <= max_B && a.max_det >= 0 && a.max_det <= YM_DRAW_MAX_DET, "%s: 1 <= B <= %d and 0 <= max_det <= %d required (B=%d max_det=%d)",
+               what, max_B, YM_DRAW_MAX_DET, a.B, a.max_det);
+    YM_REQUIRE(a.img && a.out && a.palette && a.font && a.workspace, "%s: null img / out / palette / font / workspace", what);
+    YM_REQUIRE(a.max_det == 0 || (a.ids && a.boxes_px && a.names), "%s: null ids / boxes_px / names", what);
+    YM_REQUIRE(((uintptr_t)a.names & 3) == 0, "%s: the class-name table must be 4-byte aligned", what);
+    YM_REQUIRE(!a.reads_masks() || a.masks, "%s: masks are needed unless YM_DRAW_HIDE_MASK is set", what);
+    YM_REQUIRE(!a.cutout_total || !(a.flags & YM_DRAW_HIDE_MASK), "%s: the cutout matte needs the masks (YM_DRAW_HIDE_MASK is set)", what);
+    YM_REQUIRE(a.scores || ((a.flags & YM_DRAW_HIDE_SCORE) && !(a.visual_thre > 0.f)) || a.max_det == 0,
                "%s: scores are needed for the labels and for visual_thre", what);
-    YM_REQUIRE(num_classes >= 2 && palette_n >= 1 && palette_n <= PAL && num_classes - 1 <= palette_n && num_names >= 0,
-               "%s: num_classes=%d needs a palette of at least num_classes-1 (<= %d) colours, got %d", what, num_classes, PAL, palette_n);
-    const size_t need = ym_draw_workspace_bytes(B, max_det);
-    YM_REQUIRE(workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, "%s: workspace of %zu bytes (16-byte aligned) needed, got %zu",
-               what, need, workspace_bytes);
-    YM_REQUIRE(!packed || (uintptr_t)masks % 8 == 0, "%s: the mask words must be 8-byte aligned", what);
-    *fps_len = 0;
-    if (flags & YM_DRAW_REAL_TIME) {
-        YM_REQUIRE(fps_text, "%s: YM_DRAW_REAL_TIME needs the fps text", what);
-        for (; *fps_len < 32 && fps_text[*fps_len]; ++*fps_len) {
-            const unsigned char c = (unsigned char)fps_text[*fps_len];
-            f[*fps_len >> 3] |= (unsigned long long)((c < 0x20 || c > 0x7E) ? '?' : c) << ((*fps_len & 7) * 8);
-        }
-    }
+    YM_REQUIRE(a.num_classes >= 2 && a.palette_n >= 1 && a.palette_n <= PAL && a.num_classes - 1 <= a.palette_n && a.num_names >= 0,
+               "%s: num_classes=%d needs a palette of at least num_classes-1 (<= %d) colours, got %d", what, a.num_classes, PAL, a.palette_n);
+    const size_t need = ym_draw_workspace_bytes(a.B, a.max_det);
+    YM_REQUIRE(a.workspace_bytes >= need && ((uintptr_t)a.workspace & 15) == 0, "%s: workspace of %zu bytes (16-byte aligned) needed, got %zu",
+               what, need, a.workspace_bytes);
+    YM_REQUIRE(!a.packed || (uintptr_t)a.masks % 8 == 0, "%s: the mask words must be 8-byte aligned", what);
+    YM_REQUIRE(a.fps_text || !(a.flags & YM_DRAW_REAL_TIME), "%s: YM_DRAW_REAL_TIME needs the fps text", what);
     return YM_OK;
 }
 
-// may a frame / mask block that starts at these addresses take k_draw_frame<true>?
-static bool draw_vec_ok(int W, const uint8_t* img, const uint8_t* out, const uint8_t* cutout_total, const void* masks, bool packed,
-                        bool hide_mask) {
-    return (W % 4 == 0) && ((uintptr_t)img % 4 == 0) && ((uintptr_t)out % 4 == 0) && (!cutout_total || (uintptr_t)cutout_total % 4 == 0) &&
-           (hide_mask || (uintptr_t)masks % 16 == 0 || (packed && (uintptr_t)masks % 8 == 0));
+// The launch set of the four entries (arguments checked by the caller): the prep launch, then k_draw_frame<true> over the images that
+// take the 16-byte instance and k_draw_frame<false> over the others; an empty set is not launched.
+template <class Sizes>
+static int draw_launches(const DrawArgs& a, Sizes sz) {
+    unsigned long long f[4] = {0, 0, 0, 0};                  // the fps text packed for k_draw_prep
+    int fps_len = 0;
+    if (a.flags & YM_DRAW_REAL_TIME)
+        for (; fps_len < 32 && a.fps_text[fps_len]; ++fps_len) {
+            const unsigned char c = (unsigned char)a.fps_text[fps_len];
+            f[fps_len >> 3] |= (unsigned long long)((c < 0x20 || c > 0x7E) ? '?' : c) << ((fps_len & 7) * 8);
+        }
+    hipStream_t st = (hipStream_t)a.s;
+    k_draw_prep<<<a.B, 64, 0, st>>>(a.ids, a.scores, a.boxes_px, a.counts, a.max_det, a.palette, a.palette_n, a.names, a.num_names, a.flags,
+                                    a.visual_thre, f[0], f[1], f[2], f[3], fps_len, (int*)a.workspace);
+    const int rc = ym_check_launch("k_draw_prep");
+    if (rc != YM_OK) return rc;
+    const size_t lds = (size_t)(PAL + HDR + a.max_det * REC) * sizeof(int);
+#define YM_DRAW_FRAME(V, P)                                                                                                         \
+    k_draw_frame<V, P, Sizes><<<grid, FRAME_THREADS, lds, st>>>(a.img, a.masks, (const int*)a.workspace, sz, a.max_det, a.palette,  \
+                                                                a.palette_n, a.num_classes - 1, a.font, a.flags, a.out, a.cutout_total)
+    for (int vec = 1; vec >= 0; --vec) {
+        const int tiles = sz.select(vec, a);
+        if (!tiles) continue;
+        const dim3 grid(tiles, a.B);
+        if (a.packed) { if (vec) YM_DRAW_FRAME(true, true); else YM_DRAW_FRAME(false, true); }
+        else { if (vec) YM_DRAW_FRAME(true, false); else YM_DRAW_FRAME(false, false); }
+    }
+#undef YM_DRAW_FRAME
+    return ym_check_launch("k_draw_frame");
 }
 
-#define YM_DRAW_FRAME(V, P, S)                                                                                                      \
-    k_draw_frame<V, P, S><<<grid, FRAME_THREADS, lds, st>>>(img, masks, (const int*)workspace, sz, max_det, palette, palette_n,    \
-                                                            num_classes - 1, font, flags, out, cutout_total)
-
-// `masks`: float [B][max_det][H][W], or (packed) the bit rows uint64 [B][max_det][H][ceil(W / 64)]
-static int draw_detections(const uint8_t* img, const void* masks, bool packed, const int64_t* ids, const float* scores,
-                           const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
-                           const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
-                           const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
-                           uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    const char* what = packed ? "ym_draw_detections_batch_packed" : "ym_draw_detections_batch";
-    unsigned long long f[4] = {0, 0, 0, 0};
-    int fps_len = 0;
+// One H x W for every frame, frame b right behind frame b - 1; any B up to the grid's 65535.
+static int draw_uniform(const char* what, const DrawArgs& a, int H, int W) {
     YM_REQUIRE(frame_dims_ok(H, W), "%s: frame %dx%d out of range (1..16384)", what, H, W);
-    int rc = draw_check(what, img, masks, packed, ids, scores, boxes_px, B, 65535, max_det, palette, palette_n, num_classes, names, num_names,
-                        font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, f, &fps_len);
+    const int rc = draw_check(what, a, 65535);
     if (rc != YM_OK) return rc;
-    hipStream_t st = (hipStream_t)s;
-    k_draw_prep<<<B, 64, 0, st>>>(ids, scores, boxes_px, counts, max_det, palette, palette_n, names, num_names, flags, visual_thre, f[0],
-                                  f[1], f[2], f[3], fps_len, (int*)workspace);
-    rc = ym_check_launch("k_draw_prep");
-    if (rc != YM_OK) return rc;
-    const size_t lds = (size_t)(PAL + HDR + max_det * REC) * sizeof(int);
-    const dim3 grid(frame_tiles(H, W), B);
-    const bool vec = draw_vec_ok(W, img, out, cutout_total, masks, packed, flags & YM_DRAW_HIDE_MASK);
-    const UniformSizes sz = {{H, W}};
-    if (packed) { if (vec) YM_DRAW_FRAME(true, true, UniformSizes); else YM_DRAW_FRAME(false, true, UniformSizes); }
-    else { if (vec) YM_DRAW_FRAME(true, false, UniformSizes); else YM_DRAW_FRAME(false, false, UniformSizes); }
-    return ym_check_launch("k_draw_frame");
+    return draw_launches(a, UniformSizes{{H, W}});
 }
 
 // `frames`: frame b's size and its first byte in img AND out; `mask_blocks`: ym_after_nms_ragged[_packed]'s table (NULL with
 // YM_DRAW_HIDE_MASK: the masks are not read)
-static int draw_detections_ragged(const uint8_t* img, const void* masks, bool packed, const int64_t* ids, const float* scores,
-                                  const int32_t* boxes_px, const int32_t* counts, int B, int max_det, const ym_ragged_image* frames,
-                                  const ym_ragged_image* mask_blocks, const uint8_t* palette, int palette_n, int num_classes,
-                                  const char* names, int num_names, const uint16_t* font, int flags, float visual_thre,
-                                  const char* fps_text, uint8_t* out, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    const char* what = packed ? "ym_draw_detections_ragged_packed" : "ym_draw_detections_ragged";
-    unsigned long long f[4] = {0, 0, 0, 0};
-    int fps_len = 0;
-    uint8_t* const cutout_total = nullptr;
+static int draw_ragged(const char* what, const DrawArgs& a, const ym_ragged_image* frames, const ym_ragged_image* mask_blocks) {
+    const int B = a.B, max_det = a.max_det;
+    const bool packed = a.packed;
     int rc = ym_check_ragged_table(what, frames, B, 1, [](const ym_ragged_image& im) { return (int64_t)im.img_h * im.img_w * 3; });
     if (rc != YM_OK) return rc;
     for (int b = 0; b < B; ++b)
         YM_REQUIRE(frame_dims_ok(frames[b].img_h, frames[b].img_w), "%s: frame %d is %dx%d, out of range (1..16384)", what, b,
                    frames[b].img_h, frames[b].img_w);
-    rc = draw_check(what, img, masks, packed, ids, scores, boxes_px, B, YM_RAGGED_MAX_IMAGES, max_det, palette, palette_n, num_classes, names,
-                    num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, f, &fps_len);
+    rc = draw_check(what, a, YM_RAGGED_MAX_IMAGES);
     if (rc != YM_OK) return rc;
-    const bool hide_mask = flags & YM_DRAW_HIDE_MASK, read_masks = !hide_mask && max_det > 0;
+    const bool read_masks = a.reads_masks();
     YM_REQUIRE(mask_blocks || !read_masks, "%s: the mask block table is needed unless YM_DRAW_HIDE_MASK is set", what);
     RaggedSizes sz = {};
     std::copy(frames, frames + B, sz.frames.img);
-    if (mask_blocks && read_masks) {
+    if (read_masks) {
         rc = ym_check_ragged_table(what, mask_blocks, B, packed ? 8 : 4, [=](const ym_ragged_image& im) {
-            return (int64_t)max_det * im.img_h * (int64_t)mask_row(packed, im.img_w);
+            return (int64_t)max_det * im.img_h * (int64_t)ym_mask_row(packed, im.img_w);
         });
         if (rc != YM_OK) return rc;
         for (int b = 0; b < B; ++b)
@@ -531,41 +546,16 @@ static int draw_detections_ragged(const uint8_t* img, const void* masks, bool pa
                        frames[b].img_h, frames[b].img_w);
         std::copy(mask_blocks, mask_blocks + B, sz.blocks.img);
     }
-    hipStream_t st = (hipStream_t)s;
-    k_draw_prep<<<B, 64, 0, st>>>(ids, scores, boxes_px, counts, max_det, palette, palette_n, names, num_names, flags, visual_thre, f[0],
-                                  f[1], f[2], f[3], fps_len, (int*)workspace);
-    rc = ym_check_launch("k_draw_prep");
-    if (rc != YM_OK) return rc;
-    const size_t lds = (size_t)(PAL + HDR + max_det * REC) * sizeof(int);
-    // the images that take <true> in one launch, the others in a second; an empty set is not launched
-    unsigned vec_bits = 0u, all_bits = 0u;
-    const size_t esz = packed ? 8 : 4;
-    for (int b = 0; b < B; ++b) {
-        all_bits |= 1u << b;
-        const void* mb = read_masks ? (const void*)((const char*)masks + (size_t)sz.blocks.img[b].offset * esz) : nullptr;
-        if (draw_vec_ok(frames[b].img_w, img + frames[b].offset, out + frames[b].offset, nullptr, mb, packed, !read_masks)) vec_bits |= 1u << b;
-    }
-    for (int pass = 0; pass < 2; ++pass) {
-        sz.set_bits = pass == 0 ? vec_bits : (all_bits & ~vec_bits);
-        if (!sz.set_bits) continue;
-        int tiles = 0;
-        for (int b = 0; b < B; ++b)
-            if ((sz.set_bits >> b) & 1u) tiles = std::max(tiles, frame_tiles(frames[b].img_h, frames[b].img_w));
-        const dim3 grid(tiles, B);
-        if (packed) { if (pass == 0) YM_DRAW_FRAME(true, true, RaggedSizes); else YM_DRAW_FRAME(false, true, RaggedSizes); }
-        else { if (pass == 0) YM_DRAW_FRAME(true, false, RaggedSizes); else YM_DRAW_FRAME(false, false, RaggedSizes); }
-    }
-    return ym_check_launch("k_draw_frame");
+    return draw_launches(a, sz);
 }
-#undef YM_DRAW_FRAME
 
 extern "C" int ym_draw_detections_batch(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores,
                                         const int32_t* boxes_px, const int32_t* counts, int B, int max_det, int H, int W,
                                         const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
                                         const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
                                         uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    return draw_detections(img, masks, false, ids, scores, boxes_px, counts, B, max_det, H, W, palette, palette_n, num_classes, names,
-                           num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, s);
+    return draw_uniform("ym_draw_detections_batch", {img, masks, false, ids, scores, boxes_px, counts, B, max_det, palette, palette_n, num_classes,
+                        names, num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, s}, H, W);
 }
 
 extern "C" int ym_draw_detections_batch_packed(const uint8_t* img, const uint64_t* mask_bits, const int64_t* ids, const float* scores,
@@ -573,8 +563,8 @@ extern "C" int ym_draw_detections_batch_packed(const uint8_t* img, const uint64_
                                                const uint8_t* palette, int palette_n, int num_classes, const char* names, int num_names,
                                                const uint16_t* font, int flags, float visual_thre, const char* fps_text, uint8_t* out,
                                                uint8_t* cutout_total, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    return draw_detections(img, mask_bits, true, ids, scores, boxes_px, counts, B, max_det, H, W, palette, palette_n, num_classes, names,
-                           num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, s);
+    return draw_uniform("ym_draw_detections_batch_packed", {img, mask_bits, true, ids, scores, boxes_px, counts, B, max_det, palette, palette_n,
+                        num_classes, names, num_names, font, flags, visual_thre, fps_text, out, cutout_total, workspace, workspace_bytes, s}, H, W);
 }
 
 extern "C" int ym_draw_detections_ragged(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores,
@@ -583,8 +573,8 @@ extern "C" int ym_draw_detections_ragged(const uint8_t* img, const float* masks,
                                          int palette_n, int num_classes, const char* names, int num_names, const uint16_t* font,
                                          int flags, float visual_thre, const char* fps_text, uint8_t* out, void* workspace,
                                          size_t workspace_bytes, ym_stream_t s) {
-    return draw_detections_ragged(img, masks, false, ids, scores, boxes_px, counts, B, max_det, frames, mask_blocks, palette, palette_n,
-                                  num_classes, names, num_names, font, flags, visual_thre, fps_text, out, workspace, workspace_bytes, s);
+    return draw_ragged("ym_draw_detections_ragged", {img, masks, false, ids, scores, boxes_px, counts, B, max_det, palette, palette_n, num_classes,
+                       names, num_names, font, flags, visual_thre, fps_text, out, nullptr, workspace, workspace_bytes, s}, frames, mask_blocks);
 }
 
 extern "C" int ym_draw_detections_ragged_packed(const uint8_t* img, const uint64_t* mask_bits, const int64_t* ids, const float* scores,
@@ -594,8 +584,9 @@ extern "C" int ym_draw_detections_ragged_packed(const uint8_t* img, const uint64
                                                 int num_names, const uint16_t* font, int flags, float visual_thre,
                                                 const char* fps_text, uint8_t* out, void* workspace, size_t workspace_bytes,
                                                 ym_stream_t s) {
-    return draw_detections_ragged(img, mask_bits, true, ids, scores, boxes_px, counts, B, max_det, frames, mask_blocks, palette, palette_n,
-                                  num_classes, names, num_names, font, flags, visual_thre, fps_text, out, workspace, workspace_bytes, s);
+    return draw_ragged("ym_draw_detections_ragged_packed", {img, mask_bits, true, ids, scores, boxes_px, counts, B, max_det, palette, palette_n,
+                       num_classes, names, num_names, font, flags, visual_thre, fps_text, out, nullptr, workspace, workspace_bytes, s}, frames,
+                       mask_blocks);
 }
 
 extern "C" int ym_draw_cutout_objects(const uint8_t* img, const float* masks, int n, int H, int W, uint8_t* out, ym_stream_t s) {

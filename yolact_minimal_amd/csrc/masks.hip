@@ -286,7 +286,6 @@ __device__ __forceinline__ void fused_tile(float* patch, float* cf, const float*
 //                 two-kernel path, and tiles past an image's own count, have nothing to do.
 // Bit-packed output (include/yolact_hip.h "bit-packed instance masks"): a row is wq = ceil(img_w / 64) uint64 instead of img_w floats.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <bool PACKED> __host__ __device__ inline size_t mask_row(int img_w) { return PACKED ? (size_t)((img_w + 63) >> 6) : (size_t)img_w; }
 __host__ __device__ inline int fused_tiles(int img_h, int img_w) { return ((img_w + FT_W - 1) / FT_W) * ((img_h + FT_H - 1) / FT_H); }
 
 // Does the fused kernel's LDS patch hold the source pixels of one output tile at this scale?
@@ -303,18 +302,17 @@ struct UniformSizes {
     i32x2 hw;                                  // {img_h, img_w}
     __host__ __device__ int h(int) const { return hw[0]; }
     __host__ __device__ int w(int) const { return hw[1]; }
-    template <bool PACKED> __host__ __device__ size_t base(int b, int max_det, int d = 0) const { return ((size_t)b * max_det + d) * (size_t)hw[0] * mask_row<PACKED>(hw[1]); }
+    template <bool PACKED> __host__ __device__ size_t base(int b, int max_det, int d = 0) const { return ((size_t)b * max_det + d) * (size_t)hw[0] * ym_mask_row(PACKED, hw[1]); }
     bool fused(int, int Hp, int Wp) const { return fused_fits(Hp, Wp, hw[0], hw[1]); }
     __device__ bool nothing_to_do(int, int) const { return false; }
 };
 
-struct RaggedTable { ym_ragged_image img[YM_RAGGED_MAX_IMAGES]; };
 struct RaggedSizes {
-    RaggedTable tab;
+    YmRaggedTable tab;
     unsigned fused_bits;
     __host__ __device__ int h(int b) const { return tab.img[b].img_h; }
     __host__ __device__ int w(int b) const { return tab.img[b].img_w; }
-    template <bool PACKED> __host__ __device__ size_t base(int b, int, int d = 0) const { return (size_t)tab.img[b].offset + (size_t)d * h(b) * mask_row<PACKED>(w(b)); }
+    template <bool PACKED> __host__ __device__ size_t base(int b, int, int d = 0) const { return (size_t)tab.img[b].offset + (size_t)d * h(b) * ym_mask_row(PACKED, w(b)); }
     __host__ __device__ bool fused(int b, int = 0, int = 0) const { return (fused_bits >> b) & 1u; }
     __device__ bool nothing_to_do(int b, int tile) const { return !fused(b) || tile >= fused_tiles(h(b), w(b)); }
 };
@@ -504,26 +502,16 @@ extern "C" int ym_after_nms_batch_packed(const float* proto, const float* coefs,
 }
 
 // ---- batches whose images differ in size -----------------------------------------------------------------------------------------
-// Checks the table; *fused = bit b set when image b takes the fused kernel.
+// Checks the shape and the table; *fused = bit b set when image b takes the fused kernel.
 static int ragged_check(const char* what, const ym_ragged_image* images, int B, int max_det, int Hp, int Wp, bool packed, unsigned* fused) {
-    YM_REQUIRE(images, "%s: null image table", what);
-    YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
     YM_REQUIRE(max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0, "%s: bad shape", what);
-    const int64_t esz = packed ? 8 : 4;
+    const int rc = ym_check_ragged_table(what, images, B, packed ? 8 : 4, [=](const ym_ragged_image& im) {
+        return (int64_t)max_det * im.img_h * (int64_t)ym_mask_row(packed, im.img_w);
+    });
+    if (rc != YM_OK) return rc;
     *fused = 0u;
-    for (int b = 0; b < B; ++b) {
-        const ym_ragged_image& im = images[b];
-        YM_REQUIRE(im.img_h > 0 && im.img_w > 0, "%s: image %d is %d x %d", what, b, im.img_h, im.img_w);
-        YM_REQUIRE(im.offset >= 0 && (im.offset * esz) % YM_RAGGED_ALIGN_BYTES == 0, "%s: image %d: block offset %lld is not a multiple of %d bytes",
-                   what, b, (long long)im.offset, YM_RAGGED_ALIGN_BYTES);
-        if (fused_fits(Hp, Wp, im.img_h, im.img_w)) *fused |= 1u << b;
-    }
-    for (int a = 0; a < B; ++a)          // blocks must not overlap (B <= 32: a few hundred compares)
-        for (int b = a + 1; b < B; ++b) {
-            const int64_t ea = images[a].offset + (int64_t)max_det * images[a].img_h * (packed ? ym_cdiv(images[a].img_w, 64) : images[a].img_w);
-            const int64_t eb = images[b].offset + (int64_t)max_det * images[b].img_h * (packed ? ym_cdiv(images[b].img_w, 64) : images[b].img_w);
-            YM_REQUIRE(ea <= images[b].offset || eb <= images[a].offset, "%s: the mask blocks of images %d and %d overlap", what, a, b);
-        }
+    for (int b = 0; b < B; ++b)
+        if (fused_fits(Hp, Wp, images[b].img_h, images[b].img_w)) *fused |= 1u << b;
     return YM_OK;
 }
 

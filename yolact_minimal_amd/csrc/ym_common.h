@@ -34,6 +34,9 @@ static inline int ym_cdiv(int a, int b) { return (a + b - 1) / b; }
 // arguments, indexed by a uniform block index (masks.hip "Where a launch set's output sizes come from").
 struct YmRaggedTable { ym_ragged_image img[YM_RAGGED_MAX_IMAGES]; };
 
+// Elements per row of one instance mask: img_w floats, or (packed) ceil(img_w / 64) 64-bit words.
+__host__ __device__ inline size_t ym_mask_row(bool packed, int img_w) { return packed ? (size_t)((img_w + 63) >> 6) : (size_t)img_w; }
+
 // The checks every such table gets: 1..YM_RAGGED_MAX_IMAGES entries, positive sizes, every block at a multiple of
 // YM_RAGGED_ALIGN_BYTES bytes (`esz` = bytes per element of `offset`), no two blocks overlapping; `extent(entry)` = elements per block.
 template <class Extent>

@@ -123,6 +123,29 @@ class RaggedImage(ctypes.Structure):
 RAGGED_MAX_IMAGES = 32          # YM_RAGGED_MAX_IMAGES
 RAGGED_ALIGN_BYTES = 256        # YM_RAGGED_ALIGN_BYTES
 
+
+def ragged_table(sizes, offsets):
+    """The C-ABI table `(RaggedImage * B)` of the images `sizes` = [(h, w), ...] whose blocks start at `offsets`."""
+    return (RaggedImage * len(sizes))(*[RaggedImage(h, w, o) for (h, w), o in zip(sizes, offsets)])
+
+
+def aligned_layout(what, sizes, esz, extent):
+    """`(offsets, total)` in elements of `esz` bytes of ONE flat buffer for the images `sizes` = [(h, w), ...]: image b's block of
+    `extent(h, w)` elements starts at the first multiple of RAGGED_ALIGN_BYTES bytes behind block b - 1, `total` ends the last one.
+    The rule behind `frame_layout` and `ragged_layout` (`what` names the caller in errors).  Pure Python: no GPU, no library."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    if not 1 <= len(sizes) <= RAGGED_MAX_IMAGES:
+        raise RuntimeError(f'{what}: 1 .. {RAGGED_MAX_IMAGES} images per call, got {len(sizes)}')
+    step = RAGGED_ALIGN_BYTES // esz
+    offsets, end = [], 0
+    for h, w in sizes:
+        if h <= 0 or w <= 0:
+            raise RuntimeError(f'{what}: output size {h} x {w}')
+        at = -(-end // step) * step
+        offsets.append(at)
+        end = at + extent(h, w)
+    return offsets, end
+
 _lib = None
 
 

@@ -60,33 +60,38 @@ def _flags(cfg):
             (hip.DRAW_HIDE_SCORE if _flag(cfg, 'hide_score') else 0) | (hip.DRAW_REAL_TIME if _flag(cfg, 'real_time') else 0))
 
 
-def _launch(imgs, masks, ids, scores, boxes, counts, batch, max_det, cfg, flags, visual_thre, fps, out, cutout_total):
+def _launch(imgs, masks, ids, scores, boxes, counts, cfg, flags, visual_thre, fps, out, cutout_total=None, mask_table=None):
+    """The launch set behind `draw_img`, `cutout_mattes` and both arms of `draw_batch`, arguments checked by the caller.  `imgs` /
+    `out`: uint8 `[B, H, W, 3]` tensors with `masks` `[B, max_det, H, W]` (or a `PackedMasks`; the uniform entries, which also fill
+    `cutout_total`) -- or `FrameBatch`es with `masks` = view 0 of the checked list of per-image views and `mask_table` their table
+    (`ym_draw_detections_ragged[_packed]`).  `ids` is `[B, max_det]`, or `[max_det]` for one frame."""
+    from .frames import FrameBatch
     from .output_utils import _scratch
     device = imgs.device
-    _, h, w, _ = imgs.shape
+    batch, max_det = ids.shape if ids.dim() == 2 else (1, ids.shape[0])
     res = _resources(device, cfg)
     fps_text = None
     if flags & hip.DRAW_REAL_TIME:
         if fps is None:
             raise RuntimeError('draw_img: cfg.real_time needs the fps value')
         fps_text = f'fps: {fps:.2f}'.encode('ascii', 'replace')
+    # (PackedMasks: the mask term is read from the bit rows, one word serves 64 pixels of a detection; same output bytes)
+    if isinstance(imgs, FrameBatch):
+        name, frames, dst, where, cutout = 'ym_draw_detections_ragged', imgs.data, out.data, (imgs.table(), mask_table), ()
+    else:
+        name, frames, dst, where, cutout = 'ym_draw_detections_batch', imgs, out, imgs.shape[1:3], (hip.ptr(cutout_total, torch.uint8),)
     L = hip.lib()
     with torch.cuda.device(device):
         nbytes = L.ym_draw_workspace_bytes(batch, max_det)
         if nbytes == 0:
             raise RuntimeError('ym_draw_workspace_bytes: ' + L.ym_last_error().decode())
         ws = _scratch(device, nbytes)
-        # (PackedMasks: the mask term is read from the bit rows, one word serves 64 pixels of a detection; same output bytes)
-        packed = isinstance(masks, PackedMasks)
-        draw = L.ym_draw_detections_batch_packed if packed else L.ym_draw_detections_batch
-        hip.check(draw(
-            hip.ptr(imgs, torch.uint8), _mask_ptr(masks), hip.ptr(ids, torch.int64),
-            hip.ptr(scores) if scores is not None else None, hip.ptr(boxes, torch.int32),
-            hip.ptr(counts, torch.int32) if counts is not None else None, batch, max_det, h, w,
-            hip.ptr(res['palette'], torch.uint8), res['palette_n'], int(cfg.num_classes), hip.ptr(res['names'], torch.uint8),
-            res['num_names'], hip.ptr(res['font'], torch.int16), flags, float(visual_thre), fps_text,
-            hip.ptr(out, torch.uint8), hip.ptr(cutout_total, torch.uint8) if cutout_total is not None else None,
-            ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()), 'ym_draw_detections_batch')
+        hip.check(getattr(L, name + ('_packed' if isinstance(masks, PackedMasks) else ''))(
+            hip.ptr(frames, torch.uint8), _mask_ptr(masks), hip.ptr(ids, torch.int64), hip.ptr(scores), hip.ptr(boxes, torch.int32),
+            hip.ptr(counts, torch.int32), batch, max_det, *where, hip.ptr(res['palette'], torch.uint8), res['palette_n'],
+            int(cfg.num_classes), hip.ptr(res['names'], torch.uint8), res['num_names'], hip.ptr(res['font'], torch.int16), flags,
+            float(visual_thre), fps_text, hip.ptr(dst, torch.uint8), *cutout, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+            hip.stream_ptr()), name)
 
 
 def _mask_ptr(masks):
@@ -142,7 +147,7 @@ def draw_img(ids_p, class_p, box_p, mask_p, img_origin, cfg, img_name=None, fps=
     n, masks, ids, scores, boxes = _single_inputs(ids_p, class_p, box_p, mask_p, frame, not flags & hip.DRAW_HIDE_MASK,
                                                   not flags & hip.DRAW_HIDE_SCORE)
     out = torch.empty_like(frame)
-    _launch(frame, masks, ids, scores, boxes, None, 1, n, cfg, flags, 0.0, fps, out, None)
+    _launch(frame, masks, ids, scores, boxes, None, cfg, flags, 0.0, fps, out)
     return out[0].cpu().numpy() if from_numpy else out[0]
 
 
@@ -160,8 +165,7 @@ def cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg):
     n, masks, ids, _, boxes = _single_inputs(ids_p, None, box_p, mask_p, frame, True, False)
     _, h, w, _ = frame.shape
     total = torch.empty_like(frame)
-    _launch(frame, masks, ids, None, boxes, None, 1, n, cfg, hip.DRAW_HIDE_BBOX | hip.DRAW_HIDE_SCORE, 0.0, None,
-            torch.empty_like(frame), total)
+    _launch(frame, masks, ids, None, boxes, None, cfg, hip.DRAW_HIDE_BBOX | hip.DRAW_HIDE_SCORE, 0.0, None, torch.empty_like(frame), total)
     objs = []
     if n:
         full = torch.empty(n, h, w, 3, dtype=torch.uint8, device=device)
@@ -177,8 +181,8 @@ def cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg):
 
 
 def _ragged_mask_table(masks, sizes, max_det):
-    """The list of per-image mask views of the ragged `after_nms_batch` -> (view 0, packed, the `ym_after_nms_ragged` table rebuilt
-    from the views' data pointers relative to view 0).  Raises unless the views are `[max_det, h_b, w_b]` blocks of ONE allocation in
+    """The list of per-image mask views of the ragged `after_nms_batch` -> (view 0, the `ym_after_nms_ragged` table rebuilt from the
+    views' data pointers relative to view 0).  Raises unless the views are `[max_det, h_b, w_b]` blocks of ONE allocation in
     `ragged_layout` order."""
     from .output_utils import ragged_layout
     if not isinstance(masks, (list, tuple)) or len(masks) != len(sizes):
@@ -200,59 +204,22 @@ def _ragged_mask_table(masks, sizes, max_det):
     for b, t in enumerate(words):
         if t.device != words[0].device or t.data_ptr() - base != offsets[b] * esz:
             raise RuntimeError(f'draw_batch: the mask view of image {b} is not at its place in one ragged_layout allocation')
-    table = (hip.RaggedImage * len(sizes))(*[hip.RaggedImage(h, w, o) for (h, w), o in zip(sizes, offsets)])
-    return words[0], packed, table
+    return masks[0], hip.ragged_table(sizes, offsets)
 
 
-def _draw_batch_ragged(dets_padded, imgs, cfg, fps, out):
-    from .frames import FrameBatch
-    from .output_utils import _scratch
-    ids, scores, boxes, masks, counts = dets_padded
-    imgs.need_cuda('utils.draw.draw_batch')
-    if imgs.dtype != torch.uint8:
-        raise RuntimeError('draw_batch: the frames are uint8')
+def _batch_inputs(dets_padded, frames, frames_device):
+    """What both arms of `draw_batch` check of the detections -> (batch, max_det, ids, scores, boxes, counts), contiguous."""
+    ids, scores, boxes, _, counts = dets_padded
     for t in (ids, scores, boxes, counts):
         if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
             raise RuntimeError('yolact_minimal_amd.utils.draw.draw_batch needs the detections as CUDA (HIP) tensors, as after_nms_batch '
                                'returns them; there is no CPU path.')
-    device = _device_of(ids, 'draw_batch')
-    if ids.dim() != 2 or imgs.device != device:
+    if ids.dim() != 2 or frames_device != ids.device:
         raise RuntimeError('draw_batch: ids [B, max_det] on the device of the frames expected')
     batch, max_det = ids.shape
-    if len(imgs) != batch or max_det > hip.DRAW_MAX_DET:
-        raise RuntimeError(f'draw_batch: {len(imgs)} frames for {batch} detection sets of {max_det} rows (at most {hip.DRAW_MAX_DET})')
-    flags = _flags(cfg)
-    mask0, packed, mask_table = None, False, None
-    if not flags & hip.DRAW_HIDE_MASK and max_det:
-        mask0, packed, mask_table = _ragged_mask_table(masks, imgs.sizes, max_det)
-        if mask0.device != device:
-            raise RuntimeError(f'draw_batch: masks on {mask0.device}, detections on {device}')
-    if out is None:
-        out = FrameBatch.empty_like(imgs)
-    elif not isinstance(out, FrameBatch) or out.sizes != imgs.sizes or out.dtype != torch.uint8 or out.device != device:
-        raise RuntimeError('draw_batch: the destination is a uint8 FrameBatch of the same sizes on the same device')
-    fps_text = None
-    if flags & hip.DRAW_REAL_TIME:
-        if fps is None:
-            raise RuntimeError('draw_img: cfg.real_time needs the fps value')
-        fps_text = f'fps: {fps:.2f}'.encode('ascii', 'replace')
-    res = _resources(device, cfg)
-    L = hip.lib()
-    with torch.cuda.device(device):
-        nbytes = L.ym_draw_workspace_bytes(batch, max_det)
-        if nbytes == 0:
-            raise RuntimeError('ym_draw_workspace_bytes: ' + L.ym_last_error().decode())
-        ws = _scratch(device, nbytes)
-        draw = L.ym_draw_detections_ragged_packed if packed else L.ym_draw_detections_ragged
-        hip.check(draw(
-            hip.ptr(imgs.data, torch.uint8), hip.ptr(mask0, mask0.dtype) if mask0 is not None else None,
-            hip.ptr(ids.contiguous(), torch.int64), hip.ptr(scores.contiguous()) if scores is not None else None,
-            hip.ptr(boxes.contiguous(), torch.int32), hip.ptr(counts.contiguous(), torch.int32) if counts is not None else None,
-            batch, max_det, imgs.table(), mask_table, hip.ptr(res['palette'], torch.uint8), res['palette_n'], int(cfg.num_classes),
-            hip.ptr(res['names'], torch.uint8), res['num_names'], hip.ptr(res['font'], torch.int16), flags,
-            float(getattr(cfg, 'visual_thre', 0) or 0), fps_text, hip.ptr(out.data, torch.uint8),
-            ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()), 'ym_draw_detections_ragged')
-    return out
+    if frames != batch or max_det > hip.DRAW_MAX_DET:
+        raise RuntimeError(f'draw_batch: {frames} frames for {batch} detection sets of {max_det} rows (at most {hip.DRAW_MAX_DET})')
+    return (batch, max_det) + tuple(t.contiguous() if t is not None else None for t in (ids, scores, boxes, counts))
 
 
 def draw_batch(dets_padded, imgs, cfg, fps=None, _out=None):
@@ -266,25 +233,34 @@ def draw_batch(dets_padded, imgs, cfg, fps=None, _out=None):
     new `FrameBatch` of the same sizes (`ym_draw_detections_ragged`: one prep launch and at most two frame launches for the batch).
     (`_out`: the destination `FrameBatch`, for the tests' guard bytes; `_out is imgs` draws in place.)"""
     from .frames import FrameBatch
-    if isinstance(imgs, FrameBatch):
-        return _draw_batch_ragged(dets_padded, imgs, cfg, fps, _out)
-    if _out is not None:
-        raise RuntimeError('draw_batch: a destination is taken with a FrameBatch only')
-    ids, scores, boxes, masks, counts = dets_padded
-    device = _device_of(ids, 'draw_batch')
-    if not torch.is_tensor(imgs) or not imgs.is_cuda or imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3 or \
-            imgs.device != device:
-        raise RuntimeError('draw_batch: imgs is a uint8 [B, H, W, 3] tensor on the device of the detections')
-    batch, max_det = ids.shape
-    _, h, w, _ = imgs.shape
-    if imgs.shape[0] != batch or max_det > hip.DRAW_MAX_DET:
-        raise RuntimeError(f'draw_batch: {imgs.shape[0]} frames for {batch} detection sets of {max_det} rows (at most {hip.DRAW_MAX_DET})')
     flags = _flags(cfg)
-    need_masks = not flags & hip.DRAW_HIDE_MASK
-    if need_masks and tuple(masks.shape) != (batch, max_det, h, w):
-        raise RuntimeError(f'draw_batch: masks {tuple(masks.shape)} do not fit [{batch}, {max_det}, {h}, {w}]')
-    out = torch.empty_like(imgs, memory_format=torch.contiguous_format)
-    _launch(imgs.contiguous(), masks.contiguous() if need_masks else None, ids.contiguous(), scores.contiguous(), boxes.contiguous(),
-            counts.contiguous() if counts is not None else None, batch, max_det, cfg, flags,
-            float(getattr(cfg, 'visual_thre', 0) or 0), fps, out, None)
+    masks, mask_table = (None if flags & hip.DRAW_HIDE_MASK else dets_padded[3]), None
+    if isinstance(imgs, FrameBatch):
+        imgs.need_cuda('utils.draw.draw_batch')
+        if imgs.dtype != torch.uint8:
+            raise RuntimeError('draw_batch: the frames are uint8')
+        batch, max_det, *dets = _batch_inputs(dets_padded, len(imgs), imgs.device)
+        if masks is not None and max_det:
+            masks, mask_table = _ragged_mask_table(masks, imgs.sizes, max_det)
+            if masks.device != imgs.device:
+                raise RuntimeError(f'draw_batch: masks on {masks.device}, detections on {imgs.device}')
+        else:
+            masks = None
+        out = FrameBatch.empty_like(imgs) if _out is None else _out
+        if not isinstance(out, FrameBatch) or out.sizes != imgs.sizes or out.dtype != torch.uint8 or out.device != imgs.device:
+            raise RuntimeError('draw_batch: the destination is a uint8 FrameBatch of the same sizes on the same device')
+    else:
+        if _out is not None:
+            raise RuntimeError('draw_batch: a destination is taken with a FrameBatch only')
+        if not torch.is_tensor(imgs) or not imgs.is_cuda or imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3:
+            raise RuntimeError('draw_batch: imgs is a uint8 [B, H, W, 3] tensor on the device of the detections')
+        batch, max_det, *dets = _batch_inputs(dets_padded, imgs.shape[0], imgs.device)
+        _, h, w, _ = imgs.shape
+        if masks is not None:
+            if tuple(masks.shape) != (batch, max_det, h, w):
+                raise RuntimeError(f'draw_batch: masks {tuple(masks.shape)} do not fit [{batch}, {max_det}, {h}, {w}]')
+            masks = masks.contiguous()
+        imgs = imgs.contiguous()
+        out = torch.empty_like(imgs)
+    _launch(imgs, masks, *dets, cfg, flags, float(getattr(cfg, 'visual_thre', 0) or 0), fps, out, mask_table=mask_table)
     return out

@@ -14,21 +14,10 @@ def frame_layout(sizes, itemsize=1):
     """`(offsets, total)` in ELEMENTS (bytes for uint8 frames, `itemsize=4`: floats) of one flat buffer that holds the frames
     `[h_b, w_b, 3]` of `sizes` = [(h, w), ...]: every frame starts at a multiple of 256 bytes, `total` ends the last one.
     Pure Python: no GPU, no library."""
-    sizes = [(int(h), int(w)) for h, w in sizes]
     itemsize = int(itemsize)
-    if not 1 <= len(sizes) <= hip.RAGGED_MAX_IMAGES:
-        raise RuntimeError(f'frame_layout: 1 .. {hip.RAGGED_MAX_IMAGES} images per call, got {len(sizes)}')
     if itemsize < 1 or hip.RAGGED_ALIGN_BYTES % itemsize:
         raise RuntimeError(f'frame_layout: itemsize = {itemsize}')
-    step = hip.RAGGED_ALIGN_BYTES // itemsize
-    offsets, end = [], 0
-    for h, w in sizes:
-        if h <= 0 or w <= 0:
-            raise RuntimeError(f'frame_layout: output size {h} x {w}')
-        at = -(-end // step) * step
-        offsets.append(at)
-        end = at + h * w * 3
-    return offsets, end
+    return hip.aligned_layout('frame_layout', sizes, itemsize, lambda h, w: h * w * 3)
 
 
 def _frame_size(t, what, dtypes):
@@ -127,7 +116,7 @@ class FrameBatch:
     def table(self):
         """The C-ABI table `(hip.RaggedImage * B)` of this batch (built once)."""
         if self._table is None:
-            self._table = (hip.RaggedImage * len(self.sizes))(*[hip.RaggedImage(h, w, o) for (h, w), o in zip(self.sizes, self.offsets)])
+            self._table = hip.ragged_table(self.sizes, self.offsets)
         return self._table
 
     def numpy(self):

@@ -146,7 +146,7 @@ def _after_nms_launch(proto, coefs, boxes, counts, sizes, do_crop, packed):
         plan = _ragged_plans.get(key)
         if plan is None:
             offsets, total = ragged_layout(sizes, md, packed)
-            table = (hip.RaggedImage * batch)(*[hip.RaggedImage(h, w, o) for (h, w), o in zip(sizes, offsets)])
+            table = hip.ragged_table(sizes, offsets)
             if len(_ragged_plans) >= 1024:
                 _ragged_plans.clear()
             plan = _ragged_plans[key] = (offsets, total, table, L.ym_after_nms_ragged_workspace_bytes(table, batch, md, hp, wp))
@@ -264,21 +264,10 @@ def ragged_layout(sizes, max_det, packed=False):
     `[max_det, h_b, ceil(w_b / 64)]` words) at `offsets[b]`; every block starts at a multiple of 256 bytes (the dense kernel stores 16
     bytes at a time, and an odd `max_det` x odd height x odd width would leave the next block misaligned); `total` ends the last
     block.  Pure Python: no GPU, no library."""
-    sizes = [(int(h), int(w)) for h, w in sizes]
     max_det = int(max_det)
-    if not 1 <= len(sizes) <= hip.RAGGED_MAX_IMAGES:
-        raise RuntimeError(f'ragged_layout: 1 .. {hip.RAGGED_MAX_IMAGES} images per call, got {len(sizes)}')
     if max_det < 1:
         raise RuntimeError(f'ragged_layout: max_det = {max_det}')
-    step = hip.RAGGED_ALIGN_BYTES // (8 if packed else 4)
-    offsets, end = [], 0
-    for h, w in sizes:
-        if h <= 0 or w <= 0:
-            raise RuntimeError(f'ragged_layout: output size {h} x {w}')
-        at = -(-end // step) * step
-        offsets.append(at)
-        end = at + max_det * h * ((w + 63) // 64 if packed else w)
-    return offsets, end
+    return hip.aligned_layout('ragged_layout', sizes, 8 if packed else 4, lambda h, w: max_det * h * ((w + 63) // 64 if packed else w))
 
 
 def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
