@@ -59,8 +59,10 @@ __global__ void k_fold_bn(const float* gamma, const float* beta, const float* me
     }
 }
 
-// idx (optional, training): per output element the window position 3*dy + dx of the element that won under ATen's rule
-// (a later value replaces the running maximum if it is larger or NaN), which is what max_pool2d's backward routes the gradient to.
+// idx (optional, training): per output element the window position 3*dy + dx of the element that won under ATen's rule, which is
+// what max_pool2d's backward routes the gradient to: the running maximum starts as -inf AT the first valid element of the window
+// (never at a padding position: a window whose valid elements are all -inf names that first element), and a later value replaces
+// it if it is larger or NaN (so the LAST NaN of a window wins).
 __global__ void k_maxpool3x3s2(const float* __restrict__ in, float* __restrict__ out, int B, int H, int W, int C4,
                                int Ho, int Wo, uint8_t* __restrict__ idx = nullptr) {
     const size_t total = (size_t)B * Ho * Wo * C4;
@@ -71,7 +73,8 @@ __global__ void k_maxpool3x3s2(const float* __restrict__ in, float* __restrict__
         const int oh = (int)(t % Ho);
         const int b = (int)(t / Ho);
         f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        uint32_t arg = 0;                                         // four position bytes
+        // four position bytes, each the first valid position: row 1 / column 1 of the window where row 0 / column 0 is padding
+        uint32_t arg = (uint32_t)((oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0)) * 0x01010101u;
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int ih = oh * 2 - 1 + dy;

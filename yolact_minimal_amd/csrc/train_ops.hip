@@ -399,7 +399,8 @@ __global__ void k_f64_to_f32(const double* in, float* out, int n) {
 }
 
 // MaxPool2d(3,2,1) backward: every input pixel gathers from the (at most 4) windows that contain it and takes the
-// gradient of those whose FIRST maximum (scan order kh, kw — ATen's tie rule) is this pixel.
+// gradient of those it wins under ATen's rule, the one k_maxpool3x3s2 records in its argmax bytes: the FIRST maximum in scan
+// order (kh, kw) among equal values (so the first valid element of a window of -inf), and the LAST NaN of a window that holds any.
 __global__ __launch_bounds__(256) void k_maxpool_bwd(const float* __restrict__ x, const float* __restrict__ dy,
                                                       float* __restrict__ dx, int B, int H, int W, int C4, int Ho, int Wo) {
     const size_t total = (size_t)B * H * W * C4;
@@ -429,8 +430,10 @@ __global__ __launch_bounds__(256) void k_maxpool_bwd(const float* __restrict__ x
                         const bool before = (y2 < ih) || (y2 == ih && x2 < iw);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            // another element wins if it is larger, or equal and earlier in scan order (NaN: ATen keeps NaN max)
-                            if (o[e] > xv[e] || (o[e] == xv[e] && before) || (o[e] != o[e] && !(xv[e] != xv[e]))) first[e] = false;
+                            // another element wins if it is larger, or equal and earlier in scan order, or NaN where this one is
+                            // not, or a NaN later in scan order than this NaN (ATen: every NaN replaces the running maximum)
+                            const bool onan = o[e] != o[e], xnan = xv[e] != xv[e];
+                            if (o[e] > xv[e] || (o[e] == xv[e] && before) || (onan && (!xnan || !before))) first[e] = false;
                         }
                     }
                 }
@@ -444,7 +447,8 @@ __global__ __launch_bounds__(256) void k_maxpool_bwd(const float* __restrict__ x
 }
 
 // The same gather with the argmax positions saved by the forward (ym_maxpool3x3s2_fwd_idx): per input pixel at most 4 index
-// words and 4 gradient vectors instead of re-scanning up to 4 windows of 9 (32 vector loads).
+// words and 4 gradient vectors instead of re-scanning up to 4 windows of 9 (32 vector loads).  Same rule, same dx as the re-scan,
+// -inf windows and NaNs included: the saved position is always a valid element of its window.
 __global__ __launch_bounds__(256) void k_maxpool_bwd_idx(const uint8_t* __restrict__ idx, const float* __restrict__ dy,
                                                           float* __restrict__ dx, int B, int H, int W, int C4, int Ho, int Wo) {
     const size_t total = (size_t)B * H * W * C4;
