@@ -215,6 +215,32 @@ int ym_train_aug_image(const void* img_hwc_bgr, int is_u8, const ym_aug_plan* pl
  * there: utils/augmentations.py:138-141,180-181): a {0,1} mask comes out {0,1}. */
 int ym_train_aug_masks(const void* masks, int is_u8, const int32_t* keep, int k, const ym_aug_plan* plan, float* out,
                        ym_stream_t s);
+/* The two entries above for a whole training batch: the samples are images of DIFFERENT sizes, the output one [B][3][S][S] tensor.
+ *   `items` is a HOST table of B <= YM_AUG_MAX_SAMPLES samples.  It is read during the call and travels to the kernels by value in
+ * their arguments, 16 samples per launch (B = 17 .. 32: two launches per entry): no copy to the device, no synchronisation, nothing
+ * to keep alive afterwards.  Sample b: its plan (plan.S == S), its image `img` (HWC BGR [plan.H][plan.W][3] on the device; the
+ * images need not share an allocation), its instance masks `masks` ([n_masks][plan.H][plan.W]; may be NULL when k == 0) and its
+ * k surviving instances, which are rows [row0, row0 + k) of `keep_dev` (device int32, indices into ITS masks) and of the mask
+ * output; row0 is the sum of the earlier samples' k, total_k the sum of all.  is_u8 is the dtype of every image (image entry) /
+ * every mask (mask entry); the 8-bit resize of an already-square crop is chosen per sample (is_u8 && plan.cw == plan.ch).
+ *   ym_train_aug_image_batch: grid = ceil(S * S / 256) x samples, out [B][3][S][S].  ym_train_aug_masks_batch: grid =
+ * ceil(S * S / 256) x mask rows, out [total_k][S][S]; total_k == 0 is a no-op; a keep index outside 0 .. n_masks - 1 reads nothing
+ * and gives a zero row.  ym_train_aug_image / ym_train_aug_masks are the one-sample instances of the same two kernels (keep as
+ * keep_dev, row0 = 0), so a row of a batch equals the single call bit for bit.  YM_EINVAL before any launch: B outside
+ * 1 .. YM_AUG_MAX_SAMPLES, a null table / image / output pointer, plan.S != S, an invalid plan, k < 0, k > 0 with null masks or
+ * n_masks <= 0, row0 or total_k off the running sum, total_k > 0 with a null keep_dev or output. */
+#define YM_AUG_MAX_SAMPLES 32            /* = YM_RAGGED_MAX_IMAGES: the images arrive as one frame batch */
+typedef struct ym_aug_item {
+    ym_aug_plan plan;
+    int32_t n_masks;
+    const void* img;
+    const void* masks;
+    int32_t k, row0;
+} ym_aug_item;
+size_t ym_sizeof_aug_item(void);                       /* for bindings: must equal their mirror of ym_aug_item */
+int ym_train_aug_image_batch(const ym_aug_item* items, int B, int S, int is_u8, float* out, ym_stream_t s);
+int ym_train_aug_masks_batch(const ym_aug_item* items, int B, int S, int is_u8, const int32_t* keep_dev, int total_k, float* out,
+                             ym_stream_t s);
 
 /* ---- evaluation inner products right after after_nms (next row f2) -----------------------------------------------
  * mask_iou (utils/box_utils.py:189-200): masks_a [n][P], masks_b [g][P] fp32 in {0,1} (P = img_h*img_w < 2^24) ->

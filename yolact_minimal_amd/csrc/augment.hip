@@ -4,6 +4,7 @@
 // that chain backwards to its (up to) four source texels, applies the photometric distortion to those texels only, blends them
 // with ATen / OpenCV half-pixel bilinear weights and writes the normalised RGB planes.  The random decisions arrive as a plan
 // (ym_aug_plan) drawn on the host in the reference's `random` call order.  HBM-bound: source image read ~once, output written once.
+#include <algorithm>
 #include "ym_common.h"
 
 namespace {
@@ -79,42 +80,53 @@ __device__ __forceinline__ bool to_source(const ym_aug_plan& p, int sy, int sx, 
     return true;
 }
 
+// Per-sample arguments of one launch: the caller's HOST table of ym_aug_item, ALB entries at a time BY VALUE in the kernel arguments
+// (no device copy, no synchronisation, nothing to keep alive), read through the uniform blockIdx.y only -- scalar loads, never a
+// private copy.  ym_train_aug_image / ym_train_aug_masks are the ONE-item instances of the batch kernels below, so a row of a batch
+// and the same sample alone run the same instructions and agree bit for bit (as ym_val_preprocess / ym_val_preprocess_batch do).
+constexpr int ALB = 16;
+struct AugTable { ym_aug_item it[ALB]; };
+
+// grid = (ceil(S * S / 256), samples of this launch); `out` is the first of those samples' [3][S][S] rows
 template <typename T>
-__global__ __launch_bounds__(256) void k_train_aug_image(const T* __restrict__ img, const ym_aug_plan p, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_train_aug_image(const AugTable tab, float* __restrict__ out) {
+    const ym_aug_plan& p = tab.it[blockIdx.y].plan;
+    const T* __restrict__ img = (const T*)tab.it[blockIdx.y].img;
     const int S = p.S;
     const long long total = (long long)S * S;
     const float scale = (float)p.q / (float)p.r;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int y = (int)(e / S), x = (int)(e - (long long)y * S);
-        float vb = p.mean[0], vg = p.mean[1], vr = p.mean[2];
-        int ry, rx;
-        if (to_resized(p, y, x, ry, rx)) {
-            int y0, y1, x0, x1;
-            float ly, lx;
-            src_index(scale, ry, p.q, y0, y1, ly);
-            src_index(scale, rx, p.q, x0, x1, lx);
-            Texel t[2][2];
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    out += (size_t)blockIdx.y * 3 * total;
+    const int y = (int)(e / S), x = (int)(e - (long long)y * S);
+    float vb = p.mean[0], vg = p.mean[1], vr = p.mean[2];
+    int ry, rx;
+    if (to_resized(p, y, x, ry, rx)) {
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_index(scale, ry, p.q, y0, y1, ly);
+        src_index(scale, rx, p.q, x0, x1, lx);
+        Texel t[2][2];
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+        for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    int Y, X;
-                    if (to_source(p, a ? y1 : y0, b ? x1 : x0, Y, X)) {
-                        const T* s = img + ((size_t)Y * p.W + X) * 3;
-                        t[a][b] = photometric(Texel{(float)s[0], (float)s[1], (float)s[2]}, p);
-                    } else {
-                        t[a][b] = Texel{p.mean[0], p.mean[1], p.mean[2]};
-                    }
+            for (int b = 0; b < 2; ++b) {
+                int Y, X;
+                if (to_source(p, a ? y1 : y0, b ? x1 : x0, Y, X)) {
+                    const T* s = img + ((size_t)Y * p.W + X) * 3;
+                    t[a][b] = photometric(Texel{(float)s[0], (float)s[1], (float)s[2]}, p);
+                } else {
+                    t[a][b] = Texel{p.mean[0], p.mean[1], p.mean[2]};
                 }
-            const float hy = 1.f - ly, hx = 1.f - lx;
-            vb = hy * (hx * t[0][0].b + lx * t[0][1].b) + ly * (hx * t[1][0].b + lx * t[1][1].b);
-            vg = hy * (hx * t[0][0].g + lx * t[0][1].g) + ly * (hx * t[1][0].g + lx * t[1][1].g);
-            vr = hy * (hx * t[0][0].r + lx * t[0][1].r) + ly * (hx * t[1][0].r + lx * t[1][1].r);
-        }
-        out[e] = (vr - p.mean[2]) / p.std[2];                    // RGB planes (normalize_and_toRGB :212-216)
-        out[total + e] = (vg - p.mean[1]) / p.std[1];
-        out[2 * total + e] = (vb - p.mean[0]) / p.std[0];
+            }
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        vb = hy * (hx * t[0][0].b + lx * t[0][1].b) + ly * (hx * t[1][0].b + lx * t[1][1].b);
+        vg = hy * (hx * t[0][0].g + lx * t[0][1].g) + ly * (hx * t[1][0].g + lx * t[1][1].g);
+        vr = hy * (hx * t[0][0].r + lx * t[0][1].r) + ly * (hx * t[1][0].r + lx * t[1][1].r);
     }
+    out[e] = (vr - p.mean[2]) / p.std[2];                    // RGB planes (normalize_and_toRGB :212-216)
+    out[total + e] = (vg - p.mean[1]) / p.std[1];
+    out[2 * total + e] = (vb - p.mean[0]) / p.std[0];
 }
 
 // cv2.resize on uint8 (INTER_LINEAR) is fixed point: taps of one axis as OpenCV computes them (imgproc/resize.cpp) — source index
@@ -140,50 +152,59 @@ __device__ __forceinline__ void u8_taps(int n_src, int n_dst, int d, bool clamp_
 // `fixed`: uint8 masks of an already-square crop — the reference resizes them as uint8 (pad_to_square :138-141 returns them
 // untouched, multi_scale_resize :180-181), i.e. through OpenCV's 8-bit fixed-point path, and a {0,1} mask stays {0,1}
 // (oracle/augment_ref.py resize_bilinear_u8); every other sample's masks went through the float32 pad buffer first.
+// grid = (ceil(S * S / 256), mask rows of this launch): workgroup row blockIdx.y is row `row_begin + blockIdx.y` of `keep` and of `out`;
+// its sample is the last of the launch's `nb` table entries that starts at or before it (an entry with k == 0 shares its row0 with
+// the next one).  A `keep` index outside the sample's n_masks reads nothing: the row comes out zero.
 template <typename T>
-__global__ __launch_bounds__(256) void k_train_aug_masks(const T* __restrict__ masks, const int32_t* __restrict__ keep, int k,
-                                                         const ym_aug_plan p, float* __restrict__ out, int fixed) {
+__global__ __launch_bounds__(256) void k_train_aug_masks(const AugTable tab, int nb, int row_begin, const int32_t* __restrict__ keep,
+                                                         float* __restrict__ out) {
+    const int row = row_begin + (int)blockIdx.y;
+    int b = 0;
+    for (int i = 1; i < nb; ++i)
+        if (tab.it[i].row0 <= row) b = i;
+    const ym_aug_plan& p = tab.it[b].plan;
+    const int kj = keep[row];
+    const bool fixed = sizeof(T) == 1 && p.cw == p.ch;
     const int S = p.S;
-    const long long plane = (long long)S * S, total = plane * k;
+    const long long plane = (long long)S * S;
     const float scale = (float)p.q / (float)p.r;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int j = (int)(e / plane);
-        const long long rem = e - (long long)j * plane;
-        const int y = (int)(rem / S), x = (int)(rem - (long long)y * S);
-        const T* m = masks + (size_t)keep[j] * p.H * p.W;
-        float v = 0.f;
-        int ry, rx;
-        if (fixed && to_resized(p, y, x, ry, rx)) {
-            int y0, y1, x0, x1, a0, a1, b0, b1;
-            u8_taps(p.q, p.r, rx, true, x0, x1, a0, a1);
-            u8_taps(p.q, p.r, ry, false, y0, y1, b0, b1);
-            int t[2][2];
+    const long long rem = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (rem >= plane) return;
+    const int y = (int)(rem / S), x = (int)(rem - (long long)y * S);
+    const T* __restrict__ m = (const T*)tab.it[b].masks + (size_t)kj * p.H * p.W;
+    float v = 0.f;
+    int ry, rx;
+    if (kj < 0 || kj >= tab.it[b].n_masks) {
+    } else if (fixed && to_resized(p, y, x, ry, rx)) {
+        int y0, y1, x0, x1, a0, a1, b0, b1;
+        u8_taps(p.q, p.r, rx, true, x0, x1, a0, a1);
+        u8_taps(p.q, p.r, ry, false, y0, y1, b0, b1);
+        int t[2][2];
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+        for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    int Y, X;
-                    t[a][b] = to_source(p, a ? y1 : y0, b ? x1 : x0, Y, X) ? (int)m[(size_t)Y * p.W + X] : 0;
-                }
-            const int h0 = t[0][0] * a0 + t[0][1] * a1, h1 = t[1][0] * a0 + t[1][1] * a1;          // horizontal pass, scale 2048
-            v = (float)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
-        } else if (to_resized(p, y, x, ry, rx)) {
-            int y0, y1, x0, x1;
-            float ly, lx;
-            src_index(scale, ry, p.q, y0, y1, ly);
-            src_index(scale, rx, p.q, x0, x1, lx);
-            float t[2][2];
+            for (int c = 0; c < 2; ++c) {
+                int Y, X;
+                t[a][c] = to_source(p, a ? y1 : y0, c ? x1 : x0, Y, X) ? (int)m[(size_t)Y * p.W + X] : 0;
+            }
+        const int h0 = t[0][0] * a0 + t[0][1] * a1, h1 = t[1][0] * a0 + t[1][1] * a1;          // horizontal pass, scale 2048
+        v = (float)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+    } else if (to_resized(p, y, x, ry, rx)) {
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_index(scale, ry, p.q, y0, y1, ly);
+        src_index(scale, rx, p.q, x0, x1, lx);
+        float t[2][2];
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+        for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    int Y, X;
-                    t[a][b] = to_source(p, a ? y1 : y0, b ? x1 : x0, Y, X) ? (float)m[(size_t)Y * p.W + X] : 0.f;
-                }
-            v = (1.f - ly) * ((1.f - lx) * t[0][0] + lx * t[0][1]) + ly * ((1.f - lx) * t[1][0] + lx * t[1][1]);
-        }
-        out[e] = v;
+            for (int c = 0; c < 2; ++c) {
+                int Y, X;
+                t[a][c] = to_source(p, a ? y1 : y0, c ? x1 : x0, Y, X) ? (float)m[(size_t)Y * p.W + X] : 0.f;
+            }
+        v = (1.f - ly) * ((1.f - lx) * t[0][0] + lx * t[0][1]) + ly * ((1.f - lx) * t[1][0] + lx * t[1][1]);
     }
+    out[(size_t)row * plane + rem] = v;
 }
 
 int check_plan(const ym_aug_plan* p) {
@@ -199,21 +220,68 @@ int check_plan(const ym_aug_plan* p) {
     return YM_OK;
 }
 
-int grid_for(long long n) {
-    long long g = (n + 255) / 256;
-    return (int)(g > 8192 ? 8192 : g);
+// One launch per ALB samples, the grid (ceil(S * S / 256), samples); `what` names the entry in a launch error.
+int launch_image(const char* what, const ym_aug_item* items, int B, int S, int is_u8, float* out, ym_stream_t s) {
+    const long long plane = (long long)S * S;
+    const unsigned gx = (unsigned)((plane + 255) / 256);
+    for (int b0 = 0; b0 < B; b0 += ALB) {
+        const int nb = B - b0 < ALB ? B - b0 : ALB;
+        AugTable tab = {};
+        std::copy(items + b0, items + b0 + nb, tab.it);
+        float* o = out + (size_t)b0 * 3 * plane;
+        if (is_u8) hipLaunchKernelGGL(k_train_aug_image<uint8_t>, dim3(gx, nb), dim3(256), 0, (hipStream_t)s, tab, o);
+        else hipLaunchKernelGGL(k_train_aug_image<float>, dim3(gx, nb), dim3(256), 0, (hipStream_t)s, tab, o);
+    }
+    return ym_check_launch(what);
+}
+
+// One launch per ALB samples that have rows (more only where their rows exceed grid.y's 65535), the grid (ceil(S * S / 256), rows).
+// `items[b].row0` is the running sum of the earlier k (checked by the callers).
+int launch_masks(const char* what, const ym_aug_item* items, int B, int S, int is_u8, const int32_t* keep, float* out, ym_stream_t s) {
+    const long long plane = (long long)S * S;
+    const unsigned gx = (unsigned)((plane + 255) / 256);
+    for (int b0 = 0; b0 < B; b0 += ALB) {
+        const int nb = B - b0 < ALB ? B - b0 : ALB;
+        AugTable tab = {};
+        std::copy(items + b0, items + b0 + nb, tab.it);
+        const int lo = items[b0].row0, hi = items[b0 + nb - 1].row0 + items[b0 + nb - 1].k;
+        for (int r = lo; r < hi; r += 65535) {
+            const int ny = hi - r < 65535 ? hi - r : 65535;
+            if (is_u8) hipLaunchKernelGGL(k_train_aug_masks<uint8_t>, dim3(gx, ny), dim3(256), 0, (hipStream_t)s, tab, nb, r, keep, out);
+            else hipLaunchKernelGGL(k_train_aug_masks<float>, dim3(gx, ny), dim3(256), 0, (hipStream_t)s, tab, nb, r, keep, out);
+        }
+    }
+    return ym_check_launch(what);
+}
+
+// The checks the two batch entries share: 1 .. YM_AUG_MAX_SAMPLES items, every plan valid and of the call's S.
+int check_items(const char* what, const ym_aug_item* items, int B, int S) {
+    YM_REQUIRE(items, "%s: null item table", what);
+    YM_REQUIRE(B >= 1 && B <= YM_AUG_MAX_SAMPLES, "%s: 1 .. %d samples per call, got %d", what, YM_AUG_MAX_SAMPLES, B);
+    for (int b = 0; b < B; ++b) {
+        YM_REQUIRE(items[b].plan.S == S, "%s: sample %d: plan.S = %d, the call's S = %d", what, b, items[b].plan.S, S);
+        if (check_plan(&items[b].plan) != YM_OK) {
+            char why[160];
+            snprintf(why, sizeof(why), "%s", ym_last_error());
+            ym_set_error("%s: sample %d: %s", what, b, why);
+            return YM_EINVAL;
+        }
+    }
+    return YM_OK;
 }
 
 }  // namespace
+
+extern "C" size_t ym_sizeof_aug_item(void) { return sizeof(ym_aug_item); }
 
 extern "C" int ym_train_aug_image(const void* img_hwc_bgr, int is_u8, const ym_aug_plan* plan, float* out_chw, ym_stream_t s) {
     int rc = check_plan(plan);
     if (rc != YM_OK) return rc;
     YM_REQUIRE(img_hwc_bgr && out_chw, "train_aug_image: null pointer");
-    const int g = grid_for((long long)plan->S * plan->S);
-    if (is_u8) hipLaunchKernelGGL(k_train_aug_image<uint8_t>, dim3(g), dim3(256), 0, (hipStream_t)s, (const uint8_t*)img_hwc_bgr, *plan, out_chw);
-    else hipLaunchKernelGGL(k_train_aug_image<float>, dim3(g), dim3(256), 0, (hipStream_t)s, (const float*)img_hwc_bgr, *plan, out_chw);
-    return ym_check_launch("train_aug_image");
+    ym_aug_item it = {};
+    it.plan = *plan;
+    it.img = img_hwc_bgr;
+    return launch_image("train_aug_image", &it, 1, plan->S, is_u8, out_chw, s);
 }
 
 extern "C" int ym_train_aug_masks(const void* masks, int is_u8, const int32_t* keep, int k, const ym_aug_plan* plan, float* out,
@@ -223,9 +291,40 @@ extern "C" int ym_train_aug_masks(const void* masks, int is_u8, const int32_t* k
     YM_REQUIRE(k >= 0, "train_aug_masks: k < 0");
     if (k == 0) return YM_OK;
     YM_REQUIRE(masks && keep && out, "train_aug_masks: null pointer");
-    const int g = grid_for((long long)plan->S * plan->S * k);
-    const int fixed = (is_u8 && plan->cw == plan->ch) ? 1 : 0;          // already-square sample: the reference's masks stay uint8
-    if (is_u8) hipLaunchKernelGGL(k_train_aug_masks<uint8_t>, dim3(g), dim3(256), 0, (hipStream_t)s, (const uint8_t*)masks, keep, k, *plan, out, fixed);
-    else hipLaunchKernelGGL(k_train_aug_masks<float>, dim3(g), dim3(256), 0, (hipStream_t)s, (const float*)masks, keep, k, *plan, out, 0);
-    return ym_check_launch("train_aug_masks");
+    ym_aug_item it = {};
+    it.plan = *plan;
+    it.masks = masks;
+    it.n_masks = INT32_MAX;                      // (this entry is not told how many instances `masks` holds)
+    it.k = k;
+    return launch_masks("train_aug_masks", &it, 1, plan->S, is_u8, keep, out, s);
+}
+
+extern "C" int ym_train_aug_image_batch(const ym_aug_item* items, int B, int S, int is_u8, float* out, ym_stream_t s) {
+    const char* what = "train_aug_image_batch";
+    int rc = check_items(what, items, B, S);
+    if (rc != YM_OK) return rc;
+    YM_REQUIRE(out, "%s: null output pointer", what);
+    for (int b = 0; b < B; ++b) YM_REQUIRE(items[b].img, "%s: sample %d: null image pointer", what, b);
+    return launch_image(what, items, B, S, is_u8, out, s);
+}
+
+extern "C" int ym_train_aug_masks_batch(const ym_aug_item* items, int B, int S, int is_u8, const int32_t* keep_dev, int total_k,
+                                        float* out, ym_stream_t s) {
+    const char* what = "train_aug_masks_batch";
+    int rc = check_items(what, items, B, S);
+    if (rc != YM_OK) return rc;
+    long long rows = 0;
+    for (int b = 0; b < B; ++b) {
+        const ym_aug_item& it = items[b];
+        YM_REQUIRE(it.k >= 0, "%s: sample %d: k = %d < 0", what, b, it.k);
+        YM_REQUIRE(it.k == 0 || (it.masks && it.n_masks > 0), "%s: sample %d: k = %d with %s", what, b, it.k,
+                   it.masks ? "n_masks <= 0" : "a null masks pointer");
+        YM_REQUIRE(it.row0 == rows, "%s: sample %d: row0 = %d, the earlier samples hold %lld rows", what, b, it.row0, rows);
+        rows += it.k;
+        YM_REQUIRE(rows <= INT32_MAX, "%s: more than 2^31 - 1 mask rows", what);
+    }
+    YM_REQUIRE(rows == total_k, "%s: the samples hold %lld rows, total_k = %d", what, rows, total_k);
+    if (total_k == 0) return YM_OK;
+    YM_REQUIRE(keep_dev && out, "%s: total_k = %d with a null keep or output pointer", what, total_k);
+    return launch_masks(what, items, B, S, is_u8, keep_dev, out, s);
 }

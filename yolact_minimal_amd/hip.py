@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     'ym_coco_iou_box', 'ym_coco_iou_mask_packed', 'ym_coco_match_log', 'ym_coco_accumulate_workspace_bytes', 'ym_coco_accumulate',
     'ym_after_nms_ragged_workspace_bytes', 'ym_after_nms_ragged', 'ym_after_nms_ragged_packed',
     'ym_val_preprocess_batch', 'ym_draw_detections_ragged', 'ym_draw_detections_ragged_packed',
+    'ym_sizeof_aug_item', 'ym_train_aug_image_batch', 'ym_train_aug_masks_batch',
 )
 
 
@@ -93,6 +94,15 @@ class AugPlanC(ctypes.Structure):
                                               'fx', 'fy', 'has_brightness', 'has_contrast')] + \
                [(n, ctypes.c_float) for n in ('brightness', 'contrast', 'saturation', 'hue')] + \
                [('mean', ctypes.c_float * 3), ('std', ctypes.c_float * 3)]
+
+
+class AugItemC(ctypes.Structure):
+    """ym_aug_item: one sample of `ym_train_aug_image_batch` / `ym_train_aug_masks_batch`'s host table."""
+    _fields_ = [('plan', AugPlanC), ('n_masks', ctypes.c_int32), ('img', ctypes.c_void_p), ('masks', ctypes.c_void_p),
+                ('k', ctypes.c_int32), ('row0', ctypes.c_int32)]
+
+
+AUG_MAX_SAMPLES = 32            # YM_AUG_MAX_SAMPLES
 
 
 class PackItem(ctypes.Structure):
@@ -241,6 +251,12 @@ def lib():
         L.ym_adamw_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]
         L.ym_train_aug_image.argtypes = [vp, i32, ctypes.POINTER(AugPlanC), vp, vp]
         L.ym_train_aug_masks.argtypes = [vp, i32, vp, i32, ctypes.POINTER(AugPlanC), vp, vp]
+        L.ym_sizeof_aug_item.restype = sz
+        if L.ym_sizeof_aug_item() != ctypes.sizeof(AugItemC):
+            raise RuntimeError(f'libyolact_hip.so was built from a different ym_aug_item ({L.ym_sizeof_aug_item()} B) than '
+                               f'hip.AugItemC ({ctypes.sizeof(AugItemC)} B): rebuild the library')
+        L.ym_train_aug_image_batch.argtypes = [ctypes.POINTER(AugItemC), i32, i32, i32, vp, vp]
+        L.ym_train_aug_masks_batch.argtypes = [ctypes.POINTER(AugItemC), i32, i32, i32, vp, i32, vp, vp]
         L.ym_match_anchors.argtypes = [vp, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
         L.ym_match_anchors_batch.argtypes = [vp, vp, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
         L.ym_semantic_loss_batch.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp, vp]
@@ -304,7 +320,7 @@ def lib():
             fn = getattr(L, name)
             if name not in ('ym_last_error', 'ym_conv2d_workspace_bytes', 'ym_nms_workspace_bytes',
                             'ym_greedy_nms_workspace_bytes', 'ym_conv2d_wgrad_workspace_bytes',
-                            'ym_sizeof_conv_desc', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
+                            'ym_sizeof_conv_desc', 'ym_sizeof_aug_item', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
                             'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes',
                             'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes',
                             'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes'):

@@ -229,3 +229,128 @@ def train_aug(img, masks, boxes, labels, train_size, rng=_random):
         return None, None, None, None
     out, mout = apply_train_aug(img, masks, plan)
     return out, mout, plan.boxes, plan.labels
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# train_aug for a whole training batch: images of different sizes in, ONE [B, 3, S, S] tensor out, one launch pair per batch
+# (`ym_train_aug_image_batch` / `ym_train_aug_masks_batch`; B = 17 .. 32 takes two pairs).  The host half draws the B plans on one
+# `rng` in sample order, so a seeded run decides exactly what B successive `train_aug` calls decide; the device half writes every
+# image straight into its row of the batch tensor (no `torch.stack` copy) and every mask into one [K, S, S] allocation, with ONE
+# upload of all the `keep` indices.  The single-sample entries are the one-item instances of the same two kernels: row b of a batch
+# equals `train_aug` of sample b bit for bit.
+# ------------------------------------------------------------------------------------------------------------------------
+def sample_train_aug_batch(sizes, boxes, labels, train_size, rng=_random):
+    """The host half for B samples (no device, no library): `sizes` = [(h, w), ...], `boxes[b]` [n_b, 4] pixels or None (a sample
+    without a valid annotation: rejected WITHOUT a draw, as `COCODetection.finish` does), `labels[b]` [n_b].  One `sample_train_aug`
+    per sample, in order, on the one `rng`.  Returns `(plans, order)`: `plans[b]` an AugPlan or None (rejected); `order` the
+    batch `train_collate` makes of them -- the valid samples in order, then `valid_batch[i]` for each missing slot i (that list
+    grows while it is read, so one valid sample can fill several slots).  RuntimeError when no sample survives."""
+    sizes, boxes, labels = list(sizes), list(boxes), list(labels)
+    if not (len(sizes) == len(boxes) == len(labels)):
+        raise RuntimeError(f'sample_train_aug_batch: {len(sizes)} sizes, {len(boxes)} box arrays and {len(labels)} label arrays')
+    plans = [None if bx is None else sample_train_aug(int(h), int(w), bx, lb, train_size, rng)
+             for (h, w), bx, lb in zip(sizes, boxes, labels)]
+    order = [b for b, p in enumerate(plans) if p is not None]
+    if not order:
+        raise RuntimeError(f'sample_train_aug_batch: none of the {len(plans)} samples of the batch survived the augmentation')
+    for i in range(len(plans) - len(order)):
+        order.append(order[i])
+    return plans, order
+
+
+def _one_dtype(tensors, what, fn):
+    if any(not torch.is_tensor(t) for t in tensors):
+        raise RuntimeError(f'{fn}: {what} are device tensors')
+    if any(not t.is_cuda or t.device != tensors[0].device for t in tensors):
+        raise RuntimeError(f'yolact_minimal_amd.utils.augmentations.{fn} needs CUDA (HIP) tensors on one device; there is no CPU path.')
+    if tensors[0].dtype not in (torch.uint8, torch.float32) or any(t.dtype != tensors[0].dtype for t in tensors):
+        raise RuntimeError(f'{fn}: the {what} of a batch are all uint8 or all float32')
+
+
+def apply_train_aug_batch(imgs, masks, plans, out=None):
+    """The pixel half for B samples: `imgs` a `FrameBatch` or a list of device HWC BGR tensors (all uint8 or all float32; they need
+    not share an allocation and are not repacked), `masks` a list of device `[n_b, H_b, W_b]` tensors (all uint8 or all float32),
+    `plans` B AugPlans (no None: the caller has applied `order`; a repeated sample is the same item twice).  Returns
+    `(images [B, 3, S, S] float32, [masks_b [k_b, S, S] float32])`, the masks B views into ONE `[K, S, S]` allocation.  `out`: a
+    contiguous float32 device tensor `[>= B, 3, S, S]` whose first B rows are written (the result is then `out[:B]`).  One launch
+    per 16 samples for the images, one for the masks; every `keep` index of the batch goes up in one non-blocking copy from pinned
+    memory after being checked against n_b on the host.  No host synchronisation."""
+    from .frames import FrameBatch
+    fn = 'apply_train_aug_batch'
+    if isinstance(imgs, FrameBatch):
+        imgs.need_cuda('utils.augmentations.' + fn)
+        imgs = imgs.frames
+    elif isinstance(imgs, torch.Tensor) or not hasattr(imgs, '__len__'):
+        raise RuntimeError(f'{fn}: a FrameBatch or a list of [H, W, 3] device tensors expected')
+    if isinstance(masks, torch.Tensor) or not hasattr(masks, '__len__'):
+        raise RuntimeError(f'{fn}: a list of [n, H, W] device tensors expected')
+    imgs, masks, plans = list(imgs), list(masks), list(plans)
+    batch = len(imgs)
+    if not 1 <= batch <= hip.AUG_MAX_SAMPLES:
+        raise RuntimeError(f'{fn}: 1 .. {hip.AUG_MAX_SAMPLES} samples per call, got {batch}')
+    if len(masks) != batch or len(plans) != batch:
+        raise RuntimeError(f'{fn}: {batch} images, {len(masks)} mask tensors and {len(plans)} plans')
+    if any(p is None for p in plans):
+        raise RuntimeError(f'{fn}: a rejected sample (None) among the plans; apply the order of sample_train_aug_batch first')
+    _one_dtype(imgs, 'images', fn)
+    _one_dtype(masks, 'masks', fn)
+    dev = imgs[0].device
+    if masks[0].device != dev:
+        raise RuntimeError(f'{fn}: images on {dev}, masks on {masks[0].device}')
+    size = int(plans[0].size)
+    items = (hip.AugItemC * batch)()
+    keep_all, alive = [], []
+    for b, (img, m, plan) in enumerate(zip(imgs, masks, plans)):
+        if img.dim() != 3 or img.shape[2] != 3 or m.dim() != 3 or tuple(m.shape[1:]) != tuple(img.shape[:2]):
+            raise RuntimeError(f'{fn}: sample {b}: image {tuple(img.shape)} is [H, W, 3] and masks {tuple(m.shape)} are [n, H, W]')
+        if int(plan.size) != size:
+            raise RuntimeError(f'{fn}: sample {b}: plan of train size {plan.size} in a batch of {size}')
+        keep = [int(v) for v in plan.keep]
+        if any(v < 0 or v >= m.shape[0] for v in keep):
+            raise RuntimeError(f'{fn}: sample {b}: keep index outside its {m.shape[0]} masks')
+        img, m = img.contiguous(), m.contiguous()
+        alive += [img, m]
+        it = items[b]
+        it.plan = plan_to_c(plan, int(img.shape[0]), int(img.shape[1]))
+        it.n_masks, it.img, it.masks = int(m.shape[0]), img.data_ptr(), (m.data_ptr() if m.numel() else None)
+        it.k, it.row0 = len(keep), len(keep_all)
+        keep_all += keep
+    total = len(keep_all)
+    if out is None:
+        out = torch.empty(batch, 3, size, size, dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.device != dev or out.dtype != torch.float32 or out.dim() != 4 or \
+            out.shape[0] < batch or tuple(out.shape[1:]) != (3, size, size) or not out.is_contiguous():
+        raise RuntimeError(f'{fn}: out is a contiguous float32 [>= {batch}, 3, {size}, {size}] tensor on the device of the images')
+    mout = torch.empty(total, size, size, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        keep_dev = None
+        if total:
+            keep_dev = torch.tensor(keep_all, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        L = hip.lib()
+        hip.check(L.ym_train_aug_image_batch(items, batch, size, int(imgs[0].dtype == torch.uint8), hip.ptr(out), hip.stream_ptr()),
+                  'ym_train_aug_image_batch')
+        hip.check(L.ym_train_aug_masks_batch(items, batch, size, int(masks[0].dtype == torch.uint8), hip.ptr(keep_dev, torch.int32),
+                                             total, hip.ptr(mout), hip.stream_ptr()), 'ym_train_aug_masks_batch')
+    views = [mout[it.row0:it.row0 + it.k] for it in items]
+    return out[:batch], views
+
+
+def train_aug_batch(imgs, masks, boxes, labels, train_size, rng=_random):
+    """`train_aug` for a batch: `imgs` / `masks` as for `apply_train_aug_batch`, `boxes[b]` (pixels; None = no valid annotation) and
+    `labels[b]` host arrays.  Returns `(images [B, 3, S, S], [masks_b [k_b, S, S]], [boxes_b [k_b, 4] in 0..1], [labels_b [k_b]])`
+    in `train_collate`'s batch composition: rejected samples are replaced by repeated valid ones."""
+    from .frames import FrameBatch
+    frames = imgs.frames if isinstance(imgs, FrameBatch) else imgs
+    if isinstance(frames, torch.Tensor) or not hasattr(frames, '__len__') or isinstance(masks, torch.Tensor) or not hasattr(masks, '__len__'):
+        raise RuntimeError('train_aug_batch: a FrameBatch or a list of [H, W, 3] device tensors, and a list of [n, H, W] mask tensors expected')
+    frames, masks = list(frames), list(masks)
+    if not 1 <= len(frames) <= hip.AUG_MAX_SAMPLES:
+        raise RuntimeError(f'train_aug_batch: 1 .. {hip.AUG_MAX_SAMPLES} samples per call, got {len(frames)}')
+    if len(masks) != len(frames) or len(boxes) != len(frames) or len(labels) != len(frames):
+        raise RuntimeError(f'train_aug_batch: {len(frames)} images, {len(masks)} mask tensors, {len(boxes)} box arrays and '
+                           f'{len(labels)} label arrays')
+    _one_dtype(frames, 'images', 'train_aug_batch')
+    _one_dtype([m for m in masks if m is not None] or frames, 'masks', 'train_aug_batch')
+    plans, order = sample_train_aug_batch([(f.shape[0], f.shape[1]) for f in frames], boxes, labels, train_size, rng)
+    images, mviews = apply_train_aug_batch([frames[b] for b in order], [masks[b] for b in order], [plans[b] for b in order])
+    return images, mviews, [plans[b].boxes for b in order], [plans[b].labels for b in order]

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from .augmentations import train_aug, val_aug
+from .augmentations import train_aug, train_aug_batch, val_aug
 
 
 def _rle_string_to_counts(s):
@@ -278,6 +278,37 @@ class COCODetection:
         boxes = boxes / np.array([width, height, width, height])     # to 0~1 scale
         return img_out, np.hstack((boxes, np.expand_dims(labels, axis=1))), masks, height, width
 
+    def finish_batch(self, recs):
+        """`finish` for a whole training batch + `train_collate`, batch-native: ONE pinned upload of the B decoded images
+        (`FrameBatch.from_numpy`), the masks rasterised per image as in `finish`, ONE `train_aug_batch` (a launch pair per 16
+        samples, the images written straight into their rows of the batch tensor), ONE upload of all the targets.  The `random`
+        draws are those of B `finish` calls in order.  Returns what `train_collate` returns:
+        `(images [B, 3, S, S], [targets_b float32 [k_b, 5]], [masks_b float32 [k_b, S, S]])`."""
+        from .frames import FrameBatch
+        if self.mode != 'train':
+            raise RuntimeError(f"COCODetection.finish_batch serves mode 'train' only, this dataset is in mode '{self.mode}'")
+        recs = list(recs)
+        frames = FrameBatch.from_numpy([rec['img'] for rec in recs], self.device)
+        masks, boxes, labels = [], [], []
+        for rec, frame in zip(recs, frames.frames):
+            if len(rec['boxes']) == 0:
+                print(f"No valid object in image: {rec['img_id']}. Use a repeated image in this batch.")
+                masks.append(None)
+                boxes.append(None)
+                labels.append(None)
+                continue
+            bx = np.array(rec['boxes'])
+            m = self.coco.annsToMasks(rec['anns'])
+            assert tuple(m.shape) == (bx.shape[0], frame.shape[0], frame.shape[1]), 'Unmatched annotations.'
+            masks.append(m)
+            boxes.append(bx)
+            labels.append(np.array(rec['labels']))
+        images, masks_out, boxes_out, labels_out = train_aug_batch(frames, masks, boxes, labels, self.cfg.img_size, self.rng)
+        rows = [np.hstack((b, np.expand_dims(l, axis=1))) for b, l in zip(boxes_out, labels_out)]
+        host = torch.from_numpy(np.concatenate(rows, 0).astype(np.float32)).pin_memory()
+        targets = list(host.to(images.device, non_blocking=True).split([r.shape[0] for r in rows], 0))
+        return images, targets, masks_out
+
     def __getitem__(self, index):
         return self.finish(self.read(index))
 
@@ -288,7 +319,18 @@ class BatchLoader:
     ahead on `threads` host threads, `dataset.finish` (HIP launches, `random` draws) in sample order on the caller's thread,
     collated by `collate_fn`."""
 
-    def __init__(self, dataset, batch_size, collate_fn, shuffle=False, rank=0, world_size=1, seed=0, threads=4, drop_last=False):
+    def __init__(self, dataset, batch_size, collate_fn, shuffle=False, rank=0, world_size=1, seed=0, threads=4, drop_last=False,
+                 batched=False):
+        """`batched=True` (train mode, `train_collate` only): one `dataset.finish_batch` per batch in place of `batch_size` `finish`
+        calls + `collate_fn` -- the same batches from the same `random` draws."""
+        self.batched = bool(batched)
+        if self.batched:
+            if getattr(dataset, 'mode', None) != 'train':
+                raise RuntimeError(f"BatchLoader(batched=True) needs a dataset in mode 'train', got '{getattr(dataset, 'mode', None)}'")
+            if collate_fn is not train_collate:
+                raise RuntimeError('BatchLoader(batched=True) produces what train_collate produces: pass collate_fn=train_collate')
+            if not 1 <= batch_size <= hip.AUG_MAX_SAMPLES:
+                raise RuntimeError(f'BatchLoader(batched=True): 1 .. {hip.AUG_MAX_SAMPLES} samples per batch, got {batch_size}')
         self.dataset, self.batch_size, self.collate_fn = dataset, batch_size, collate_fn
         self.shuffle, self.rank, self.world_size, self.seed, self.threads, self.drop_last = shuffle, rank, world_size, seed, threads, drop_last
         self.epoch = 0
@@ -322,6 +364,11 @@ class BatchLoader:
             pending = [pool.submit(self.dataset.read, i) for i in batches[0]] if batches else []
             for b in range(len(batches)):
                 ahead = [pool.submit(self.dataset.read, i) for i in batches[b + 1]] if b + 1 < len(batches) else []
+                if self.batched:
+                    recs = [f.result() for f in pending]
+                    pending = ahead
+                    yield self.dataset.finish_batch(recs)                       # one upload, one launch pair, draws in sample order
+                    continue
                 samples = [self.dataset.finish(f.result()) for f in pending]    # GPU work + random draws: consumer thread, in order
                 pending = ahead
                 yield self.collate_fn(samples)
