@@ -279,6 +279,30 @@ int ym_poly_to_mask(const double* xy, const int32_t* poly_off, const int32_t* an
 int ym_runs_to_mask(const uint32_t* counts, const int32_t* run_off, int n, int H, int W, uint8_t* masks, void* workspace,
                     size_t workspace_bytes, ym_stream_t s);
 
+/* ym_ann_to_mask_ragged: the annotations of B <= YM_RAGGED_MAX_IMAGES images of DIFFERENT sizes, polygon lists and run lengths mixed,
+ * in ONE launch (the batched loader; ym_poly_to_mask / ym_runs_to_mask are its one-image instances: the same kernel, the same bits).
+ * Host tables, read during the call and passed to the kernel by value -- no device copy, no synchronisation, nothing to keep alive
+ * (the contract of ym_after_nms_ragged, whose table type `images` borrows; declared below):
+ *   images[b]    = {img_h_b, img_w_b, offset_b}: image b's block is [n_b][img_h_b][img_w_b] uint8 at masks + offset_b BYTES, what
+ *                  ym_poly_to_mask writes for that image alone; offset_b is a multiple of YM_RAGGED_ALIGN_BYTES, blocks do not overlap;
+ *   ann_first    = [B + 1]: image b owns the annotations [ann_first[b], ann_first[b + 1]) (n_b = 0 is allowed), ann_first[0] = 0,
+ *                  n = ann_first[B]; the annotations are ordered by image.
+ * Device arrays, indexed over the whole batch:
+ *   ann_kind[a]  = 0: a list of polygons, 1: uncompressed run lengths;
+ *   ann_off      = [n + 1]: annotation a owns the entries item_off[ann_off[a] .. ann_off[a + 1]): the start of each of its items, then
+ *                  one closing end (the two kinds index different arrays, so every annotation closes its own list).  An item of a
+ *                  polygon annotation is a polygon and its entries count (x, y) pairs of `xy`; a run-length annotation has exactly
+ *                  one item and its two entries index `counts`.  An annotation without polygons owns the closing entry alone.
+ * `xy` may be NULL when no annotation is a polygon list, `counts` when none is run lengths.  masks is 4-byte aligned, W <= 4096 and
+ * H * W < 2^31 per image.  Images whose two bitmaps do not fit the LDS (ym_ann_to_mask_workspace_bytes(1, H, W) > 0) take them from
+ * `workspace`, one slice per annotation: ym_ann_to_mask_ragged_workspace_bytes = the sum of those (0 when every image fits, and 0
+ * for tables the entry would refuse); YM_ENOSPC when it is short.  n = 0 launches nothing. */
+struct ym_ragged_image;
+size_t ym_ann_to_mask_ragged_workspace_bytes(const struct ym_ragged_image* images, const int32_t* ann_first, int B);
+int ym_ann_to_mask_ragged(const double* xy, const uint32_t* counts, const int32_t* item_off, const int32_t* ann_off,
+                          const int32_t* ann_kind, const struct ym_ragged_image* images, const int32_t* ann_first, int B,
+                          uint8_t* masks, void* workspace, size_t workspace_bytes, ym_stream_t s);
+
 /* ---- training: weight gradient, batch-norm with batch statistics, small backward ops, SGD -------------------
  * These replace what autograd + ATen/cuDNN execute for `loss_total.backward()` / `optimizer.step()`
  * (reference train.py:124-130) and nn.BatchNorm2d in train mode (modules/resnet.py:10-14,46). */

@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
     'ym_after_nms_ragged_workspace_bytes', 'ym_after_nms_ragged', 'ym_after_nms_ragged_packed',
     'ym_val_preprocess_batch', 'ym_draw_detections_ragged', 'ym_draw_detections_ragged_packed',
     'ym_sizeof_aug_item', 'ym_train_aug_image_batch', 'ym_train_aug_masks_batch',
+    'ym_ann_to_mask_ragged_workspace_bytes', 'ym_ann_to_mask_ragged',
 )
 
 
@@ -237,6 +238,9 @@ def lib():
         L.ym_ann_to_mask_workspace_bytes.restype = sz
         L.ym_poly_to_mask.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]
         L.ym_runs_to_mask.argtypes = [vp, vp, i32, i32, i32, vp, vp, sz, vp]
+        L.ym_ann_to_mask_ragged_workspace_bytes.argtypes = [ctypes.POINTER(RaggedImage), ctypes.POINTER(ctypes.c_int32), i32]
+        L.ym_ann_to_mask_ragged_workspace_bytes.restype = sz
+        L.ym_ann_to_mask_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(RaggedImage), ctypes.POINTER(ctypes.c_int32), i32, vp, vp, sz, vp]
         L.ym_layernorm_bwd_workspace_bytes.argtypes = [i32]
         L.ym_layernorm_bwd_workspace_bytes.restype = sz
         L.ym_layernorm_bwd.argtypes = [vp, vp, vp, f32, i64, i32, vp, vp, vp, vp, sz, vp]
@@ -323,7 +327,8 @@ def lib():
                             'ym_sizeof_conv_desc', 'ym_sizeof_aug_item', 'ym_bn_train_bwd_workspace_bytes', 'ym_mask_loss_workspace_bytes', 'ym_mask_loss_batch_workspace_bytes', 'ym_loss_workspace_bytes', 'ym_mask_iou_workspace_bytes', 'ym_layernorm_bwd_workspace_bytes',
                             'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes',
                             'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes',
-                            'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes'):
+                            'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes',
+                            'ym_ann_to_mask_ragged_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

@@ -11,6 +11,8 @@ What is rebuilt and how:
 * `anns_to_masks` / `COCO.annToMask` — polygon / RLE annotation -> dense uint8 mask **on the device** (`ym_poly_to_mask`,
   `ym_runs_to_mask`): the reference rasterises every instance on the CPU and later ships n x H x W floats over PCIe; here
   only the vertices cross and the masks are born in HBM, where `train_aug` / `val_aug` / the loss kernels consume them.
+* `pack_annotations` / `anns_to_masks_batch` / `COCO.annsToMasksBatch` — the same for the images of a whole batch, whatever their
+  sizes: one packed host buffer, one pinned upload, one `ym_ann_to_mask_ragged` launch per 32 images (`finish_batch`).
 * image decode — PIL (libjpeg) instead of `cv2.imread`; BGR channel order and EXIF orientation handled like cv2.  Host I/O,
   "parity unpinned" (no cv2 here to compare with).
 * `COCODetection.__getitem__` — same three modes and return shapes as the reference, with CUDA tensors for the image and the
@@ -22,7 +24,7 @@ import glob
 import json
 import os.path as osp
 import random as _random
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import ctypes
@@ -114,6 +116,128 @@ def anns_to_masks(segmentations, height, width, device='cuda'):
     return masks
 
 
+PackedAnnotations = namedtuple('PackedAnnotations', 'xy counts item_off ann_off ann_kind ann_first sizes block_offsets total_bytes '
+                                                    'buffer array_offsets')
+PackedAnnotations.__doc__ = """What `pack_annotations` returns: the five arrays of `ym_ann_to_mask_ragged` (views of `buffer`, a flat
+uint8 host array, each starting at its 8-byte aligned `array_offsets[name]`), `ann_first` = [len(images) + 1] ints, and the layout of the
+masks: image b's `[n_b, h_b, w_b]` block starts at byte `block_offsets[b]` of an allocation of `total_bytes`."""
+
+
+def _mask_block_layout(sizes, n_per_image):
+    """Byte offsets of the images' `[n_b, h_b, w_b]` uint8 blocks and where the last one ends: `frame_layout`'s rule (`hip.aligned_layout`:
+    every block at a multiple of 256 bytes) with a block's own extent, applied per launch of at most 32 images, one launch's blocks
+    behind the other's."""
+    offsets, end = [], 0
+    for i0 in range(0, len(sizes), hip.RAGGED_MAX_IMAGES):
+        base = -(-end // hip.RAGGED_ALIGN_BYTES) * hip.RAGGED_ALIGN_BYTES
+        count = iter(n_per_image[i0:i0 + hip.RAGGED_MAX_IMAGES])               # (aligned_layout asks for the extents in image order)
+        offs, total = hip.aligned_layout('pack_annotations', sizes[i0:i0 + hip.RAGGED_MAX_IMAGES], 1, lambda h, w: next(count) * h * w)
+        offsets += [base + o for o in offs]
+        end = base + total
+    return offsets, end
+
+
+def pack_annotations(segs_per_image, sizes, alloc=None):
+    """Host half of `anns_to_masks_batch` (numpy only, no GPU, no library): `segs_per_image` = [[COCO `segmentation`, ...] per image],
+    `sizes` = [(h, w) per image] -> `PackedAnnotations`.  The rules are `anns_to_masks`': k = len(poly) // 2 vertices per polygon, a
+    compressed RLE string is decoded, an RLE whose `size` is not its image's raises ValueError.  Annotation a (global, in image order)
+    owns the entries `item_off[ann_off[a] : ann_off[a + 1]]`: the start of each of its items and one closing end -- (x, y) pairs of
+    `xy` for a polygon list (`ann_kind` 0), one item in `counts` for run lengths (`ann_kind` 1).  `alloc(nbytes)` supplies the flat
+    uint8 buffer (default `np.empty`; `anns_to_masks_batch` hands out pinned memory)."""
+    segs_per_image = [list(segs) for segs in segs_per_image]
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    if len(segs_per_image) != len(sizes):
+        raise ValueError(f'pack_annotations: {len(segs_per_image)} annotation lists for {len(sizes)} image sizes')
+    xy, counts, item_off, ann_off, ann_kind, ann_first = [], [], [], [0], [], [0]
+    n_xy = 0
+    for segs, (height, width) in zip(segs_per_image, sizes):
+        for seg in segs:
+            if isinstance(seg, list):
+                for poly in seg:
+                    k = len(poly) // 2                               # frPyObjects: k = len / 2, a trailing odd value is ignored
+                    xy.extend(poly[:2 * k])
+                    item_off.append(n_xy)
+                    n_xy += k
+                item_off.append(n_xy)
+                ann_kind.append(0)
+            else:
+                c = seg['counts']
+                c = _rle_string_to_counts(c) if isinstance(c, (str, bytes)) else list(c)
+                if list(seg.get('size', [height, width])) != [height, width]:
+                    raise ValueError(f"RLE annotation of size {seg.get('size')} in a {height} x {width} image")
+                item_off.append(len(counts))
+                counts.extend(c)
+                item_off.append(len(counts))
+                ann_kind.append(1)
+            ann_off.append(len(item_off))
+        ann_first.append(len(ann_kind))
+    block_offsets, total_bytes = _mask_block_layout(sizes, [len(segs) for segs in segs_per_image])
+    arrays = (('xy', xy, np.float64), ('counts', counts, np.uint32), ('item_off', item_off, np.int32), ('ann_off', ann_off, np.int32),
+              ('ann_kind', ann_kind, np.int32))
+    array_offsets, end = {}, 0
+    for name, values, dtype in arrays:
+        array_offsets[name] = end
+        end += -(-len(values) * np.dtype(dtype).itemsize // 8) * 8
+    buffer = (alloc or (lambda nbytes: np.empty(nbytes, np.uint8)))(max(end, 8))
+    views = {}
+    for name, values, dtype in arrays:
+        views[name] = buffer[array_offsets[name]:array_offsets[name] + len(values) * np.dtype(dtype).itemsize].view(dtype)
+        views[name][:] = np.asarray(values, dtype=dtype)
+    return PackedAnnotations(views['xy'], views['counts'], views['item_off'], views['ann_off'], views['ann_kind'], ann_first, sizes,
+                             block_offsets, total_bytes, buffer, array_offsets)
+
+
+def anns_to_masks_batch(segs_per_image, sizes, device='cuda', out=None):
+    """`anns_to_masks` for the images of a batch, of any sizes: [[segmentation, ...] per image], [(h, w) per image] -> a list of
+    `[n_b, h_b, w_b]` uint8 views of ONE device allocation (an image without annotations: an empty `[0, h_b, w_b]` view), each what
+    `anns_to_masks` returns for that image alone.  ONE pinned, non-blocking upload of the packed annotations (the pinned buffer goes
+    back to torch's host allocator, which holds it until the copy is done: `FrameBatch.from_numpy`'s rule), one workspace allocation
+    if an image's bitmaps do not fit the LDS, ONE `ym_ann_to_mask_ragged` launch per 32 images.  `out`: a flat uint8 device tensor to
+    rasterise into instead of a new allocation (bytes between the blocks are not written)."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('yolact_minimal_amd.utils.coco rasterises masks with HIP kernels: a CUDA/HIP device is required')
+    pinned = []
+
+    def alloc(nbytes):
+        pinned.append(torch.empty(nbytes, dtype=torch.uint8).pin_memory())
+        return pinned[0].numpy()
+    pk = pack_annotations(segs_per_image, sizes, alloc)
+    if out is None:
+        out = torch.empty(pk.total_bytes, dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous() and out.device == dev
+              and out.numel() >= pk.total_bytes):
+        raise RuntimeError(f'anns_to_masks_batch: `out` is a flat contiguous uint8 tensor of at least {pk.total_bytes} bytes on {dev}')
+    counts = [pk.ann_first[b + 1] - pk.ann_first[b] for b in range(len(pk.sizes))]
+    views = [out[o:o + n * h * w].view(n, h, w) for n, (h, w), o in zip(counts, pk.sizes, pk.block_offsets)]
+    if pk.ann_first[-1] == 0:
+        return views
+    L = hip.lib()
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    launches = []
+    for i0 in range(0, len(pk.sizes), hip.RAGGED_MAX_IMAGES):
+        i1 = min(i0 + hip.RAGGED_MAX_IMAGES, len(pk.sizes))
+        a0 = pk.ann_first[i0]
+        if pk.ann_first[i1] == a0:
+            continue
+        table = hip.ragged_table(pk.sizes[i0:i1], pk.block_offsets[i0:i1])
+        first = (ctypes.c_int32 * (i1 - i0 + 1))(*[f - a0 for f in pk.ann_first[i0:i1 + 1]])
+        launches.append((table, first, i1 - i0, a0, L.ym_ann_to_mask_ragged_workspace_bytes(table, ctypes.cast(first, i32p), i1 - i0)))
+    with torch.cuda.device(dev):
+        packed = pinned[0].to(dev, non_blocking=True)
+        at = {name: packed.data_ptr() + o for name, o in pk.array_offsets.items()}
+        ws_bytes = max(l[4] for l in launches)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev) if ws_bytes else None
+        for table, first, count, a0, _ in launches:
+            # (the annotations of a launch are a0 ...: its ann_off / ann_kind start there, their values stay global)
+            hip.check(L.ym_ann_to_mask_ragged(ctypes.c_void_p(at['xy']), ctypes.c_void_p(at['counts']), ctypes.c_void_p(at['item_off']),
+                                              ctypes.c_void_p(at['ann_off'] + 4 * a0), ctypes.c_void_p(at['ann_kind'] + 4 * a0), table,
+                                              ctypes.cast(first, i32p), count, ctypes.c_void_p(out.data_ptr()),
+                                              ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, ws_bytes, hip.stream_ptr()),
+                      'ym_ann_to_mask_ragged')
+    return views
+
+
 class COCO:
     """The part of `pycocotools.coco.COCO` the reader uses, same attribute / method names."""
 
@@ -176,6 +300,13 @@ class COCO:
         """All the annotations of ONE image in one launch -> [n, h, w] uint8 CUDA tensor."""
         rec = self.imgs[anns[0]['image_id']]
         return anns_to_masks([a['segmentation'] for a in anns], rec['height'], rec['width'], self.device)
+
+    def annsToMasksBatch(self, anns_per_image):
+        """`annsToMasks` for several images (each list non-empty, of one image) in one launch per 32 images -> a list of
+        [n_b, h_b, w_b] uint8 CUDA views of one allocation."""
+        recs = [self.imgs[anns[0]['image_id']] for anns in anns_per_image]
+        return anns_to_masks_batch([[a['segmentation'] for a in anns] for anns in anns_per_image],
+                                   [(rec['height'], rec['width']) for rec in recs], self.device)
 
 
 def imread_bgr(path):
@@ -280,8 +411,8 @@ class COCODetection:
 
     def finish_batch(self, recs):
         """`finish` for a whole training batch + `train_collate`, batch-native: ONE pinned upload of the B decoded images
-        (`FrameBatch.from_numpy`), the masks rasterised per image as in `finish`, ONE `train_aug_batch` (a launch pair per 16
-        samples, the images written straight into their rows of the batch tensor), ONE upload of all the targets.  The `random`
+        (`FrameBatch.from_numpy`), ONE rasteriser launch for the masks of all of them (`COCO.annsToMasksBatch`), ONE
+        `train_aug_batch` (a launch pair per 16 samples, the images written straight into their rows of the batch tensor), ONE upload of all the targets.  The `random`
         draws are those of B `finish` calls in order.  Returns what `train_collate` returns:
         `(images [B, 3, S, S], [targets_b float32 [k_b, 5]], [masks_b float32 [k_b, S, S]])`."""
         from .frames import FrameBatch
@@ -289,6 +420,8 @@ class COCODetection:
             raise RuntimeError(f"COCODetection.finish_batch serves mode 'train' only, this dataset is in mode '{self.mode}'")
         recs = list(recs)
         frames = FrameBatch.from_numpy([rec['img'] for rec in recs], self.device)
+        valid = [rec for rec in recs if len(rec['boxes']) > 0]
+        rasters = iter(self.coco.annsToMasksBatch([rec['anns'] for rec in valid]) if valid else [])
         masks, boxes, labels = [], [], []
         for rec, frame in zip(recs, frames.frames):
             if len(rec['boxes']) == 0:
@@ -298,7 +431,7 @@ class COCODetection:
                 labels.append(None)
                 continue
             bx = np.array(rec['boxes'])
-            m = self.coco.annsToMasks(rec['anns'])
+            m = next(rasters)
             assert tuple(m.shape) == (bx.shape[0], frame.shape[0], frame.shape[1]), 'Unmatched annotations.'
             masks.append(m)
             boxes.append(bx)
