@@ -747,6 +747,27 @@ int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* bo
                                int Wp, int K, const ym_ragged_image* images, int do_crop, uint64_t* mask_bits, int32_t* boxes_px,
                                void* workspace, size_t workspace_bytes, ym_stream_t s);
 
+/* ---- window mode: a network that ran on the top-left Hn x Wn of its square input ---------------------------------------------------
+ * The square input of a non-square frame is picture at the top-left and norm_mean (normalised: exactly 0.0) below / right of it.
+ * ym_val_preprocess_window writes only the top-left Hn x Wn of the S x S result, the network runs on that, and its prototype map is
+ * the top-left Hp x Wp = Hn/4 x Wn/4 of the VIRTUAL Pv x Pv map (Pv = S / 4) the square run would have produced; boxes stay in 0..1 of
+ * the S x S square.  ym_after_nms_window[_packed] is ym_after_nms_ragged[_packed] (same table, same layout, same launch path; one
+ * output size is the one-entry table) with that virtual extent:
+ *   - box -> prototype pixels and the crop window use Pv on BOTH axes (clamped to [0, Pv] as before);
+ *   - the resize scale is Pv / max(img_h_b, img_w_b) on both axes;
+ *   - source indices clamp to the physical Hp - 1 / Wp - 1, so an output row whose source lies past the window reads row Hp - 1,
+ *     crop status included (bilinear interpolation over the replicate-padded map);
+ *   - boxes_px as before: S_b = max(img_h_b, img_w_b).
+ * Pv >= max(Hp, Wp) (YM_EINVAL otherwise).  The older entries are the Pv = 0 case of the same kernels ("the map is the whole extent")
+ * and return the bits they always did.  Workspace: ym_after_nms_window_workspace_bytes (the fused kernel is chosen by Pv / S). */
+size_t ym_after_nms_window_workspace_bytes(const ym_ragged_image* images, int B, int max_det, int Hp, int Wp, int Pv);
+int ym_after_nms_window(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
+                        int Wp, int K, const ym_ragged_image* images, int Pv, int do_crop, float* masks, int32_t* boxes_px,
+                        void* workspace, size_t workspace_bytes, ym_stream_t s);
+int ym_after_nms_window_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
+                               int Wp, int K, const ym_ragged_image* images, int Pv, int do_crop, uint64_t* mask_bits,
+                               int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s);
+
 /* ---- frames of different sizes: the two ends of a mixed-size request ----------------------------------------------------------
  * The same table type describes a batch of FRAMES: entry b = {img_h_b, img_w_b, offset_b}, frame b is HWC BGR [img_h_b][img_w_b][3]
  * at `frames + offset_b`, offset counted in elements of the frame buffer (bytes for uint8, floats for float32).  The rules are the
@@ -768,6 +789,11 @@ int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* bo
  * size, B <= YM_RAGGED_MAX_IMAGES and no matte for the tables -- and each entry reports errors under its own name. */
 int ym_val_preprocess_batch(const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S, const float* mean_bgr,
                             const float* std_bgr, float* out, ym_stream_t s);
+/* The same launch with an output of [B][3][Hn][Wn], 0 < Hn, Wn <= S: the top-left window of every frame's S x S result, bit for bit
+ * (a pixel's arithmetic depends on its own coordinates only; scale = max(img_h, img_w) / S as before).  Hn = Wn = S is
+ * ym_val_preprocess_batch.  The caller picks a window that holds every frame's picture (rect_window in the Python package). */
+int ym_val_preprocess_window(const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S, int Hn, int Wn,
+                             const float* mean_bgr, const float* std_bgr, float* out, ym_stream_t s);
 int ym_draw_detections_ragged(const uint8_t* img, const float* masks, const int64_t* ids, const float* scores, const int32_t* boxes_px,
                               const int32_t* counts, int B, int max_det, const ym_ragged_image* frames,
                               const ym_ragged_image* mask_blocks, const uint8_t* palette, int palette_n, int num_classes,

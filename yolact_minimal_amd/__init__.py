@@ -7,5 +7,8 @@ Only what the data-parallel hot path needs lives here:
   modules/   `Yolact` with the reference's constructor / forward / state-dict surface
   utils/     `nms`, `after_nms`, `make_anchors` with the reference's signatures
   config.py  cfg classes + `get_config`
+`rect_window` / `rect_anchor_index` (utils/rect.py): the geometry of rectangular inference, host only.
 """
-__all__ = ['config', 'hip', 'engine', 'modules', 'utils']
+from .utils.rect import rect_window, rect_anchor_index  # noqa: F401
+
+__all__ = ['config', 'hip', 'engine', 'modules', 'utils', 'rect_window', 'rect_anchor_index']

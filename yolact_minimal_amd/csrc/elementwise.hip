@@ -252,15 +252,19 @@ extern "C" int ym_softmax_rows(const float* in, float* out, int64_t rows, int C,
 // ym_val_preprocess and ym_val_preprocess_batch are ONE kernel (grid.y = frame, the {img_h, img_w, offset} table by value in the
 // kernel arguments, indexed by the uniform blockIdx.y: no device copy, no synchronisation); the single-image entry is its B = 1
 // instance, so a frame of a batch and the same frame alone run the same instructions and agree bit for bit.
+// ym_val_preprocess_window is the same kernel again with an output of Hn x Wn <= S x S: the top-left WINDOW of the S x S result (the
+// padding sits at the bottom / right, so a window that holds every frame's picture drops only norm_mean = exactly 0.0).  A pixel's
+// arithmetic depends on (oy, ox) alone, so the window equals the square output's [:Hn, :Wn] bit for bit; the two older entries are
+// its Hn = Wn = S case.
 namespace {
-// output pixel i (= oy * S + ox) of one H x W frame, all three channels
+// output pixel i (= oy * Wn + ox) of the Hn x Wn window of one H x W frame's S x S output, all three channels
 template <typename T>
-__device__ __forceinline__ void val_preprocess_pixel(const T* __restrict__ img, int H, int W, int S, int i, f32x4 mean, f32x4 stdv,
-                                                     float* __restrict__ out) {
+__device__ __forceinline__ void val_preprocess_pixel(const T* __restrict__ img, int H, int W, int S, int Hn, int Wn, int i, f32x4 mean,
+                                                     f32x4 stdv, float* __restrict__ out) {
     const int P = H > W ? H : W;
     const float scale = (float)P / (float)S;
-    const int total = S * S;
-    const int oy = i / S, ox = i - oy * S;
+    const int total = Hn * Wn;
+    const int oy = i / Wn, ox = i - oy * Wn;
     float sy = scale * ((float)oy + 0.5f) - 0.5f, sx = scale * ((float)ox + 0.5f) - 0.5f;
     if (sy < 0.f) sy = 0.f;
     if (sx < 0.f) sx = 0.f;
@@ -280,24 +284,38 @@ __device__ __forceinline__ void val_preprocess_pixel(const T* __restrict__ img, 
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void k_val_preprocess(const T* __restrict__ frames, const YmRaggedTable tab, int S, f32x4 mean,
-                                                         f32x4 stdv, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_val_preprocess(const T* __restrict__ frames, const YmRaggedTable tab, int S, int Hn, int Wn,
+                                                         f32x4 mean, f32x4 stdv, float* __restrict__ out) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= S * S) return;
-    val_preprocess_pixel<T>(frames + tab.img[b].offset, tab.img[b].img_h, tab.img[b].img_w, S, i, mean, stdv,
-                            out + (size_t)b * 3 * S * S);
+    if (i >= Hn * Wn) return;
+    val_preprocess_pixel<T>(frames + tab.img[b].offset, tab.img[b].img_h, tab.img[b].img_w, S, Hn, Wn, i, mean, stdv,
+                            out + (size_t)b * 3 * Hn * Wn);
 }
 
-int val_preprocess_launch(const void* frames, int is_uint8, const YmRaggedTable& tab, int B, int S, const float* mean_bgr,
+int val_preprocess_launch(const void* frames, int is_uint8, const YmRaggedTable& tab, int B, int S, int Hn, int Wn, const float* mean_bgr,
                           const float* std_bgr, float* out, ym_stream_t s) {
     const f32x4 mean = {mean_bgr[0], mean_bgr[1], mean_bgr[2], 0.f}, stdv = {std_bgr[0], std_bgr[1], std_bgr[2], 1.f};
-    const dim3 grid((S * S + 255) / 256, B);
+    const dim3 grid((Hn * Wn + 255) / 256, B);
     if (is_uint8)
         hipLaunchKernelGGL(k_val_preprocess<unsigned char>, grid, dim3(256), 0, (hipStream_t)s, (const unsigned char*)frames, tab, S,
-                           mean, stdv, out);
+                           Hn, Wn, mean, stdv, out);
     else
-        hipLaunchKernelGGL(k_val_preprocess<float>, grid, dim3(256), 0, (hipStream_t)s, (const float*)frames, tab, S, mean, stdv, out);
+        hipLaunchKernelGGL(k_val_preprocess<float>, grid, dim3(256), 0, (hipStream_t)s, (const float*)frames, tab, S, Hn, Wn, mean, stdv,
+                           out);
     return ym_check_launch("val_preprocess");
+}
+
+int val_preprocess_table(const char* what, const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S, int Hn, int Wn,
+                         const float* mean_bgr, const float* std_bgr, float* out, ym_stream_t s) {
+    YM_REQUIRE(frames && out && mean_bgr && std_bgr, "%s: null pointer", what);
+    YM_REQUIRE(S > 0 && S <= 32768, "%s: output size %d out of range (1..32768)", what, S);
+    YM_REQUIRE(Hn > 0 && Wn > 0 && Hn <= S && Wn <= S, "%s: window %d x %d is not inside %d x %d", what, Hn, Wn, S, S);
+    const int rc = ym_check_ragged_table(what, images, B, is_uint8 ? 1 : 4,
+                                         [](const ym_ragged_image& im) { return (int64_t)im.img_h * im.img_w * 3; });
+    if (rc != YM_OK) return rc;
+    YmRaggedTable tab = {};
+    std::copy(images, images + B, tab.img);
+    return val_preprocess_launch(frames, is_uint8, tab, B, S, Hn, Wn, mean_bgr, std_bgr, out, s);
 }
 }  // namespace
 
@@ -306,17 +324,15 @@ extern "C" int ym_val_preprocess(const void* img_hwc_bgr, int is_uint8, int H, i
     YM_REQUIRE(img_hwc_bgr && out_chw_rgb && mean_bgr && std_bgr && H > 0 && W > 0 && S > 0, "val_preprocess: bad args");
     YmRaggedTable tab = {};
     tab.img[0] = ym_ragged_image{H, W, 0};
-    return val_preprocess_launch(img_hwc_bgr, is_uint8, tab, 1, S, mean_bgr, std_bgr, out_chw_rgb, s);
+    return val_preprocess_launch(img_hwc_bgr, is_uint8, tab, 1, S, S, S, mean_bgr, std_bgr, out_chw_rgb, s);
 }
 
 extern "C" int ym_val_preprocess_batch(const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S,
                                        const float* mean_bgr, const float* std_bgr, float* out, ym_stream_t s) {
-    YM_REQUIRE(frames && out && mean_bgr && std_bgr, "val_preprocess_batch: null pointer");
-    YM_REQUIRE(S > 0 && S <= 32768, "val_preprocess_batch: output size %d out of range (1..32768)", S);
-    const int rc = ym_check_ragged_table("val_preprocess_batch", images, B, is_uint8 ? 1 : 4,
-                                         [](const ym_ragged_image& im) { return (int64_t)im.img_h * im.img_w * 3; });
-    if (rc != YM_OK) return rc;
-    YmRaggedTable tab = {};
-    std::copy(images, images + B, tab.img);
-    return val_preprocess_launch(frames, is_uint8, tab, B, S, mean_bgr, std_bgr, out, s);
+    return val_preprocess_table("val_preprocess_batch", frames, is_uint8, images, B, S, S, S, mean_bgr, std_bgr, out, s);
+}
+
+extern "C" int ym_val_preprocess_window(const void* frames, int is_uint8, const ym_ragged_image* images, int B, int S, int Hn, int Wn,
+                                        const float* mean_bgr, const float* std_bgr, float* out, ym_stream_t s) {
+    return val_preprocess_table("val_preprocess_window", frames, is_uint8, images, B, S, Hn, Wn, mean_bgr, std_bgr, out, s);
 }

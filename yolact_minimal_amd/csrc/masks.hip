@@ -13,6 +13,10 @@
 //                    (RaggedSizes); after_nms_launches<PACKED, Sizes> is the launch set of the four ym_after_nms_* entries, with
 //                    k_boxes_to_pixels_batch<Sizes> at its end.
 //  k_pack_masks / k_unpack_masks : dense <-> bits.
+//  Window mode (`Pv`, ym_after_nms_window[_packed]): the Hp x Wp prototype map is the top-left window of a VIRTUAL Pv x Pv map (the
+//                    network ran on the top-left Hn x Wn of its square input, Pv = img_size / 4).  Pv = 0 is the reference's rule
+//                    (the map is the whole extent, scaled per axis) and what every older entry passes; the rule for Pv > 0 is at
+//                    `ProtoGeom` below.  One argument of the same kernels, not a second set.
 #pragma clang fp contract(off)
 #include "ym_common.h"
 #include <algorithm>
@@ -31,8 +35,23 @@ __device__ __forceinline__ void crop_span(float a, float b, float size, float& l
     hi = hi > size ? size : hi;
 }
 
+// Where a 0..1 box lands on the prototype map and how an output pixel maps back to it.
+//   Pv == 0: the map is the whole extent: boxes scale by (Wp, Hp), the resize by Hp / S and Wp / S, S = max(img_h, img_w).
+//   Pv  > 0: the map is the top-left Hp x Wp of a virtual Pv x Pv map: boxes and the crop window scale by Pv on both axes, the resize
+//            by Pv / S on both axes, and source indices clamp to the PHYSICAL Hp - 1 / Wp - 1 (src_coord's own clamp), so a row or
+//            column past the window reads the window's last one, crop status included.
+struct ProtoGeom {
+    float ch, cw;       // crop extents (rows, columns)
+    float sy, sx;       // resize scales
+};
+__device__ __forceinline__ ProtoGeom proto_geom(int Hp, int Wp, int Pv, int img_h, int img_w) {
+    const int S = img_h > img_w ? img_h : img_w;
+    const float eh = (float)(Pv > 0 ? Pv : Hp), ew = (float)(Pv > 0 ? Pv : Wp);
+    return ProtoGeom{eh, ew, eh / (float)S, ew / (float)S};
+}
+
 __global__ __launch_bounds__(256) void k_mask_assemble(const float* __restrict__ proto, const float* __restrict__ coefs,
-                                                        const float* __restrict__ boxes, int n, int Hp, int Wp,
+                                                        const float* __restrict__ boxes, int n, int Hp, int Wp, int Pv,
                                                         int do_crop, float* __restrict__ out) {
     const int P = Hp * Wp;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -68,8 +87,8 @@ __global__ __launch_bounds__(256) void k_mask_assemble(const float* __restrict__
             if (do_crop) {
                 const f32x4 b = *reinterpret_cast<const f32x4*>(boxes + (size_t)d * 4);
                 float x1, x2, y1, y2;
-                crop_span(b[0], b[2], (float)Wp, x1, x2);
-                crop_span(b[1], b[3], (float)Hp, y1, y2);
+                crop_span(b[0], b[2], (float)(Pv > 0 ? Pv : Wp), x1, x2);
+                crop_span(b[1], b[3], (float)(Pv > 0 ? Pv : Hp), y1, y2);
                 const bool inside = fx >= x1 && fx < x2 && fy >= y1 && fy < y2;
                 v = inside ? v : 0.f;
             }
@@ -82,9 +101,9 @@ __device__ __forceinline__ void src_coord(int dst, float scale, int in_sz, int& 
     float src = scale * ((float)dst + 0.5f) - 0.5f;
     if (src < 0.f) src = 0.f;
     i0 = (int)src;
-    if (i0 > in_sz - 1) i0 = in_sz - 1;
-    i1 = i0 + ((i0 < in_sz - 1) ? 1 : 0);
-    l1 = src - (float)i0;
+    l1 = src - (float)i0;                      // (the fraction of the UNclamped index: a coordinate past the map blends its last
+    if (i0 > in_sz - 1) i0 = in_sz - 1;        //  row with itself, like interpolation over a replicate-padded map; only window mode
+    i1 = i0 + ((i0 < in_sz - 1) ? 1 : 0);      //  gets there, a map scaled to its own extent never exceeds in_sz - 1)
 }
 
 // Is the soft mask, interpolated between source rows r0 / r1 (weights 1 - ly / ly) at output column x, foreground?  THE expression of
@@ -110,11 +129,12 @@ template <> struct mask_elem<true> { typedef unsigned long long type; };
 // so rows at or past it are not written.
 template <bool PACKED>
 __global__ __launch_bounds__(256) void k_mask_resize(const float* __restrict__ masks, const int32_t* __restrict__ count, int n, int Hp,
-                                                      int Wp, int img_h, int img_w, typename mask_elem<PACKED>::type* __restrict__ out) {
+                                                      int Wp, int Pv, int img_h, int img_w,
+                                                      typename mask_elem<PACKED>::type* __restrict__ out) {
     n = count ? clamped_count(count, n) : n;
     constexpr int LG = PACKED ? 6 : 2, PER_BLOCK = PACKED ? 4 : 256;
-    const int S = img_h > img_w ? img_h : img_w;
-    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
+    const ProtoGeom g = proto_geom(Hp, Wp, Pv, img_h, img_w);
+    const float sy = g.sy, sx = g.sx;
     const int wq = (img_w + (1 << LG) - 1) >> LG;
     const size_t total = (size_t)n * img_h * wq;
     const size_t first = (size_t)blockIdx.x * PER_BLOCK + (PACKED ? threadIdx.x >> 6 : threadIdx.x);
@@ -167,21 +187,21 @@ constexpr int FP_W = 96, FP_H = 10;           // source patch capacity (floats):
 // [img_h][wq] words), `patch` / `cf` the workgroup's LDS.  PACKED only changes the lane -> pixel map and the store (below).
 template <bool PACKED>
 __device__ __forceinline__ void fused_tile(float* patch, float* cf, const float* __restrict__ pimg, const float* __restrict__ coef,
-                                           const float* __restrict__ box, int tile, int Hp, int Wp, int img_h, int img_w, int do_crop,
-                                           typename mask_elem<PACKED>::type* __restrict__ obase) {
+                                           const float* __restrict__ box, int tile, int Hp, int Wp, int Pv, int img_h, int img_w,
+                                           int do_crop, typename mask_elem<PACKED>::type* __restrict__ obase) {
     static_assert(FT_W == 256 && FT_H == 16, "4 words x (4 waves x 4 rows) per tile");
     const int tiles_x = (img_w + FT_W - 1) / FT_W;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int oy0 = ty * FT_H, ox0 = tx * FT_W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int S = img_h > img_w ? img_h : img_w;
-    const float sy = (float)Hp / (float)S, sx = (float)Wp / (float)S;
+    const ProtoGeom g = proto_geom(Hp, Wp, Pv, img_h, img_w);
+    const float sy = g.sy, sx = g.sx;
 
-    float x1 = 0.f, x2 = (float)Wp, y1 = 0.f, y2 = (float)Hp;
+    float x1 = 0.f, x2 = g.cw, y1 = 0.f, y2 = g.ch;
     if (do_crop) {
         const f32x4 bx = *reinterpret_cast<const f32x4*>(box);
-        crop_span(bx[0], bx[2], (float)Wp, x1, x2);
-        crop_span(bx[1], bx[3], (float)Hp, y1, y2);
+        crop_span(bx[0], bx[2], g.cw, x1, x2);
+        crop_span(bx[1], bx[3], g.ch, y1, y2);
     }
     // source patch of this tile (src_coord is monotonic in the destination index)
     int py0, py1, px0, px1, t0, t1; float l;
@@ -288,10 +308,11 @@ __device__ __forceinline__ void fused_tile(float* patch, float* cf, const float*
 // ---------------------------------------------------------------------------------------------------------------------------
 __host__ __device__ inline int fused_tiles(int img_h, int img_w) { return ((img_w + FT_W - 1) / FT_W) * ((img_h + FT_H - 1) / FT_H); }
 
-// Does the fused kernel's LDS patch hold the source pixels of one output tile at this scale?
-bool fused_fits(int Hp, int Wp, int img_h, int img_w) {
+// Does the fused kernel's LDS patch hold the source pixels of one output tile at this scale?  (Window mode scales both axes by Pv / S;
+// the clamp to the physical map only ever shortens a patch.)
+bool fused_fits(int Hp, int Wp, int Pv, int img_h, int img_w) {
     const int S = img_h > img_w ? img_h : img_w;
-    const double sy = (double)Hp / S, sx = (double)Wp / S;
+    const double sy = (double)(Pv > 0 ? Pv : Hp) / S, sx = (double)(Pv > 0 ? Pv : Wp) / S;
     return (int)(FT_H * sy) + 3 <= FP_H && (int)(FT_W * sx) + 3 <= FP_W;
 }
 
@@ -303,7 +324,7 @@ struct UniformSizes {
     __host__ __device__ int h(int) const { return hw[0]; }
     __host__ __device__ int w(int) const { return hw[1]; }
     template <bool PACKED> __host__ __device__ size_t base(int b, int max_det, int d = 0) const { return ((size_t)b * max_det + d) * (size_t)hw[0] * ym_mask_row(PACKED, hw[1]); }
-    bool fused(int, int Hp, int Wp) const { return fused_fits(Hp, Wp, hw[0], hw[1]); }
+    bool fused(int, int Hp, int Wp) const { return fused_fits(Hp, Wp, 0, hw[0], hw[1]); }
     __device__ bool nothing_to_do(int, int) const { return false; }
 };
 
@@ -325,7 +346,7 @@ struct RaggedSizes {
 template <bool PACKED, class Sizes>
 __global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ proto, const float* __restrict__ coefs,
                                                       const float* __restrict__ boxes, const int32_t* __restrict__ counts,
-                                                      int max_det, int Hp, int Wp, const Sizes sz, int do_crop,
+                                                      int max_det, int Hp, int Wp, int Pv, const Sizes sz, int do_crop,
                                                       typename mask_elem<PACKED>::type* __restrict__ out) {
     __shared__ float patch[FP_H * FP_W];
     __shared__ __attribute__((aligned(16))) float cf[32];
@@ -335,8 +356,8 @@ __global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ p
     const int n = counts ? counts[b] : max_det;
     if (d >= n) return;
     const size_t slot = (size_t)b * max_det + d;
-    fused_tile<PACKED>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, img_h, img_w,
-                       do_crop, out + sz.template base<PACKED>(b, max_det, d));
+    fused_tile<PACKED>(patch, cf, proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, blockIdx.x, Hp, Wp, Pv, img_h,
+                       img_w, do_crop, out + sz.template base<PACKED>(b, max_det, d));
 }
 
 // dense {0, nonzero} rows -> words.  A wave takes PK consecutive words of the flat [rows][wq] output (PK row pieces of 64 pixels in
@@ -407,8 +428,9 @@ __global__ void k_boxes_to_pixels_batch(float* boxes, int32_t* px, int per_image
 
 }  // namespace
 
-extern "C" int ym_mask_assemble(const float* proto, const float* coefs, const float* boxes, int n, int Hp, int Wp, int K,
-                                int do_crop, float* out, ym_stream_t s) {
+// n soft masks of one image; Pv as in proto_geom (ym_mask_assemble: 0)
+static int mask_assemble(const float* proto, const float* coefs, const float* boxes, int n, int Hp, int Wp, int Pv, int K, int do_crop,
+                         float* out, ym_stream_t s) {
     YM_REQUIRE(K == 32, "mask_assemble: coefficient dim must be 32, got %d", K);
     YM_REQUIRE(n >= 0 && Hp > 0 && Wp > 0, "mask_assemble: bad shape");
     if (n == 0) return YM_OK;
@@ -416,18 +438,23 @@ extern "C" int ym_mask_assemble(const float* proto, const float* coefs, const fl
     const int P = Hp * Wp;
     const int waves = ym_cdiv(P, 32);
     hipLaunchKernelGGL(k_mask_assemble, dim3(ym_cdiv(waves, 4)), dim3(256), 0, (hipStream_t)s, proto, coefs, boxes, n, Hp,
-                       Wp, do_crop, out);
+                       Wp, Pv, do_crop, out);
     return ym_check_launch("mask_assemble");
+}
+
+extern "C" int ym_mask_assemble(const float* proto, const float* coefs, const float* boxes, int n, int Hp, int Wp, int K,
+                                int do_crop, float* out, ym_stream_t s) {
+    return mask_assemble(proto, coefs, boxes, n, Hp, Wp, 0, K, do_crop, out, s);
 }
 
 // n soft masks (the device count, when given, bounds n) -> img_h x img_w binary masks, dense or packed
 template <bool PACKED>
-static void launch_resize(const float* masks, const int32_t* count, int n, int Hp, int Wp, int img_h, int img_w,
+static void launch_resize(const float* masks, const int32_t* count, int n, int Hp, int Wp, int Pv, int img_h, int img_w,
                           typename mask_elem<PACKED>::type* out, hipStream_t st) {
     const size_t items = PACKED ? ((size_t)n * img_h * ym_cdiv(img_w, 64) + 3) / 4       // a wave per word
                                 : ((size_t)n * img_h * ((img_w + 3) / 4) + 255) / 256;   // a thread per 4 pixels
     hipLaunchKernelGGL(k_mask_resize<PACKED>, dim3((int)(items > 16384 ? 16384 : items)), dim3(256), 0, st, masks, count, n, Hp, Wp,
-                       img_h, img_w, out);
+                       Pv, img_h, img_w, out);
 }
 
 extern "C" int ym_mask_resize_binarize(const float* masks, int n, int Hp, int Wp, int img_h, int img_w, float* out,
@@ -435,7 +462,7 @@ extern "C" int ym_mask_resize_binarize(const float* masks, int n, int Hp, int Wp
     YM_REQUIRE(n >= 0 && Hp > 0 && Wp > 0 && img_h > 0 && img_w > 0, "mask_resize: bad shape");
     if (n == 0) return YM_OK;
     YM_REQUIRE(masks && out, "mask_resize: null pointer");
-    launch_resize<false>(masks, nullptr, n, Hp, Wp, img_h, img_w, out, (hipStream_t)s);
+    launch_resize<false>(masks, nullptr, n, Hp, Wp, 0, img_h, img_w, out, (hipStream_t)s);
     return ym_check_launch("mask_resize");
 }
 
@@ -453,24 +480,25 @@ extern "C" int ym_boxes_to_pixels(float* boxes_f, int32_t* boxes_px, int n, floa
 // written (all max_det without counts): the fused kernel's slots past the count exit, and the resize reads the count on the device.
 template <bool PACKED, class Sizes>
 static int after_nms_launches(const char* what, const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B,
-                              int max_det, int Hp, int Wp, int K, const Sizes& sz, int do_crop, typename mask_elem<PACKED>::type* masks,
-                              int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+                              int max_det, int Hp, int Wp, int Pv, int K, const Sizes& sz, int do_crop,
+                              typename mask_elem<PACKED>::type* masks, int32_t* boxes_px, void* workspace, size_t workspace_bytes,
+                              ym_stream_t s) {
     hipStream_t st = (hipStream_t)s;
     int tiles = 0;
     for (int b = 0; b < B; ++b)
         if (sz.fused(b, Hp, Wp)) tiles = std::max(tiles, fused_tiles(sz.h(b), sz.w(b)));
     if (tiles)
         hipLaunchKernelGGL((k_masks_fused<PACKED, Sizes>), dim3(tiles, max_det, B), dim3(256), 0, st, proto, coefs, boxes, counts, max_det,
-                           Hp, Wp, sz, do_crop, masks);
+                           Hp, Wp, Pv, sz, do_crop, masks);
     for (int b = 0; b < B; ++b) {
         if (sz.fused(b, Hp, Wp)) continue;
         const size_t soft_bytes = (size_t)max_det * Hp * Wp * sizeof(float);
         if (!workspace || workspace_bytes < soft_bytes) { ym_set_error("%s: workspace %zu B < %zu B", what, workspace_bytes, soft_bytes); return YM_ENOSPC; }
         const size_t slot = (size_t)b * max_det;
-        const int rc = ym_mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, K, do_crop,
-                                        (float*)workspace, s);
+        const int rc = mask_assemble(proto + (size_t)b * Hp * Wp * 32, coefs + slot * 32, boxes + slot * 4, max_det, Hp, Wp, Pv, K, do_crop,
+                                     (float*)workspace, s);
         if (rc != YM_OK) return rc;
-        launch_resize<PACKED>((const float*)workspace, counts ? counts + b : nullptr, max_det, Hp, Wp, sz.h(b), sz.w(b),
+        launch_resize<PACKED>((const float*)workspace, counts ? counts + b : nullptr, max_det, Hp, Wp, Pv, sz.h(b), sz.w(b),
                               masks + sz.template base<PACKED>(b, max_det), st);
     }
     hipLaunchKernelGGL(k_boxes_to_pixels_batch<Sizes>, dim3(ym_cdiv(max_det * 4, 256), B), dim3(256), 0, st, boxes, boxes_px, max_det * 4, sz);
@@ -478,7 +506,7 @@ static int after_nms_launches(const char* what, const float* proto, const float*
 }
 
 extern "C" size_t ym_after_nms_batch_workspace_bytes(int max_det, int Hp, int Wp, int img_h, int img_w) {
-    return fused_fits(Hp, Wp, img_h, img_w) ? 0 : (size_t)max_det * Hp * Wp * sizeof(float);
+    return fused_fits(Hp, Wp, 0, img_h, img_w) ? 0 : (size_t)max_det * Hp * Wp * sizeof(float);
 }
 
 extern "C" int ym_after_nms_batch(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
@@ -487,7 +515,7 @@ extern "C" int ym_after_nms_batch(const float* proto, const float* coefs, float*
     YM_REQUIRE(K == 32, "after_nms: coefficient dim must be 32, got %d", K);
     YM_REQUIRE(B >= 1 && B <= 65535 && max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0 && img_h > 0 && img_w > 0, "after_nms: bad shape");
     YM_REQUIRE(proto && coefs && boxes && masks && boxes_px, "after_nms: null pointer");
-    return after_nms_launches<false>("after_nms", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, UniformSizes{{img_h, img_w}}, do_crop, masks,
+    return after_nms_launches<false>("after_nms", proto, coefs, boxes, counts, B, max_det, Hp, Wp, 0, K, UniformSizes{{img_h, img_w}}, do_crop, masks,
                                      boxes_px, workspace, workspace_bytes, s);
 }
 
@@ -497,58 +525,82 @@ extern "C" int ym_after_nms_batch_packed(const float* proto, const float* coefs,
     YM_REQUIRE(K == 32, "after_nms_packed: coefficient dim must be 32, got %d", K);
     YM_REQUIRE(B >= 1 && B <= 65535 && max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0 && img_h > 0 && img_w > 0, "after_nms_packed: bad shape");
     YM_REQUIRE(proto && coefs && boxes && mask_bits && boxes_px, "after_nms_packed: null pointer");
-    return after_nms_launches<true>("after_nms_packed", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, UniformSizes{{img_h, img_w}}, do_crop,
+    return after_nms_launches<true>("after_nms_packed", proto, coefs, boxes, counts, B, max_det, Hp, Wp, 0, K, UniformSizes{{img_h, img_w}}, do_crop,
                                     reinterpret_cast<unsigned long long*>(mask_bits), boxes_px, workspace, workspace_bytes, s);
 }
 
 // ---- batches whose images differ in size -----------------------------------------------------------------------------------------
 // Checks the shape and the table; *fused = bit b set when image b takes the fused kernel.
-static int ragged_check(const char* what, const ym_ragged_image* images, int B, int max_det, int Hp, int Wp, bool packed, unsigned* fused) {
+static int ragged_check(const char* what, const ym_ragged_image* images, int B, int max_det, int Hp, int Wp, int Pv, bool packed,
+                        unsigned* fused) {
     YM_REQUIRE(max_det >= 1 && max_det <= 65535 && Hp > 0 && Wp > 0, "%s: bad shape", what);
+    YM_REQUIRE(Pv == 0 || (Pv >= Hp && Pv >= Wp), "%s: the %d x %d prototype map is not inside the virtual extent %d", what, Hp, Wp, Pv);
     const int rc = ym_check_ragged_table(what, images, B, packed ? 8 : 4, [=](const ym_ragged_image& im) {
         return (int64_t)max_det * im.img_h * (int64_t)ym_mask_row(packed, im.img_w);
     });
     if (rc != YM_OK) return rc;
     *fused = 0u;
     for (int b = 0; b < B; ++b)
-        if (fused_fits(Hp, Wp, images[b].img_h, images[b].img_w)) *fused |= 1u << b;
+        if (fused_fits(Hp, Wp, Pv, images[b].img_h, images[b].img_w)) *fused |= 1u << b;
     return YM_OK;
 }
 
-extern "C" size_t ym_after_nms_ragged_workspace_bytes(const ym_ragged_image* images, int B, int max_det, int Hp, int Wp) {
-    if (!images || B < 1 || B > YM_RAGGED_MAX_IMAGES || max_det < 1 || Hp <= 0 || Wp <= 0) return 0;
+extern "C" size_t ym_after_nms_window_workspace_bytes(const ym_ragged_image* images, int B, int max_det, int Hp, int Wp, int Pv) {
+    if (!images || B < 1 || B > YM_RAGGED_MAX_IMAGES || max_det < 1 || Hp <= 0 || Wp <= 0 || Pv < 0) return 0;
     for (int b = 0; b < B; ++b)
-        if (images[b].img_h > 0 && images[b].img_w > 0 && !fused_fits(Hp, Wp, images[b].img_h, images[b].img_w))
+        if (images[b].img_h > 0 && images[b].img_w > 0 && !fused_fits(Hp, Wp, Pv, images[b].img_h, images[b].img_w))
             return (size_t)max_det * Hp * Wp * sizeof(float);
     return 0;
 }
 
+extern "C" size_t ym_after_nms_ragged_workspace_bytes(const ym_ragged_image* images, int B, int max_det, int Hp, int Wp) {
+    return ym_after_nms_window_workspace_bytes(images, B, max_det, Hp, Wp, 0);
+}
+
 template <bool PACKED>
 static int after_nms_ragged(const char* what, const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
-                            int Hp, int Wp, int K, const ym_ragged_image* images, int do_crop, typename mask_elem<PACKED>::type* masks,
-                            int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+                            int Hp, int Wp, int Pv, int K, const ym_ragged_image* images, int do_crop,
+                            typename mask_elem<PACKED>::type* masks, int32_t* boxes_px, void* workspace, size_t workspace_bytes,
+                            ym_stream_t s) {
     YM_REQUIRE(K == 32, "%s: coefficient dim must be 32, got %d", what, K);
     RaggedSizes sz = {};
-    const int rc = ragged_check(what, images, B, max_det, Hp, Wp, PACKED, &sz.fused_bits);
+    const int rc = ragged_check(what, images, B, max_det, Hp, Wp, Pv, PACKED, &sz.fused_bits);
     if (rc != YM_OK) return rc;
     YM_REQUIRE(proto && coefs && boxes && masks && boxes_px, "%s: null pointer", what);
     YM_REQUIRE(((uintptr_t)masks & 15) == 0, "%s: the mask buffer must be 16-byte aligned", what);
     std::copy(images, images + B, sz.tab.img);
-    return after_nms_launches<PACKED>(what, proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, sz, do_crop, masks, boxes_px, workspace,
+    return after_nms_launches<PACKED>(what, proto, coefs, boxes, counts, B, max_det, Hp, Wp, Pv, K, sz, do_crop, masks, boxes_px, workspace,
                                       workspace_bytes, s);
 }
 
 extern "C" int ym_after_nms_ragged(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
                                    int Wp, int K, const ym_ragged_image* images, int do_crop, float* masks, int32_t* boxes_px,
                                    void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    return after_nms_ragged<false>("after_nms_ragged", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, images, do_crop, masks, boxes_px,
+    return after_nms_ragged<false>("after_nms_ragged", proto, coefs, boxes, counts, B, max_det, Hp, Wp, 0, K, images, do_crop, masks, boxes_px,
                                    workspace, workspace_bytes, s);
 }
 
 extern "C" int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
                                           int Hp, int Wp, int K, const ym_ragged_image* images, int do_crop, uint64_t* mask_bits,
                                           int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
-    return after_nms_ragged<true>("after_nms_ragged_packed", proto, coefs, boxes, counts, B, max_det, Hp, Wp, K, images, do_crop,
+    return after_nms_ragged<true>("after_nms_ragged_packed", proto, coefs, boxes, counts, B, max_det, Hp, Wp, 0, K, images, do_crop,
+                                  reinterpret_cast<unsigned long long*>(mask_bits), boxes_px, workspace, workspace_bytes, s);
+}
+
+// ---- window mode: the ragged entries with the virtual extent (one image size is the one-entry table) ---------------------------------
+extern "C" int ym_after_nms_window(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
+                                   int Wp, int K, const ym_ragged_image* images, int Pv, int do_crop, float* masks, int32_t* boxes_px,
+                                   void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    YM_REQUIRE(Pv > 0, "after_nms_window: virtual prototype extent %d", Pv);
+    return after_nms_ragged<false>("after_nms_window", proto, coefs, boxes, counts, B, max_det, Hp, Wp, Pv, K, images, do_crop, masks, boxes_px,
+                                   workspace, workspace_bytes, s);
+}
+
+extern "C" int ym_after_nms_window_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det,
+                                          int Hp, int Wp, int K, const ym_ragged_image* images, int Pv, int do_crop, uint64_t* mask_bits,
+                                          int32_t* boxes_px, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    YM_REQUIRE(Pv > 0, "after_nms_window_packed: virtual prototype extent %d", Pv);
+    return after_nms_ragged<true>("after_nms_window_packed", proto, coefs, boxes, counts, B, max_det, Hp, Wp, Pv, K, images, do_crop,
                                   reinterpret_cast<unsigned long long*>(mask_bits), boxes_px, workspace, workspace_bytes, s);
 }
 

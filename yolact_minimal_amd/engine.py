@@ -462,7 +462,11 @@ class InferEngine:
         hd = net.prediction_layers
         nc, cd, na = self.num_classes, self.coef_dim, self.na
         n_total = sum(lv.shape[1] * lv.shape[2] * na for lv in levels)
-        assert n_total * 4 == len(net.anchors) or not isinstance(net.anchors, list), 'anchor count mismatch'
+        if self.H == self.W:
+            assert n_total * 4 == len(net.anchors) or not isinstance(net.anchors, list), 'anchor count mismatch'
+        else:       # a window of the square input (utils/rect.py): its anchors are net.anchors_for(H, W), one per prediction row
+            from .utils.rect import rect_level_shapes
+            assert shapes == rect_level_shapes(self.H, self.W), 'level shapes of a rectangular input'
         self.n_anchors = n_total
         self.class_logits = self._buf(B, n_total, nc)
         self.class_pred = self._buf(B, n_total, nc)

@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     'ym_val_preprocess_batch', 'ym_draw_detections_ragged', 'ym_draw_detections_ragged_packed',
     'ym_sizeof_aug_item', 'ym_train_aug_image_batch', 'ym_train_aug_masks_batch',
     'ym_ann_to_mask_ragged_workspace_bytes', 'ym_ann_to_mask_ragged',
+    'ym_val_preprocess_window', 'ym_after_nms_window_workspace_bytes', 'ym_after_nms_window', 'ym_after_nms_window_packed',
 )
 
 
@@ -299,6 +300,12 @@ def lib():
         L.ym_after_nms_ragged_packed.argtypes = L.ym_after_nms_ragged.argtypes
         L.ym_val_preprocess_batch.argtypes = [vp, i32, ctypes.POINTER(RaggedImage), i32, i32, ctypes.POINTER(ctypes.c_float),
                                               ctypes.POINTER(ctypes.c_float), vp, vp]
+        L.ym_val_preprocess_window.argtypes = [vp, i32, ctypes.POINTER(RaggedImage), i32, i32, i32, i32, ctypes.POINTER(ctypes.c_float),
+                                               ctypes.POINTER(ctypes.c_float), vp, vp]
+        L.ym_after_nms_window_workspace_bytes.argtypes = [ctypes.POINTER(RaggedImage), i32, i32, i32, i32, i32]
+        L.ym_after_nms_window_workspace_bytes.restype = sz
+        L.ym_after_nms_window.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(RaggedImage), i32, i32, vp, vp, vp, sz, vp]
+        L.ym_after_nms_window_packed.argtypes = L.ym_after_nms_window.argtypes
         L.ym_draw_detections_ragged.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(RaggedImage), ctypes.POINTER(RaggedImage),
                                                 vp, i32, i32, vp, i32, vp, i32, f32, ctypes.c_char_p, vp, vp, sz, vp]
         L.ym_draw_detections_ragged_packed.argtypes = L.ym_draw_detections_ragged.argtypes
@@ -328,7 +335,7 @@ def lib():
                             'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes',
                             'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes',
                             'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes',
-                            'ym_ann_to_mask_ragged_workspace_bytes'):
+                            'ym_ann_to_mask_ragged_workspace_bytes', 'ym_after_nms_window_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

@@ -108,10 +108,26 @@ class Yolact(nn.Module):
                     module.bias.data.zero_()
 
         self._engines = {}
+        self._rect_anchors = {}
         self._weights_epoch = 0
         self._train_state = None          # train_state.ModuleTrainState, created at the first train-mode forward on the GPU
         self._ddp_wrapped = False
         self._ddp_wrapper = None
+
+    def anchors_for(self, height, width, device=None):
+        """The anchors of an eval forward on a `height x width` WINDOW of the square input (utils/rect.py): the rows of the square
+        list that `rect_anchor_index` keeps, float32 `[N_rect, 4]`, cached per shape and device.  The VALUES are the square list's
+        (centres (i + .5) / n_l with the square n_l, extents scale / img_size): a window's predictions live in the square's frame.
+        `self.anchors` itself is untouched; a square window returns all of it."""
+        from ..utils.rect import rect_anchor_index
+        dev = torch.device(device) if device is not None else torch.device('cpu')
+        key = (int(height), int(width), str(dev))
+        hit = self._rect_anchors.get(key)
+        if hit is None:
+            idx = rect_anchor_index(self.cfg, height, width)
+            full = self.anchors if torch.is_tensor(self.anchors) else torch.tensor(self.anchors, dtype=torch.float32)
+            hit = self._rect_anchors[key] = full.detach().reshape(-1, 4).to('cpu', torch.float32)[idx].contiguous().to(dev)
+        return hit
 
     # ---- torch.nn.parallel.DistributedDataParallel around this module (reference train.py:76) ------------------------------------
     @property

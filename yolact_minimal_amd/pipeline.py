@@ -13,6 +13,10 @@ With batch > 1 a request may give every image its own output size (`submit(out_h
 sizes, one launch set, the size table in the kernel arguments, so nothing is copied or synchronised per request).
 `submit_frames(FrameBatch)` is the whole request for frames of different sizes: uint8 frames in (`val_aug_batch` on the slot's
 stream), and with `draw=True` drawn uint8 frames of those sizes out (the ragged `draw_batch`), no host read in between.
+`RequestPipeline(net, cfg, height, width, ...)` with `height != width` serves in WINDOW mode (utils/rect.py): the network runs on the
+top-left `height x width` of its square input only -- the anchors are `net.anchors_for(height, width)`, `after_nms_batch` gets
+`window=True`, `submit_frames` pre-processes into the window and refuses frames whose picture does not fit it;
+`RequestPipeline.for_frames` picks the window from the frame sizes.  Opt-in, not a parity path; `height == width` is untouched.
 
 Measured mid-round 3 (res101_coco 544 px, MI355X, forward + nms + after_nms(480x640)): depth 1: 325 img/s, 2: 468, 3: 545, 4: 594, 5: 495,
 8: 479; with round 4's kernels 3: 580, 4: 603-617, 5: 499, 6: 527 -- the part schedules four compute pipes; GPU_MAX_HW_QUEUES must be >= depth + 1 (ROCm multiplexes HIP streams onto 4
@@ -29,6 +33,7 @@ from .utils.augmentations import val_aug_batch
 from .utils.draw import draw_batch
 from .utils.frames import FrameBatch
 from .utils.output_utils import nms_batch, after_nms_batch, unpad_detections
+from .utils.rect import rect_window
 
 _streams = {}
 
@@ -88,11 +93,22 @@ class RequestPipeline:
         self.latencies_ms = []
         self.pending = [None] * depth
         self.frame_inputs = [None] * depth              # submit_frames: a slot's input before its engine's graph exists
-        self.anchors = torch.tensor(net.anchors, dtype=torch.float32).reshape(-1, 4).to(device) \
-            if not torch.is_tensor(net.anchors) else net.anchors.to(device)
+        self.window = (int(height), int(width)) if int(height) != int(width) else None
+        if self.window is not None:
+            self.anchors = net.anchors_for(height, width, device)
+        else:
+            self.anchors = torch.tensor(net.anchors, dtype=torch.float32).reshape(-1, 4).to(device) \
+                if not torch.is_tensor(net.anchors) else net.anchors.to(device)
         self.vt = float(getattr(cfg, 'visual_thre', 0) or 0)
         self.submitted = 0
         self.detections = 0
+
+    @classmethod
+    def for_frames(cls, net, cfg, frame_hw, device, **kwargs):
+        """A pipeline whose network input is the window of the frame sizes `frame_hw` = [(h, w), ...] (or one pair):
+        `rect_window(frame_hw, cfg.img_size)`.  Square frames, or landscape and portrait together, give the square pipeline."""
+        height, width = rect_window(frame_hw, cfg.img_size)
+        return cls(net, cfg, height, width, device, **kwargs)
 
     def warm_up(self, img, head_outputs=None, rounds=4):
         """Capture every slot's hipGraph (first run of an engine) and push `rounds` requests through every slot, outside any timed
@@ -204,13 +220,13 @@ class RequestPipeline:
                 # straight into the buffer the engine's graph reads (its `copy_` of a tensor onto itself is then a no-op); before
                 # the graph exists, into a buffer of the slot's own
                 buf = eng.static_img if getattr(eng, 'graph', None) is not None else self._frame_input(slot)
-                img = val_aug_batch(frames, eng.H, out=buf)
+                img = val_aug_batch(frames, self.cfg.img_size if self.window else eng.H, out=buf, window=self.window)
                 frames.record_stream(self.streams[slot])       # the caller may drop `frames` while the slot still reads them
             eng.run(img)
             if self.with_post:
                 cls, box, coef, proto = head_outputs if head_outputs is not None else eng.outputs()
                 r = after_nms_batch(nms_batch(cls, box, coef, proto, self.anchors, self.cfg), out_h, out_w, self.cfg,
-                                    sync=False, packed=self.packed_masks)
+                                    sync=False, packed=self.packed_masks, window=self.window is not None)
                 if consumer is None:
                     self.counts_host[slot].copy_(r[4], non_blocking=True)
                 else:
@@ -260,9 +276,11 @@ class RequestPipeline:
                                'host; a consumer would be handed the unfiltered rows')
         if self.device.index is not None and frames.device != self.device:
             raise RuntimeError(f'RequestPipeline.submit_frames: frames on {frames.device}, pipeline on {self.device}')
-        eng = self.engines[0]
-        if eng.H != eng.W:
-            raise RuntimeError(f'RequestPipeline.submit_frames: val_aug makes square inputs, the pipeline was built for {eng.H} x {eng.W}')
+        if self.window is not None:
+            need = rect_window(frames.sizes, self.cfg.img_size)
+            if need[0] > self.window[0] or need[1] > self.window[1]:
+                raise RuntimeError(f'RequestPipeline.submit_frames: frames {frames.sizes} need a {need[0]} x {need[1]} window at '
+                                   f'{self.cfg.img_size} px, the pipeline was built for {self.window[0]} x {self.window[1]}')
         if draw:
             cfg = self.cfg
 

@@ -20,13 +20,33 @@ _MEAN = (ctypes.c_float * 3)(*[float(v) for v in norm_mean])
 _STD = (ctypes.c_float * 3)(*[float(v) for v in norm_std])
 
 
-def val_aug(img, val_size):
+def _window(window, val_size, what):
+    """`window=None` -> the square; else `(Hn, Wn)` inside it."""
+    if window is None:
+        return None
+    hn, wn = int(window[0]), int(window[1])
+    if not (0 < hn <= val_size and 0 < wn <= val_size):
+        raise RuntimeError(f'{what}: window {hn} x {wn} is not inside {val_size} x {val_size}')
+    return hn, wn
+
+
+def val_aug(img, val_size, window=None):
+    """`window=(Hn, Wn)`: only the top-left `Hn x Wn` of the `[3, S, S]` result, bit for bit (`ym_val_preprocess_window`, the same
+    kernel): the input of a rectangular forward (utils/rect.py).  `window=None`: the reference's square."""
     if not (torch.is_tensor(img) and img.is_cuda):
         raise RuntimeError('yolact_minimal_amd.utils.augmentations.val_aug expects a CUDA tensor (HWC, BGR)')
     if img.dtype not in (torch.uint8, torch.float32) or img.dim() != 3 or img.shape[2] != 3:
         raise RuntimeError('val_aug: image must be [H, W, 3] uint8 or float32')
     img = img.contiguous()
     h, w, _ = img.shape
+    window = _window(window, int(val_size), 'val_aug')
+    if window is not None:
+        out = torch.empty(3, *window, dtype=torch.float32, device=img.device)
+        with torch.cuda.device(img.device):
+            hip.check(hip.lib().ym_val_preprocess_window(ctypes.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8),
+                                                         hip.ragged_table([(h, w)], [0]), 1, int(val_size), *window, _MEAN, _STD,
+                                                         hip.ptr(out), hip.stream_ptr()), 'ym_val_preprocess_window')
+        return out
     out = torch.empty(3, val_size, val_size, dtype=torch.float32, device=img.device)
     with torch.cuda.device(img.device):
         hip.check(hip.lib().ym_val_preprocess(ctypes.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), h, w, val_size, _MEAN,
@@ -34,12 +54,13 @@ def val_aug(img, val_size):
     return out
 
 
-def val_aug_batch(frames, val_size, out=None):
+def val_aug_batch(frames, val_size, out=None, window=None):
     """`val_aug` for B frames of different sizes in ONE launch (`ym_val_preprocess_batch`) -> float32 `[B, 3, S, S]`.
     `frames`: a `FrameBatch` (utils/frames.py), or a list of device HWC BGR tensors (all uint8 or all float32), which is packed
     through `FrameBatch.from_tensors` first.  `out`: a contiguous float32 device tensor whose first B rows `[3, S, S]` are written
     (a pipeline slot's own input buffer); the result is then `out[:B]`.  Row b equals `val_aug(frame_b, val_size)` bit for bit: the
-    two entries are one kernel.  No host synchronisation."""
+    two entries are one kernel.  No host synchronisation.
+    `window=(Hn, Wn)`: rows are `[3, Hn, Wn]`, the top-left window of the square rows bit for bit (`ym_val_preprocess_window`)."""
     from .frames import FrameBatch
     val_size = int(val_size)
     if not isinstance(frames, FrameBatch):
@@ -48,11 +69,19 @@ def val_aug_batch(frames, val_size, out=None):
     batch = len(frames)
     if val_size < 1:
         raise RuntimeError(f'val_aug_batch: val_size = {val_size}')
+    window = _window(window, val_size, 'val_aug_batch')
+    hn, wn = window if window is not None else (val_size, val_size)
     if out is None:
-        out = torch.empty(batch, 3, val_size, val_size, dtype=torch.float32, device=frames.device)
+        out = torch.empty(batch, 3, hn, wn, dtype=torch.float32, device=frames.device)
     elif not torch.is_tensor(out) or not out.is_cuda or out.device != frames.device or out.dtype != torch.float32 or out.dim() != 4 or \
-            out.shape[0] < batch or tuple(out.shape[1:]) != (3, val_size, val_size) or not out.is_contiguous():
-        raise RuntimeError(f'val_aug_batch: out is a contiguous float32 [>= {batch}, 3, {val_size}, {val_size}] tensor on the device of the frames')
+            out.shape[0] < batch or tuple(out.shape[1:]) != (3, hn, wn) or not out.is_contiguous():
+        raise RuntimeError(f'val_aug_batch: out is a contiguous float32 [>= {batch}, 3, {hn}, {wn}] tensor on the device of the frames')
+    if window is not None:
+        with torch.cuda.device(frames.device):
+            hip.check(hip.lib().ym_val_preprocess_window(ctypes.c_void_p(frames.data.data_ptr()), int(frames.dtype == torch.uint8),
+                                                         frames.table(), batch, val_size, hn, wn, _MEAN, _STD, hip.ptr(out),
+                                                         hip.stream_ptr()), 'ym_val_preprocess_window')
+        return out[:batch]
     with torch.cuda.device(frames.device):
         hip.check(hip.lib().ym_val_preprocess_batch(ctypes.c_void_p(frames.data.data_ptr()), int(frames.dtype == torch.uint8),
                                                     frames.table(), batch, val_size, _MEAN, _STD, hip.ptr(out), hip.stream_ptr()),

@@ -11,6 +11,8 @@ Same call shapes and return conventions:
       (ids, scores, boxes int32[n,4] pixels, masks f32[n,img_h,img_w] in {0,1}) or four Nones;
       `box_p` is scaled IN PLACE like the reference (:230).  `packed=True` (or `cfg.packed_masks`): the fourth result is a
       `PackedMasks` (utils/packed_masks.py: 1 bit per pixel, written by the mask kernel itself; the float tensor never exists).
+      `window=True` (not in the reference; utils/rect.py): `proto_p` is the top-left `[Hp, Wp]` window of the square prototype map
+      of a rectangular forward, its virtual extent is `max(Hp, Wp)` on both axes (`ym_after_nms_window`).
 The only host<->device synchronisation is one 4-byte read of the detection count at the end of `nms`
 (the reference's boolean-mask gathers synchronise several times per call).
 
@@ -101,7 +103,7 @@ def _want_packed(cfg, packed):
     return bool(packed) or bool(cfg and getattr(cfg, 'packed_masks', False))
 
 
-def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, img_name=None, packed=False):
+def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, img_name=None, packed=False, window=False):
     if ids_p is None:
         return None, None, None, None
     packed = _want_packed(cfg, packed)
@@ -119,7 +121,14 @@ def after_nms(ids_p, class_p, box_p, coef_p, proto_p, img_h, img_w, cfg=None, im
 
     do_crop = not (cfg and getattr(cfg, 'no_crop', False))
     box_c = box_p if box_p.is_contiguous() else box_p.contiguous()
-    masks, box_px = _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, (img_h, img_w), do_crop, packed)
+    if window:
+        if not proto_p.is_cuda:
+            raise RuntimeError('yolact_minimal_amd.utils.output_utils.after_nms(window=True) needs CUDA (HIP) tensors; there is no CPU path.')
+        masks, box_px = _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, [(int(img_h), int(img_w))], do_crop, packed,
+                                          window=True)
+        masks = masks[0]
+    else:
+        masks, box_px = _after_nms_launch(proto_p.contiguous(), coef_p.contiguous(), box_c, None, (img_h, img_w), do_crop, packed)
     if box_c is not box_p:
         box_p.copy_(box_c)              # keep the reference's in-place scaling visible to the caller
     return ids_p, class_p, box_px, masks
@@ -129,30 +138,38 @@ _ragged_plans = {}
 _NO_SWITCH = contextlib.nullcontext()
 
 
-def _after_nms_launch(proto, coefs, boxes, counts, sizes, do_crop, packed):
+def _after_nms_launch(proto, coefs, boxes, counts, sizes, do_crop, packed, window=False):
     """The launch set behind `after_nms` and both arms of `after_nms_batch`: allocates and returns `(masks, box_px)` for the
     detections `coefs` [B, max_det, 32] / `boxes` (scaled in place) of `proto` [B, Hp, Wp, 32], or of ONE image without the
     leading B.  `sizes` is one `(h, w)` for every image -- the uniform entries, masks `[B, max_det, h, w]` (packed: the words
     `[B, max_det, h, ceil(w / 64)]`) -- or a LIST of B pairs -- `ym_after_nms_ragged[_packed]`, masks = a list of B views
-    `[max_det, h_b, w_b]` of one flat allocation (`ragged_layout`).  Packed masks come wrapped as `PackedMasks`."""
+    `[max_det, h_b, w_b]` of one flat allocation (`ragged_layout`).  Packed masks come wrapped as `PackedMasks`.
+    `window`: `proto` is the top-left window of a square map of side `Pv = max(Hp, Wp)` (utils/rect.py); always with a list of sizes
+    (`ym_after_nms_window[_packed]`: the ragged entries with the virtual extent, one size being the one-entry table)."""
     L = hip.lib()
     device = proto.device
     *lead, k = coefs.shape
     batch, md = lead if len(lead) == 2 else (1, lead[0])
     *_, hp, wp, _ = proto.shape
     ragged = isinstance(sizes, list)
+    pv = max(hp, wp) if window else 0
+    if window and not ragged:
+        raise RuntimeError('_after_nms_launch: window mode takes a list of sizes')
     if ragged:
-        key = (tuple(sizes), md, hp, wp, packed)
+        key = (tuple(sizes), md, hp, wp, packed, pv)
         plan = _ragged_plans.get(key)
         if plan is None:
             offsets, total = ragged_layout(sizes, md, packed)
             table = hip.ragged_table(sizes, offsets)
             if len(_ragged_plans) >= 1024:
                 _ragged_plans.clear()
-            plan = _ragged_plans[key] = (offsets, total, table, L.ym_after_nms_ragged_workspace_bytes(table, batch, md, hp, wp))
+            plan = _ragged_plans[key] = (offsets, total, table, L.ym_after_nms_window_workspace_bytes(table, batch, md, hp, wp, pv))
         offsets, total, table, nbytes = plan
-        shape, where = (total,), (table,)
-        fn, name = (L.ym_after_nms_ragged_packed if packed else L.ym_after_nms_ragged), 'ym_after_nms_ragged'
+        shape, where = (total,), ((table, pv) if window else (table,))
+        if window:
+            fn, name = (L.ym_after_nms_window_packed if packed else L.ym_after_nms_window), 'ym_after_nms_window'
+        else:
+            fn, name = (L.ym_after_nms_ragged_packed if packed else L.ym_after_nms_ragged), 'ym_after_nms_ragged'
     else:
         img_h, img_w = sizes
         nbytes = L.ym_after_nms_batch_workspace_bytes(md, hp, wp, img_h, img_w)
@@ -270,7 +287,7 @@ def ragged_layout(sizes, max_det, packed=False):
     return hip.aligned_layout('ragged_layout', sizes, 8 if packed else 4, lambda h, w: max_det * h * ((w + 63) // 64 if packed else w))
 
 
-def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
+def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False, window=False):
     """`after_nms` for every image of a `BatchDetections` in one launch set.  Returns a list of per-image 4-tuples like `after_nms`
     -- or, with `sync=False`, the padded device tensors (ids, scores, boxes_px, masks, counts) without any host read.
     `packed=True` (or `cfg.packed_masks`): the masks are `PackedMasks`.
@@ -278,9 +295,13 @@ def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
     `[B, max_det, img_h, img_w]` (packed: `[B, max_det, img_h, ceil(img_w / 64)]` words).
     Sequences of B heights and B widths: every image at its OWN size (`ym_after_nms_ragged`, also when the sizes are all equal);
     the padded `masks` is then a list of B per-image views `[max_det, h_b, w_b]` of one flat allocation (`ragged_layout`), each
-    what the consumers of one image's padded rows take (`DeviceAPData.add`, `rle_encode`, `draw_img`)."""
+    what the consumers of one image's padded rows take (`DeviceAPData.add`, `rle_encode`, `draw_img`).
+    `window=True`: `dets.proto` is the `[B, Hp, Wp, 32]` window of a rectangular forward (utils/rect.py; `ym_after_nms_window`).  The
+    window entries take the size table, so ints `img_h`, `img_w` mean B entries of that size and `masks` is the list of views."""
     packed = _want_packed(cfg, packed)
     batch, md = dets.ids.shape
+    if window and not hasattr(img_h, '__len__') and not hasattr(img_w, '__len__'):
+        img_h, img_w = [int(img_h)] * batch, [int(img_w)] * batch
     do_crop = not (cfg and getattr(cfg, 'no_crop', False))
     if cfg and getattr(cfg, 'save_lincomb', False):
         raise NotImplementedError('draw_lincomb (visualisation, reference output_utils.py:276-324) is out of scope')
@@ -293,7 +314,7 @@ def after_nms_batch(dets, img_h, img_w, cfg=None, sync=True, packed=False):
             raise RuntimeError('yolact_minimal_amd.utils.output_utils.after_nms_batch needs CUDA (HIP) tensors; there is no CPU path.')
     else:
         sizes = (img_h, img_w)
-    masks, box_px = _after_nms_launch(dets.proto.contiguous(), dets.coefs, dets.boxes, dets.counts, sizes, do_crop, packed)
+    masks, box_px = _after_nms_launch(dets.proto.contiguous(), dets.coefs, dets.boxes, dets.counts, sizes, do_crop, packed, window=bool(window))
     if not sync:
         return dets.ids, dets.scores, box_px, masks, dets.counts
     vt = float(getattr(cfg, 'visual_thre', 0) or 0) if cfg else 0.0
