@@ -241,6 +241,13 @@ size_t ym_sizeof_aug_item(void);                       /* for bindings: must equ
 int ym_train_aug_image_batch(const ym_aug_item* items, int B, int S, int is_u8, float* out, ym_stream_t s);
 int ym_train_aug_masks_batch(const ym_aug_item* items, int B, int S, int is_u8, const int32_t* keep_dev, int total_k, float* out,
                              ym_stream_t s);
+/* Window training (utils/rect.py): only the top-left Hn x Wn WINDOW of every S x S sample, out [B][3][Hn][Wn] / [total_k][Hn][Wn],
+ * grid = ceil(Hn * Wn / 256) x samples / rows.  The same two kernels: a pixel's arithmetic depends on its coordinates in the square
+ * only, so the rows equal the square result's [:Hn, :Wn] bit for bit, and the entries above are the Hn = Wn = S case.  Plans and
+ * items are unchanged (plan.S == S).  YM_EINVAL before any launch as above, and for a window outside 1 .. S on either axis. */
+int ym_train_aug_image_batch_window(const ym_aug_item* items, int B, int S, int Hn, int Wn, int is_u8, float* out, ym_stream_t s);
+int ym_train_aug_masks_batch_window(const ym_aug_item* items, int B, int S, int Hn, int Wn, int is_u8, const int32_t* keep_dev,
+                                    int total_k, float* out, ym_stream_t s);
 
 /* ---- evaluation inner products right after after_nms (next row f2) -----------------------------------------------
  * mask_iou (utils/box_utils.py:189-200): masks_a [n][P], masks_b [g][P] fp32 in {0,1} (P = img_h*img_w < 2^24) ->
@@ -444,6 +451,17 @@ size_t ym_mask_loss_batch_workspace_bytes(int B);
 /* total_pos_dev: NULL, or a device int32 by which gscale is divided (gscale = mask_alpha / Hp / Wp then). */
 int ym_mask_loss_batch(const ym_mask_loss_item* items, int B, int Hp, int Wp, float gscale, const int32_t* total_pos_dev,
                        double* loss_accum, void* workspace, size_t workspace_bytes, ym_stream_t s);
+/* Window training: the prototype map is the top-left Hp x Wp of a VIRTUAL Pv x Pv map (Pv >= Hp, Wp) and the boxes live in that
+ * square's frame.  The crop window of a positive is box * Pv on both axes with the reference's padding of 1, clamped to the
+ * physical map: rows >= Hp and columns >= Wp do not exist, contribute nothing and are never read.  1 / area uses the box as it
+ * is; the caller's gscale carries mask_alpha / Pv / Pv.  Hp * Wp need not be a multiple of the 32-pixel tile.  Pv = 0: per-axis
+ * extents -- the two entries above are that instance of the same kernels and return the same bits.  YM_EINVAL for 0 < Pv < Hp or Wp. */
+int ym_mask_loss_batch_window(const ym_mask_loss_item* items, int B, int Hp, int Wp, int Pv, float gscale,
+                              const int32_t* total_pos_dev, double* loss_accum, void* workspace, size_t workspace_bytes, ym_stream_t s);
+int ym_mask_loss_fwd_bwd_window(const float* proto, const float* coef_pos, const float* box_pos, const int32_t* gt_idx,
+                                const float* gt_masks_ds, const int64_t* anchor_idx, int n, int Hp, int Wp, int Pv, float wscale,
+                                float gscale, double* loss_accum, float* dproto, float* dcoef_full, void* workspace,
+                                size_t workspace_bytes, ym_stream_t s);
 
 /* match() for ONE image (utils/box_utils.py:57-83, encode :104-114): gt_boxes_cls [g][5] = (x1,y1,x2,y2,class) in [0,1]
  * coordinates, anchors [N][4] (cx,cy,w,h).  Writes offsets [N][4], conf [N] int64 (class+1 / 0 background / -1 neutral),

@@ -13,6 +13,10 @@ pixels.  Everything is seeded.
     python tools/overfit_demo.py --steps 1500            # prints the loss every 100 steps and the final mAP table (JSON last)
     YM_DIST_BACKEND=gloo python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 tools/overfit_demo.py --size 128 \
         --steps 600                                      # two ranks of 4 pictures each (sharing one GPU), rank 0 scores
+    python tools/overfit_demo.py --size 128 --steps 600 --window 96 128     # window training: the pictures cut to 96 x 128, trained on
+                                                         # [B, 3, 96, 128] and scored through the window path
+    python tools/overfit_demo.py --size 128 --steps 600 --window 96 128 --window-recipe square   # the yardstick: the same cut
+                                                         # pictures zero-padded to the square, trained and scored as squares
 """
 import argparse
 import json
@@ -65,6 +69,70 @@ def make_dataset(n_images, size, seed=0):
             img[:, m] = COLOURS[kind][:, None] + rng.normal(0.0, 0.1, (3, int(m.sum()))).astype(np.float32)
         data.append((torch.from_numpy(img), torch.tensor(gts, dtype=torch.float32), torch.from_numpy(np.stack(masks))))
     return data
+
+
+def cut_dataset(data, size, window):
+    """The pictures and their ground truth cut to the top-left `window = (Hn, Wn)`: boxes are re-taken from the cut masks, instances
+    without pixels are dropped, pictures without instances too.  Returns [(image [3, Hn, Wn], train gt [n, 5] in 0..1 of the `size`
+    square (what window training takes), masks [n, Hn, Wn], eval gt [n, 5] in 0..1 of the cut picture (what `prep_metrics` takes))]."""
+    hn, wn = window
+    out = []
+    for img, gt, masks in data:
+        m = masks[:, :hn, :wn]
+        keep = m.flatten(1).sum(1) > 0
+        if not bool(keep.any()):
+            continue
+        m, cls = m[keep].contiguous(), gt[keep, 4]
+        px = []
+        for one in m:
+            ys, xs = torch.nonzero(one, as_tuple=True)
+            px.append([xs.min().item(), ys.min().item(), xs.max().item() + 1, ys.max().item() + 1])
+        px = torch.tensor(px, dtype=torch.float32).reshape(-1, 4)
+        train_gt = torch.cat([px / size, cls.reshape(-1, 1)], 1)
+        eval_gt = torch.cat([px / torch.tensor([wn, hn, wn, hn], dtype=torch.float32), cls.reshape(-1, 1)], 1)
+        out.append((img[:, :hn, :wn].contiguous(), train_gt, m, eval_gt))
+    return out
+
+
+def pad_to_square(x, size):
+    """[..., Hn, Wn] -> [..., size, size], the window at the top-left, exactly 0.0 elsewhere (what the padding normalises to)."""
+    out = torch.zeros(*x.shape[:-2], size, size, dtype=x.dtype, device=x.device)
+    out[..., :x.shape[-2], :x.shape[-1]] = x
+    return out
+
+
+def evaluate_window(net, cfg, cut, device, size, window, path):
+    """`evaluate` on cut pictures (`cut_dataset`), masks at the cut picture's size.  `path` 'window': the `[1, 3, Hn, Wn]` picture
+    through `anchors_for` and `after_nms(window=True)`; 'square': the picture zero-padded to the square through the square calls."""
+    from yolact_minimal_amd.utils.common_utils import APDataObject, prep_metrics, calc_map
+    from yolact_minimal_amd.utils.output_utils import nms, after_nms
+    hn, wn = window
+    thres = [x / 100 for x in range(50, 100, 5)]
+    nc = len(cfg.class_names)
+    ap = {k: [[APDataObject() for _ in range(nc)] for _ in thres] for k in ('box', 'mask')}
+    net.eval()
+    found, strong = 0, 0
+    with torch.no_grad():
+        for img, _, masks, gt in cut:
+            x = img[None].to(device).contiguous()
+            if path == 'window':
+                out = net(x)
+                anchors = net.anchors_for(hn, wn, device)
+            else:
+                out = net(pad_to_square(x, size))
+                anchors = net.anchors
+            ids, sc, bx, cf, pr = nms(out[0], out[1], out[2], out[3], anchors, cfg)
+            ids, sc, boxes_p, masks_p = after_nms(ids, sc, bx, cf, pr, hn, wn, cfg, window=(path == 'window'))
+            if ids is None:
+                continue
+            found += 1
+            strong += int((sc > 0.3).sum())
+            prep_metrics(ap, list(ids.cpu().numpy().astype(int)), list(sc.cpu().numpy().astype(float)), boxes_p, masks_p,
+                         gt.clone().to(device), masks.to(device), hn, wn, thres)
+    table, row_box, row_mask = calc_map(ap, thres, nc, step=0)
+    net.train()
+    net._engines.clear()
+    return table, row_box, row_mask, found, strong
 
 
 def evaluate(net, cfg, data, device, size):
@@ -141,7 +209,12 @@ def state_digest(tr):
 
 
 def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', seed=0, lr=None, log=print, eval_every=0, log_every=100,
-        deterministic=False):
+        deterministic=False, window=None, window_recipe='window'):
+    """`window=(Hn, Wn)`: the pictures and their ground truth are cut to the top-left window (`cut_dataset`).  `window_recipe`
+    'window': training runs on `[B, 3, Hn, Wn]` (window training) and the detector is scored through the window path; 'square': the
+    same cut pictures zero-padded to `size x size`, trained and scored as squares (the existing recipe: the yardstick).  Either
+    way the result also carries the score of the other path (`paths`).  The window path scores frames whose longer side fills the
+    square: `max(Hn, Wn) == size`."""
     from yolact_minimal_amd.config import build_cfg
     from yolact_minimal_amd.modules.yolact import Yolact
     from yolact_minimal_amd.trainer import Trainer, init_distributed, shard_batch
@@ -160,9 +233,27 @@ def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', see
     if rank != 0:
         log = lambda *_: None                                                   # noqa: E731
     data = make_dataset(n_images, size, seed)
-    imgs = torch.stack([d[0] for d in data]).to(device)
-    gts = [d[1].to(device) for d in data]
-    mks = [d[2].to(device) for d in data]
+    cut = None
+    if window is not None:
+        window = (int(window[0]), int(window[1]))
+        if window_recipe not in ('window', 'square'):
+            raise ValueError(f"window_recipe is 'window' or 'square', got {window_recipe!r}")
+        if max(window) != size or min(window) < 32 or window[0] % 32 or window[1] % 32:
+            raise ValueError(f'--window {window[0]} {window[1]}: multiples of 32 with the longer side equal to --size {size}')
+        if world > 1:
+            raise ValueError('--window runs on one rank')
+        cut = cut_dataset(data, size, window)
+        n_images = len(cut)
+        if n_images < batch:
+            raise ValueError(f'only {n_images} pictures keep an instance inside the window, the batch is {batch}')
+        squared = window_recipe == 'square'
+        imgs = torch.stack([pad_to_square(d[0], size) if squared else d[0] for d in cut]).to(device)
+        gts = [d[1].to(device) for d in cut]
+        mks = [(pad_to_square(d[2], size) if squared else d[2]).to(device) for d in cut]
+    else:
+        imgs = torch.stack([d[0] for d in data]).to(device)
+        gts = [d[1].to(device) for d in data]
+        mks = [d[2].to(device) for d in data]
     order = np.random.default_rng(seed + 1)
     hist, curve = [], []
     t0 = time.time()
@@ -174,7 +265,8 @@ def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', see
             hist.append((step, vals))
             log(f'step {step:5d}  lr {tr.opt.lr:.5f}  loss c/b/m/s {vals}  total {sum(vals):.3f}')
         if eval_every and step and step % eval_every == 0:
-            _, rb, rm, _ = evaluate(net, cfg, data, device, size)
+            _, rb, rm = (evaluate(net, cfg, data, device, size) if cut is None else
+                         evaluate_window(net, cfg, cut, device, size, window, window_recipe))[:3]
             curve.append((step, rb[1], rm[1]))
             log(f'         box mAP {rb[1]}  mask mAP {rm[1]}')
     torch.cuda.synchronize()
@@ -191,6 +283,25 @@ def run(steps=1500, n_images=16, size=256, batch=8, cfg_name='res50_custom', see
             dist.barrier()                       # (rank 0 scores alone, like train.py:162-174)
             return None
     digest = state_digest(tr) if deterministic else None        # (before the evaluation: the trained state and nothing else)
+    if cut is not None:
+        paths = {}
+        for path in ('square', 'window'):
+            t, rb, rm, fnd, strong = evaluate_window(net, cfg, cut, device, size, window, path)
+            paths[path] = dict(box_map=rb[1:], mask_map=rm[1:], images_with_detections=fnd, detections_above_0p3=strong, table=t)
+        own = paths[window_recipe]
+        cfg.traditional_nms = True
+        _, trad_box, trad_mask = evaluate_window(net, cfg, cut, device, size, window, window_recipe)[:3]
+        cfg.traditional_nms = False
+        table = own['table']
+        for p in paths.values():
+            del p['table']
+        # (the serving comparison of the square demo is not run: `serving_path_identical_pictures` and `detections` are None)
+        return dict(cfg=cfg_name, size=size, images=n_images, batch=batch, steps=steps, train_s=round(train_s, 1), losses=hist,
+                    box_map=own['box_map'], mask_map=own['mask_map'], images_with_detections=own['images_with_detections'], curve=curve,
+                    table=table, serving_path_identical_pictures=None, detections=None, detections_above_0p3=own['detections_above_0p3'],
+                    world=world, replicas_identical=replicas_identical, box_map_traditional_nms=trad_box[1:],
+                    mask_map_traditional_nms=trad_mask[1:], window=list(window), window_recipe=window_recipe, paths=paths,
+                    **({'state_digest': digest} if deterministic else {}))
     table, row_box, row_mask, found = evaluate(net, cfg, data, device, size)
     strong = evaluate.detections_above_0p3
     # the same detector through `--traditional_nms` (greedy per-class NMS, utils/output_utils.py:84-123 + cython_nms.pyx)
@@ -220,9 +331,13 @@ def main():
     ap.add_argument('--log-every', type=int, default=100)
     ap.add_argument('--deterministic', action='store_true', help='ordered BatchNorm sums (train_engine._DETERMINISTIC): the result '
                     'carries a sha256 `state_digest` of the trained state that is the same from run to run')
+    ap.add_argument('--window', type=int, nargs=2, metavar=('HN', 'WN'), default=None, help='cut the pictures to their top-left '
+                    'HN x WN and train / score that window (window training); the longer side equals --size')
+    ap.add_argument('--window-recipe', choices=('window', 'square'), default='window', help="with --window: 'window' trains on "
+                    "[B, 3, HN, WN]; 'square' trains the same cut pictures zero-padded to the square (the yardstick)")
     a = ap.parse_args()
     r = run(a.steps, a.images, a.size, a.batch, a.cfg, seed=a.seed, lr=a.lr, eval_every=a.eval_every, log_every=a.log_every,
-            deterministic=a.deterministic)
+            deterministic=a.deterministic, window=a.window, window_recipe=a.window_recipe)
     if r is not None:                            # (rank 0)
         print(r.pop('table'))
         print('OVERFIT ' + json.dumps(r) if r['world'] > 1 else json.dumps(r))

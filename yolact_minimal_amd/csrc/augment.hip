@@ -87,18 +87,18 @@ __device__ __forceinline__ bool to_source(const ym_aug_plan& p, int sy, int sx, 
 constexpr int ALB = 16;
 struct AugTable { ym_aug_item it[ALB]; };
 
-// grid = (ceil(S * S / 256), samples of this launch); `out` is the first of those samples' [3][S][S] rows
+// grid = (ceil(Hn * Wn / 256), samples of this launch); `out` is the first of those samples' [3][Hn][Wn] rows: the top-left Hn x Wn
+// WINDOW of the S x S sample (Hn = Wn = S: all of it).  A pixel's arithmetic depends on its (y, x) in the square only.
 template <typename T>
-__global__ __launch_bounds__(256) void k_train_aug_image(const AugTable tab, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_train_aug_image(const AugTable tab, int Hn, int Wn, float* __restrict__ out) {
     const ym_aug_plan& p = tab.it[blockIdx.y].plan;
     const T* __restrict__ img = (const T*)tab.it[blockIdx.y].img;
-    const int S = p.S;
-    const long long total = (long long)S * S;
+    const long long total = (long long)Hn * Wn;
     const float scale = (float)p.q / (float)p.r;
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     out += (size_t)blockIdx.y * 3 * total;
-    const int y = (int)(e / S), x = (int)(e - (long long)y * S);
+    const int y = (int)(e / Wn), x = (int)(e - (long long)y * Wn);
     float vb = p.mean[0], vg = p.mean[1], vr = p.mean[2];
     int ry, rx;
     if (to_resized(p, y, x, ry, rx)) {
@@ -152,12 +152,13 @@ __device__ __forceinline__ void u8_taps(int n_src, int n_dst, int d, bool clamp_
 // `fixed`: uint8 masks of an already-square crop — the reference resizes them as uint8 (pad_to_square :138-141 returns them
 // untouched, multi_scale_resize :180-181), i.e. through OpenCV's 8-bit fixed-point path, and a {0,1} mask stays {0,1}
 // (oracle/augment_ref.py resize_bilinear_u8); every other sample's masks went through the float32 pad buffer first.
-// grid = (ceil(S * S / 256), mask rows of this launch): workgroup row blockIdx.y is row `row_begin + blockIdx.y` of `keep` and of `out`;
+// grid = (ceil(Hn * Wn / 256), mask rows of this launch), the rows [Hn][Wn] windows of the S x S masks: workgroup row blockIdx.y is
+// row `row_begin + blockIdx.y` of `keep` and of `out`;
 // its sample is the last of the launch's `nb` table entries that starts at or before it (an entry with k == 0 shares its row0 with
 // the next one).  A `keep` index outside the sample's n_masks reads nothing: the row comes out zero.
 template <typename T>
-__global__ __launch_bounds__(256) void k_train_aug_masks(const AugTable tab, int nb, int row_begin, const int32_t* __restrict__ keep,
-                                                         float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_train_aug_masks(const AugTable tab, int nb, int row_begin, int Hn, int Wn,
+                                                         const int32_t* __restrict__ keep, float* __restrict__ out) {
     const int row = row_begin + (int)blockIdx.y;
     int b = 0;
     for (int i = 1; i < nb; ++i)
@@ -165,12 +166,11 @@ __global__ __launch_bounds__(256) void k_train_aug_masks(const AugTable tab, int
     const ym_aug_plan& p = tab.it[b].plan;
     const int kj = keep[row];
     const bool fixed = sizeof(T) == 1 && p.cw == p.ch;
-    const int S = p.S;
-    const long long plane = (long long)S * S;
+    const long long plane = (long long)Hn * Wn;
     const float scale = (float)p.q / (float)p.r;
     const long long rem = (long long)blockIdx.x * 256 + threadIdx.x;
     if (rem >= plane) return;
-    const int y = (int)(rem / S), x = (int)(rem - (long long)y * S);
+    const int y = (int)(rem / Wn), x = (int)(rem - (long long)y * Wn);
     const T* __restrict__ m = (const T*)tab.it[b].masks + (size_t)kj * p.H * p.W;
     float v = 0.f;
     int ry, rx;
@@ -220,25 +220,26 @@ int check_plan(const ym_aug_plan* p) {
     return YM_OK;
 }
 
-// One launch per ALB samples, the grid (ceil(S * S / 256), samples); `what` names the entry in a launch error.
-int launch_image(const char* what, const ym_aug_item* items, int B, int S, int is_u8, float* out, ym_stream_t s) {
-    const long long plane = (long long)S * S;
+// One launch per ALB samples, the grid (ceil(Hn * Wn / 256), samples); `what` names the entry in a launch error.
+int launch_image(const char* what, const ym_aug_item* items, int B, int Hn, int Wn, int is_u8, float* out, ym_stream_t s) {
+    const long long plane = (long long)Hn * Wn;
     const unsigned gx = (unsigned)((plane + 255) / 256);
     for (int b0 = 0; b0 < B; b0 += ALB) {
         const int nb = B - b0 < ALB ? B - b0 : ALB;
         AugTable tab = {};
         std::copy(items + b0, items + b0 + nb, tab.it);
         float* o = out + (size_t)b0 * 3 * plane;
-        if (is_u8) hipLaunchKernelGGL(k_train_aug_image<uint8_t>, dim3(gx, nb), dim3(256), 0, (hipStream_t)s, tab, o);
-        else hipLaunchKernelGGL(k_train_aug_image<float>, dim3(gx, nb), dim3(256), 0, (hipStream_t)s, tab, o);
+        if (is_u8) hipLaunchKernelGGL(k_train_aug_image<uint8_t>, dim3(gx, nb), dim3(256), 0, (hipStream_t)s, tab, Hn, Wn, o);
+        else hipLaunchKernelGGL(k_train_aug_image<float>, dim3(gx, nb), dim3(256), 0, (hipStream_t)s, tab, Hn, Wn, o);
     }
     return ym_check_launch(what);
 }
 
-// One launch per ALB samples that have rows (more only where their rows exceed grid.y's 65535), the grid (ceil(S * S / 256), rows).
+// One launch per ALB samples that have rows (more only where their rows exceed grid.y's 65535), the grid (ceil(Hn * Wn / 256), rows).
 // `items[b].row0` is the running sum of the earlier k (checked by the callers).
-int launch_masks(const char* what, const ym_aug_item* items, int B, int S, int is_u8, const int32_t* keep, float* out, ym_stream_t s) {
-    const long long plane = (long long)S * S;
+int launch_masks(const char* what, const ym_aug_item* items, int B, int Hn, int Wn, int is_u8, const int32_t* keep, float* out,
+                 ym_stream_t s) {
+    const long long plane = (long long)Hn * Wn;
     const unsigned gx = (unsigned)((plane + 255) / 256);
     for (int b0 = 0; b0 < B; b0 += ALB) {
         const int nb = B - b0 < ALB ? B - b0 : ALB;
@@ -247,8 +248,8 @@ int launch_masks(const char* what, const ym_aug_item* items, int B, int S, int i
         const int lo = items[b0].row0, hi = items[b0 + nb - 1].row0 + items[b0 + nb - 1].k;
         for (int r = lo; r < hi; r += 65535) {
             const int ny = hi - r < 65535 ? hi - r : 65535;
-            if (is_u8) hipLaunchKernelGGL(k_train_aug_masks<uint8_t>, dim3(gx, ny), dim3(256), 0, (hipStream_t)s, tab, nb, r, keep, out);
-            else hipLaunchKernelGGL(k_train_aug_masks<float>, dim3(gx, ny), dim3(256), 0, (hipStream_t)s, tab, nb, r, keep, out);
+            if (is_u8) hipLaunchKernelGGL(k_train_aug_masks<uint8_t>, dim3(gx, ny), dim3(256), 0, (hipStream_t)s, tab, nb, r, Hn, Wn, keep, out);
+            else hipLaunchKernelGGL(k_train_aug_masks<float>, dim3(gx, ny), dim3(256), 0, (hipStream_t)s, tab, nb, r, Hn, Wn, keep, out);
         }
     }
     return ym_check_launch(what);
@@ -270,6 +271,11 @@ int check_items(const char* what, const ym_aug_item* items, int B, int S) {
     return YM_OK;
 }
 
+int check_window(const char* what, int S, int Hn, int Wn) {
+    YM_REQUIRE(Hn >= 1 && Wn >= 1 && Hn <= S && Wn <= S, "%s: window %d x %d is not inside %d x %d", what, Hn, Wn, S, S);
+    return YM_OK;
+}
+
 }  // namespace
 
 extern "C" size_t ym_sizeof_aug_item(void) { return sizeof(ym_aug_item); }
@@ -281,7 +287,7 @@ extern "C" int ym_train_aug_image(const void* img_hwc_bgr, int is_u8, const ym_a
     ym_aug_item it = {};
     it.plan = *plan;
     it.img = img_hwc_bgr;
-    return launch_image("train_aug_image", &it, 1, plan->S, is_u8, out_chw, s);
+    return launch_image("train_aug_image", &it, 1, plan->S, plan->S, is_u8, out_chw, s);
 }
 
 extern "C" int ym_train_aug_masks(const void* masks, int is_u8, const int32_t* keep, int k, const ym_aug_plan* plan, float* out,
@@ -296,22 +302,31 @@ extern "C" int ym_train_aug_masks(const void* masks, int is_u8, const int32_t* k
     it.masks = masks;
     it.n_masks = INT32_MAX;                      // (this entry is not told how many instances `masks` holds)
     it.k = k;
-    return launch_masks("train_aug_masks", &it, 1, plan->S, is_u8, keep, out, s);
+    return launch_masks("train_aug_masks", &it, 1, plan->S, plan->S, is_u8, keep, out, s);
 }
 
-extern "C" int ym_train_aug_image_batch(const ym_aug_item* items, int B, int S, int is_u8, float* out, ym_stream_t s) {
+extern "C" int ym_train_aug_image_batch_window(const ym_aug_item* items, int B, int S, int Hn, int Wn, int is_u8, float* out,
+                                               ym_stream_t s) {
     const char* what = "train_aug_image_batch";
     int rc = check_items(what, items, B, S);
     if (rc != YM_OK) return rc;
+    rc = check_window(what, S, Hn, Wn);
+    if (rc != YM_OK) return rc;
     YM_REQUIRE(out, "%s: null output pointer", what);
     for (int b = 0; b < B; ++b) YM_REQUIRE(items[b].img, "%s: sample %d: null image pointer", what, b);
-    return launch_image(what, items, B, S, is_u8, out, s);
+    return launch_image(what, items, B, Hn, Wn, is_u8, out, s);
 }
 
-extern "C" int ym_train_aug_masks_batch(const ym_aug_item* items, int B, int S, int is_u8, const int32_t* keep_dev, int total_k,
-                                        float* out, ym_stream_t s) {
+extern "C" int ym_train_aug_image_batch(const ym_aug_item* items, int B, int S, int is_u8, float* out, ym_stream_t s) {
+    return ym_train_aug_image_batch_window(items, B, S, S, S, is_u8, out, s);
+}
+
+extern "C" int ym_train_aug_masks_batch_window(const ym_aug_item* items, int B, int S, int Hn, int Wn, int is_u8,
+                                               const int32_t* keep_dev, int total_k, float* out, ym_stream_t s) {
     const char* what = "train_aug_masks_batch";
     int rc = check_items(what, items, B, S);
+    if (rc != YM_OK) return rc;
+    rc = check_window(what, S, Hn, Wn);
     if (rc != YM_OK) return rc;
     long long rows = 0;
     for (int b = 0; b < B; ++b) {
@@ -326,5 +341,10 @@ extern "C" int ym_train_aug_masks_batch(const ym_aug_item* items, int B, int S, 
     YM_REQUIRE(rows == total_k, "%s: the samples hold %lld rows, total_k = %d", what, rows, total_k);
     if (total_k == 0) return YM_OK;
     YM_REQUIRE(keep_dev && out, "%s: total_k = %d with a null keep or output pointer", what, total_k);
-    return launch_masks(what, items, B, S, is_u8, keep_dev, out, s);
+    return launch_masks(what, items, B, Hn, Wn, is_u8, keep_dev, out, s);
+}
+
+extern "C" int ym_train_aug_masks_batch(const ym_aug_item* items, int B, int S, int is_u8, const int32_t* keep_dev, int total_k,
+                                        float* out, ym_stream_t s) {
+    return ym_train_aug_masks_batch_window(items, B, S, S, S, is_u8, keep_dev, total_k, out, s);
 }

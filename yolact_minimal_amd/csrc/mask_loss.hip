@@ -39,14 +39,20 @@ struct MLP {
     double* loss;            // accumulated (atomicAdd)
     const int* total_dev;    // null, or the device-side total positive count: gscale /= *total_dev
     int Hp, Wp, P, ntiles;
-    float gscale;            // d(total loss)/d(loss_i) = mask_alpha / Hp / Wp / total_pos
+    int Pv;                  // 0: crop windows scale by the map's own extents; > 0: window mode, the map is the top-left Hp x Wp of
+                             // a Pv x Pv one (boxes live in the square's frame) and the windows are clamped to the physical map
+    float gscale;            // d(total loss)/d(loss_i) = mask_alpha / Hp / Wp / total_pos  (window mode: mask_alpha / Pv / Pv / ..)
 };
 
-__device__ __forceinline__ void crop_span(float a, float b, float size, float& lo, float& hi) {
+// `size`: the extent the box scales by (the reference's crop, padding 1); `phys`: the extent that exists (== size outside window
+// mode, where the last line changes nothing).  In window mode the last line keeps the stored window inside the map; no pixel's
+// `inside` depends on it, since pixels exist only below `phys` -- what window mode changes is the scaling by `size` = Pv
+__device__ __forceinline__ void crop_span(float a, float b, float size, float phys, float& lo, float& hi) {
     a = a * size; b = b * size;
     lo = fminf(a, b); hi = fmaxf(a, b);
     lo = lo - 1.f; lo = lo < 0.f ? 0.f : lo;
     hi = hi + 1.f; hi = hi > size ? size : hi;
+    hi = hi > phys ? phys : hi;
 }
 
 __global__ __launch_bounds__(256) void k_mask_loss(const MLP pb) {
@@ -73,8 +79,8 @@ __global__ __launch_bounds__(256) void k_mask_loss(const MLP pb) {
             s_row[i] = src;
             const f32x4 b = *reinterpret_cast<const f32x4*>(it.boxes + (size_t)src * 4);
             float x1, x2, y1, y2;
-            crop_span(b[0], b[2], (float)p.Wp, x1, x2);
-            crop_span(b[1], b[3], (float)p.Hp, y1, y2);
+            crop_span(b[0], b[2], (float)(pb.Pv > 0 ? pb.Pv : p.Wp), (float)p.Wp, x1, x2);
+            crop_span(b[1], b[3], (float)(pb.Pv > 0 ? pb.Pv : p.Hp), (float)p.Hp, y1, y2);
             s_win[i][0] = x1; s_win[i][1] = x2; s_win[i][2] = y1; s_win[i][3] = y2;
             s_w[i] = p.wscale / ((b[2] - b[0]) * (b[3] - b[1]));
             s_gt[i] = it.gt_idx32 ? it.gt_idx32[i] : (int)it.gt_idx64[src];
@@ -234,7 +240,7 @@ constexpr int ML_BLOCKS = 64;    // 256 waves per image, each walking ~P/32/256 
 constexpr size_t ML_PART_BYTES = (size_t)ML_BLOCKS * 4 * MAXP * 32 * sizeof(float);
 
 int launch_chunk(const ym_mask_loss_item* items, int nb, const float* const* coef, const float* const* boxes, const int* const* gt32,
-                 int Hp, int Wp, float gscale, const int32_t* total_dev, double* loss_accum, char* workspace, hipStream_t st) {
+                 int Hp, int Wp, int Pv, float gscale, const int32_t* total_dev, double* loss_accum, char* workspace, hipStream_t st) {
     MLP p;
     MLReduce r;
     int nmax = 0;
@@ -249,7 +255,7 @@ int launch_chunk(const ym_mask_loss_item* items, int nb, const float* const* coe
         if (a.n > nmax) nmax = a.n;
     }
     if (nmax == 0) return YM_OK;
-    p.loss = loss_accum; p.total_dev = total_dev; p.Hp = Hp; p.Wp = Wp; p.P = Hp * Wp; p.ntiles = (p.P + 31) / 32; p.gscale = gscale;
+    p.loss = loss_accum; p.total_dev = total_dev; p.Hp = Hp; p.Wp = Wp; p.Pv = Pv; p.P = Hp * Wp; p.ntiles = (p.P + 31) / 32; p.gscale = gscale;
     hipLaunchKernelGGL(k_mask_loss, dim3(ML_BLOCKS, nb), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_mask_loss_reduce, dim3(nmax, nb), dim3(256), 0, st, r, ML_BLOCKS * 4);
     return ym_check_launch("mask_loss");
@@ -260,9 +266,12 @@ int launch_chunk(const ym_mask_loss_item* items, int nb, const float* const* coe
 extern "C" size_t ym_mask_loss_workspace_bytes(void) { return ML_PART_BYTES + 256; }
 extern "C" size_t ym_mask_loss_batch_workspace_bytes(int B) { return (size_t)(B < MLB ? (B > 0 ? B : 1) : MLB) * ML_PART_BYTES + 256; }
 
-extern "C" int ym_mask_loss_batch(const ym_mask_loss_item* items, int B, int Hp, int Wp, float gscale, const int32_t* total_pos_dev,
-                                  double* loss_accum, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+// Pv = 0: the maps are whole; Pv > 0: each is the top-left Hp x Wp of a Pv x Pv map (window training)
+extern "C" int ym_mask_loss_batch_window(const ym_mask_loss_item* items, int B, int Hp, int Wp, int Pv, float gscale,
+                                         const int32_t* total_pos_dev, double* loss_accum, void* workspace, size_t workspace_bytes,
+                                         ym_stream_t s) {
     YM_REQUIRE(items && B > 0 && Hp > 0 && Wp > 0 && loss_accum && workspace, "mask_loss_batch: bad args");
+    YM_REQUIRE(Pv == 0 || (Pv >= Hp && Pv >= Wp), "mask_loss_batch: the %d x %d map is not inside the virtual extent %d", Hp, Wp, Pv);
     for (int i = 0; i < B; ++i) {
         const ym_mask_loss_item& a = items[i];
         YM_REQUIRE(a.n >= 0 && a.n <= MAXP, "mask_loss: at most %d positives per image (cfg.masks_to_train), got %d", MAXP, a.n);
@@ -272,17 +281,24 @@ extern "C" int ym_mask_loss_batch(const ym_mask_loss_item* items, int B, int Hp,
     if (workspace_bytes < ym_mask_loss_batch_workspace_bytes(B)) { ym_set_error("mask_loss_batch: workspace too small"); return YM_ENOSPC; }
     for (int b0 = 0; b0 < B; b0 += MLB) {
         const int nb = B - b0 < MLB ? B - b0 : MLB;
-        const int rc = launch_chunk(items + b0, nb, nullptr, nullptr, nullptr, Hp, Wp, gscale, total_pos_dev, loss_accum, (char*)workspace, (hipStream_t)s);
+        const int rc = launch_chunk(items + b0, nb, nullptr, nullptr, nullptr, Hp, Wp, Pv, gscale, total_pos_dev, loss_accum, (char*)workspace, (hipStream_t)s);
         if (rc != YM_OK) return rc;
     }
     return YM_OK;
 }
 
-extern "C" int ym_mask_loss_fwd_bwd(const float* proto, const float* coef_pos, const float* box_pos, const int32_t* gt_idx,
-                                    const float* gt_masks_ds, const int64_t* anchor_idx, int n, int Hp, int Wp, float wscale,
-                                    float gscale, double* loss_accum, float* dproto, float* dcoef_full, void* workspace,
-                                    size_t workspace_bytes, ym_stream_t s) {
+extern "C" int ym_mask_loss_batch(const ym_mask_loss_item* items, int B, int Hp, int Wp, float gscale, const int32_t* total_pos_dev,
+                                  double* loss_accum, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    return ym_mask_loss_batch_window(items, B, Hp, Wp, 0, gscale, total_pos_dev, loss_accum, workspace, workspace_bytes, s);
+}
+
+extern "C" int ym_mask_loss_fwd_bwd_window(const float* proto, const float* coef_pos, const float* box_pos, const int32_t* gt_idx,
+                                           const float* gt_masks_ds, const int64_t* anchor_idx, int n, int Hp, int Wp, int Pv,
+                                           float wscale, float gscale, double* loss_accum, float* dproto, float* dcoef_full,
+                                           void* workspace, size_t workspace_bytes, ym_stream_t s) {
     YM_REQUIRE(n >= 0 && n <= MAXP, "mask_loss: at most %d positives per image (cfg.masks_to_train), got %d", MAXP, n);
+    YM_REQUIRE(Hp > 0 && Wp > 0 && (Pv == 0 || (Pv >= Hp && Pv >= Wp)), "mask_loss: the %d x %d map is not inside the virtual extent %d",
+               Hp, Wp, Pv);
     if (n == 0) return YM_OK;
     YM_REQUIRE(proto && coef_pos && box_pos && gt_idx && gt_masks_ds && anchor_idx && loss_accum && dproto && dcoef_full && workspace,
                "mask_loss: null pointer");
@@ -291,5 +307,13 @@ extern "C" int ym_mask_loss_fwd_bwd(const float* proto, const float* coef_pos, c
     a.proto = proto; a.gt_masks_ds = gt_masks_ds; a.anchor_idx = anchor_idx; a.n = n; a.wscale = wscale; a.dproto = dproto;
     a.dcoef_full = dcoef_full;
     const int* g32 = gt_idx;
-    return launch_chunk(&a, 1, &coef_pos, &box_pos, &g32, Hp, Wp, gscale, nullptr, loss_accum, (char*)workspace, (hipStream_t)s);
+    return launch_chunk(&a, 1, &coef_pos, &box_pos, &g32, Hp, Wp, Pv, gscale, nullptr, loss_accum, (char*)workspace, (hipStream_t)s);
+}
+
+extern "C" int ym_mask_loss_fwd_bwd(const float* proto, const float* coef_pos, const float* box_pos, const int32_t* gt_idx,
+                                    const float* gt_masks_ds, const int64_t* anchor_idx, int n, int Hp, int Wp, float wscale,
+                                    float gscale, double* loss_accum, float* dproto, float* dcoef_full, void* workspace,
+                                    size_t workspace_bytes, ym_stream_t s) {
+    return ym_mask_loss_fwd_bwd_window(proto, coef_pos, box_pos, gt_idx, gt_masks_ds, anchor_idx, n, Hp, Wp, 0, wscale, gscale, loss_accum,
+                                       dproto, dcoef_full, workspace, workspace_bytes, s);
 }

@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     'ym_sizeof_aug_item', 'ym_train_aug_image_batch', 'ym_train_aug_masks_batch',
     'ym_ann_to_mask_ragged_workspace_bytes', 'ym_ann_to_mask_ragged',
     'ym_val_preprocess_window', 'ym_after_nms_window_workspace_bytes', 'ym_after_nms_window', 'ym_after_nms_window_packed',
+    'ym_mask_loss_batch_window', 'ym_mask_loss_fwd_bwd_window', 'ym_train_aug_image_batch_window', 'ym_train_aug_masks_batch_window',
 )
 
 
@@ -229,6 +230,8 @@ def lib():
         L.ym_mask_loss_batch_workspace_bytes.argtypes = [i32]
         L.ym_mask_loss_batch_workspace_bytes.restype = sz
         L.ym_mask_loss_batch.argtypes = [ctypes.POINTER(MaskLossItem), i32, i32, i32, f32, vp, vp, vp, sz, vp]
+        L.ym_mask_loss_batch_window.argtypes = [ctypes.POINTER(MaskLossItem), i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]
+        L.ym_mask_loss_fwd_bwd_window.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, sz, vp]
         L.ym_mask_iou_workspace_bytes.argtypes = [i32, i32, i64]
         L.ym_mask_iou_workspace_bytes.restype = sz
         L.ym_mask_iou.argtypes = [vp, i32, vp, i32, i64, vp, vp, sz, vp]
@@ -262,6 +265,8 @@ def lib():
                                f'hip.AugItemC ({ctypes.sizeof(AugItemC)} B): rebuild the library')
         L.ym_train_aug_image_batch.argtypes = [ctypes.POINTER(AugItemC), i32, i32, i32, vp, vp]
         L.ym_train_aug_masks_batch.argtypes = [ctypes.POINTER(AugItemC), i32, i32, i32, vp, i32, vp, vp]
+        L.ym_train_aug_image_batch_window.argtypes = [ctypes.POINTER(AugItemC), i32, i32, i32, i32, i32, vp, vp]
+        L.ym_train_aug_masks_batch_window.argtypes = [ctypes.POINTER(AugItemC), i32, i32, i32, i32, i32, vp, i32, vp, vp]
         L.ym_match_anchors.argtypes = [vp, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
         L.ym_match_anchors_batch.argtypes = [vp, vp, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
         L.ym_semantic_loss_batch.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp, vp]

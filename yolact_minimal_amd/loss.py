@@ -8,6 +8,8 @@ Reference: `compute_loss` `/root/reference/modules/yolact.py:166-203`, `category
   mask             -> `ym_mask_loss_batch` (f32 MFMA: coefficient x prototype GEMM, sigmoid, crop, BCE, both gradient GEMMs;
                       one launch pair for the batch)
   semantic seg     -> `ym_semantic_loss_batch` (one launch; target built on the fly from the down-sampled gt masks)
+  window training  -> `compute_loss(..., virtual=(Pv, Sv))`: the maps are the top-left window of the square's (utils/rect.py); the mask
+                      term runs `ym_mask_loss_batch_window`, both terms keep the square's per-pixel weight
 
 The losses are terminal nodes of the graph, so each kernel also writes d(loss)/d(input); the autograd Functions below only
 scale those by the incoming gradient.  Same arithmetic and normalisations as the reference (each rank normalises by its LOCAL
@@ -92,7 +94,7 @@ class _MaskLossFn(torch.autograd.Function):
     counts are read from device memory (no host synchronisation).  Autograd only scales the stored gradients."""
 
     @staticmethod
-    def forward(ctx, proto_p, coef_p, anchor_box, anchor_gt, idx, ds_masks, num_pos, alpha_hw):
+    def forward(ctx, proto_p, coef_p, anchor_box, anchor_gt, idx, ds_masks, num_pos, alpha_hw, pv=0):
         b, hp, wp, _ = proto_p.shape
         dev = proto_p.device
         proto_c, coef_c = proto_p.detach().contiguous(), coef_p.detach().contiguous()
@@ -110,8 +112,13 @@ class _MaskLossFn(torch.autograd.Function):
             it.gt_masks_ds, it.anchor_idx = hip.ptr(ds_masks[i]).value, idx[i].data_ptr()
             it.n, it.wscale, it.n_dev = cap, 1.0, num_pos.data_ptr() + 4 * i
             it.dproto, it.dcoef_full = dproto[i].data_ptr(), dcoef[i].data_ptr()
-        hip.check(hip.lib().ym_mask_loss_batch(items, b, hp, wp, float(alpha_hw), ctypes.c_void_p(num_pos.data_ptr() + 4 * b),
-                                               _vp(acc), _vp(ws), ws.numel(), hip.stream_ptr()), 'ym_mask_loss_batch')
+        if pv:                           # window training: the map is the top-left hp x wp of a pv x pv one (same kernels)
+            hip.check(hip.lib().ym_mask_loss_batch_window(items, b, hp, wp, int(pv), float(alpha_hw),
+                                                          ctypes.c_void_p(num_pos.data_ptr() + 4 * b), _vp(acc), _vp(ws), ws.numel(),
+                                                          hip.stream_ptr()), 'ym_mask_loss_batch_window')
+        else:
+            hip.check(hip.lib().ym_mask_loss_batch(items, b, hp, wp, float(alpha_hw), ctypes.c_void_p(num_pos.data_ptr() + 4 * b),
+                                                   _vp(acc), _vp(ws), ws.numel(), hip.stream_ptr()), 'ym_mask_loss_batch')
         ctx.save_for_backward(dproto, dcoef)
         return (acc * alpha_hw / num_pos[b]).float().reshape(())
 
@@ -119,8 +126,8 @@ class _MaskLossFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         dproto, dcoef = ctx.saved_tensors
         if _UNIT[0]:
-            return dproto, dcoef, None, None, None, None, None, None
-        return dproto * grad_out, dcoef * grad_out, None, None, None, None, None, None
+            return dproto, dcoef, None, None, None, None, None, None, None
+        return dproto * grad_out, dcoef * grad_out, None, None, None, None, None, None, None
 
 
 MAX_MASKS_PER_IMAGE = 128        # positives per image the mask-loss kernel holds (cfg.masks_to_train = 100)
@@ -142,12 +149,18 @@ def mask_generator(device):
 
 
 
-def lincomb_mask_loss(cfg, pos, anchor_gt, coef_p, proto_p, mask_gt, anchor_box, num_pos=None):
+def lincomb_mask_loss(cfg, pos, anchor_gt, coef_p, proto_p, mask_gt, anchor_box, num_pos=None, virtual=None):
     """`pos`: [B,N] bool, or the matched labels conf_gt (int64, > 0 = positive).  `num_pos`: int32 device tensor [n_0..n_{B-1}, total] of positive counts (`ym_class_box_loss` produces it); computed here
     when absent.  Nothing is read back to the host: the kernel takes the counts from device memory, and the reference's
     `randperm` sub-sampling of > masks_to_train positives (:261-267, a CPU generator there) is a device-side random top-k —
-    a uniformly random subset like the reference's, from the device generator instead of the host one."""
+    a uniformly random subset like the reference's, from the device generator instead of the host one.
+    `virtual` = Pv (window training, utils/rect.py): `proto_p` is the top-left `ph x pw` of a `Pv x Pv` map, boxes and `mask_gt`
+    ([n, 4 ph, 4 pw]: the window of the square's masks) live in that square's frame; crop windows scale by Pv and are clamped to
+    the map, the loss is scaled by mask_alpha / Pv / Pv, so a pixel weighs what it weighs in the square step."""
     ph, pw = proto_p.shape[1:3]
+    pv = int(virtual) if virtual else 0
+    if pv and (pv < ph or pv < pw):
+        raise RuntimeError(f'lincomb_mask_loss: the {ph} x {pw} prototype map is not inside the virtual extent {pv}')
     b, n = pos.shape
     dev = proto_p.device
     if num_pos is None:
@@ -171,7 +184,7 @@ def lincomb_mask_loss(cfg, pos, anchor_gt, coef_p, proto_p, mask_gt, anchor_box,
         hip.gt_masks_downsample(mask_gt[i].contiguous().float(), ph, pw, ds)
         ds_masks.append(ds.reshape(g, ph * pw))
     return _MaskLossFn.apply(proto_p, coef_p, anchor_box.contiguous().float(), anchor_gt.contiguous(), idx, ds_masks,
-                             num_pos.contiguous(), cfg.mask_alpha / ph / pw)
+                             num_pos.contiguous(), cfg.mask_alpha / pv / pv if pv else cfg.mask_alpha / ph / pw, pv)
 
 
 class _SemanticLossFn(torch.autograd.Function):
@@ -208,12 +221,24 @@ class _SemanticLossFn(torch.autograd.Function):
         return (dseg[..., :ctx.nc] * grad_out).permute(0, 3, 1, 2), None, None, None
 
 
-def semantic_seg_loss(cfg, seg_p, mask_gt, box_class):
+def semantic_seg_loss(cfg, seg_p, mask_gt, box_class, virtual=None):
+    """`virtual` = the square's semantic extent (window training): the map is the top-left `mh x mw` of a `virtual x virtual` one and
+    the loss keeps the square's per-pixel weight, semantic_alpha / virtual / virtual / B."""
     b, _, mh, mw = seg_p.shape
+    if virtual:
+        sv = int(virtual)
+        if sv < mh or sv < mw:
+            raise RuntimeError(f'semantic_seg_loss: the {mh} x {mw} map is not inside the virtual extent {sv}')
+        return _SemanticLossFn.apply(seg_p, mask_gt, box_class, cfg.semantic_alpha / sv / sv / b)
     return _SemanticLossFn.apply(seg_p, mask_gt, box_class, cfg.semantic_alpha / mh / mw / b)
 
 
-def compute_loss(cfg, anchors, class_p, box_p, coef_p, proto_p, seg_p, box_class, mask_gt):
+def compute_loss(cfg, anchors, class_p, box_p, coef_p, proto_p, seg_p, box_class, mask_gt, virtual=None):
+    """`virtual` = (Pv, Sv): window training (`Yolact.forward` on an image that is not the square) -- the virtual extents of the
+    prototype and the semantic map; `anchors` are then `Yolact.anchors_for` of the window."""
+    if anchors.shape[0] != box_p.shape[1]:
+        raise RuntimeError(f'compute_loss: {box_p.shape[1]} prediction rows against {anchors.shape[0]} anchors')
+    pv, sv = virtual if virtual is not None else (None, None)
     device = class_p.device
     b, n = box_p.shape[:2]
     offsets = torch.empty(b, n, 4, device=device)
@@ -225,6 +250,6 @@ def compute_loss(cfg, anchors, class_p, box_p, coef_p, proto_p, seg_p, box_class
     anchors = anchors.contiguous().float()
     match(cfg, [bc.contiguous().float() for bc in box_class], anchors, offsets, conf_gt, anchor_box, anchor_gt, ws)
     loss_c, loss_b = _ClassBoxLossFn.apply(class_p, box_p, offsets, conf_gt, num_pos, cfg.conf_alpha, cfg.bbox_alpha, 3)
-    loss_m = lincomb_mask_loss(cfg, conf_gt, anchor_gt, coef_p, proto_p, mask_gt, anchor_box, num_pos)   # counts stay on the device
-    loss_s = semantic_seg_loss(cfg, seg_p, mask_gt, box_class)
+    loss_m = lincomb_mask_loss(cfg, conf_gt, anchor_gt, coef_p, proto_p, mask_gt, anchor_box, num_pos, virtual=pv)   # counts stay on the device
+    loss_s = semantic_seg_loss(cfg, seg_p, mask_gt, box_class, virtual=sv)
     return loss_c, loss_b, loss_m, loss_s

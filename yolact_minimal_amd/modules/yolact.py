@@ -242,6 +242,23 @@ class Yolact(nn.Module):
             self._engines[key] = eng
         return eng
 
+    def _train_window(self, img):
+        """Window training (utils/rect.py): a train-mode image `[B, 3, Hn, Wn]` that is not the `S x S` square is the top-left window
+        of the square sample.  Returns the window's anchors (`anchors_for`: the square list's values), the virtual extents
+        `(S / 4, S / 8)` of the prototype / semantic map for the loss, and the level shapes the heads must have written.  Host
+        only; raises for a window outside the square, a side that is no multiple of 32, and Swin-T."""
+        from ..utils.rect import rect_level_shapes
+        size = int(self.cfg.img_size)
+        hn, wn = int(img.shape[2]), int(img.shape[3])
+        if hasattr(self.backbone, 'patch_embed'):
+            raise RuntimeError(f'window training ({hn} x {wn} of {size} x {size}) is not supported with the Swin-T backbone: '
+                               f'train it on the square')
+        levels = rect_level_shapes(hn, wn)                                  # multiples of 32
+        if hn > size or wn > size or size % 8:
+            raise RuntimeError(f'window training: the image {hn} x {wn} is not inside the {size} x {size} square '
+                               f'(img_size a multiple of 8)')
+        return self.anchors_for(hn, wn, img.device), (size // 4, size // 8), levels
+
     def forward(self, img, box_classes=None, masks_gt=None):
         if not img.is_cuda:
             raise RuntimeError('yolact_minimal_amd.Yolact runs on an MI355X only: got a CPU tensor and '
@@ -253,6 +270,10 @@ class Yolact(nn.Module):
             from ..loss import compute_loss
             if isinstance(self.anchors, list):
                 self.anchors = torch.tensor(self.anchors, device=img.device).reshape(-1, 4)    # like reference :171-172
+            anchors, virtual, levels = self.anchors, None, None
+            size = int(self.cfg.img_size)
+            if img.dim() == 4 and tuple(img.shape[2:]) != (size, size):
+                anchors, virtual, levels = self._train_window(img)      # raises before any launch
             state = self._own_train_state(img.device)
             if state is not None:
                 weights_changed()                # a torch optimizer stepped since the last forward: one batched re-pack
@@ -263,5 +284,10 @@ class Yolact(nn.Module):
             if state is not None:
                 state.after_forward()
             self.mark_weights_changed()          # the optimizer is about to change them; eval engines must repack
-            return compute_loss(self.cfg, self.anchors, class_p, box_p, coef_p, proto_p, seg_p, box_classes, masks_gt)
+            if levels is not None:
+                rows = sum(h * w for h, w in levels) * len(self.cfg.aspect_ratios)
+                if box_p.shape[1] != rows or tuple(proto_p.shape[1:3]) != (img.shape[2] // 4, img.shape[3] // 4):
+                    raise RuntimeError(f'window training: the heads wrote {box_p.shape[1]} rows and a {tuple(proto_p.shape[1:3])} '
+                                       f'prototype map, the window {img.shape[2]} x {img.shape[3]} has {rows} rows ({levels})')
+            return compute_loss(self.cfg, anchors, class_p, box_p, coef_p, proto_p, seg_p, box_classes, masks_gt, virtual=virtual)
         return self._engine(img).forward(img)

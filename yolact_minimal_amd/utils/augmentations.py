@@ -111,7 +111,18 @@ class AugPlan:
     original --mirror--> --crop (cx, cy, cw, ch)--> --pad to square q (px, py)--> --resize q -> r--> --final: pad (fx, fy)
     into s or crop (fx, fy) of s--> [s, s]."""
     __slots__ = ('brightness', 'contrast', 'saturation', 'hue', 'mirror', 'crop', 'square', 'pad', 'resize', 'final_pad',
-                 'final_crop', 'size', 'boxes', 'labels', 'keep')
+                 'final_crop', 'size', 'boxes', 'labels', 'keep', 'window')
+
+
+def _train_window(window, train_size, what):
+    """`window=None` -> the square sample; else `(Hn, Wn)`: its top-left window, the input of a window training step
+    (utils/rect.py) -- both sides positive multiples of 32 and at most `train_size`."""
+    if window is None:
+        return None
+    hn, wn = int(window[0]), int(window[1])
+    if hn < 32 or wn < 32 or hn % 32 or wn % 32 or hn > train_size or wn > train_size:
+        raise RuntimeError(f'{what}: window {hn} x {wn}: both sides are positive multiples of 32 inside {train_size} x {train_size}')
+    return hn, wn
 
 
 def _crop_boxes(rng, ori_h, crop_h, ori_w, crop_w, boxes, labels, keep_idx, keep_ratio=0.3):
@@ -135,12 +146,18 @@ def _crop_boxes(rng, ori_h, crop_h, ori_w, crop_w, boxes, labels, keep_idx, keep
     return None
 
 
-def sample_train_aug(img_h, img_w, boxes, labels, train_size, rng=_random):
+def sample_train_aug(img_h, img_w, boxes, labels, train_size, rng=_random, window=None):
     """Draw the random decisions of `train_aug` in the reference's order and carry the boxes through them.
     boxes [n,4] pixels (x1,y1,x2,y2) — float64 like the dataset's `np.array(box_list)` (utils/coco.py:97), labels [n].
-    Returns an AugPlan, or None where the reference returns Nones."""
+    Returns an AugPlan, or None where the reference returns Nones.
+    `window=(Hn, Wn)`: the sample is the top-left window of the `train_size` square one.  The draws and their order are those of
+    the square call (a seeded run decides the same geometry, `rng` ends in the same state); only the last step differs: boxes are
+    clipped to the window (x to 0 .. Wn - 1, y to 0 .. Hn - 1), dropped at area <= 20 and divided by `train_size` -- they stay in
+    the square's frame.  None when no box is left in the window."""
     import numpy as np
+    window = _train_window(window, int(train_size), 'sample_train_aug')
     p = AugPlan()
+    p.window = window
     boxes = np.array(boxes, dtype=np.float64).reshape(-1, 4)
     labels = np.array(labels)
     keep_idx = np.arange(boxes.shape[0])
@@ -195,8 +212,9 @@ def sample_train_aug(img_h, img_w, boxes, labels, train_size, rng=_random):
         p.final_crop = (fx, fy)
     p.size = train_size
     # clip_box, remove_small_box, to_01_box (:19-36)
-    boxes[:, [0, 2]] = np.clip(boxes[:, [0, 2]], 0, train_size - 1)
-    boxes[:, [1, 3]] = np.clip(boxes[:, [1, 3]], 0, train_size - 1)
+    hn, wn = window if window is not None else (train_size, train_size)
+    boxes[:, [0, 2]] = np.clip(boxes[:, [0, 2]], 0, wn - 1)
+    boxes[:, [1, 3]] = np.clip(boxes[:, [1, 3]], 0, hn - 1)
     big = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]) > 20
     boxes, labels, keep_idx = boxes[big], labels[big], keep_idx[big]
     if boxes.shape[0] == 0:
@@ -226,9 +244,21 @@ def plan_to_c(plan, img_h, img_w):
     return c
 
 
-def apply_train_aug(img, masks, plan):
+def _plan_window(plan, window, what):
+    """The window a pixel call writes: the explicit `window`, else the one the plan was drawn for, else None (the square)."""
+    if window is None:
+        return getattr(plan, 'window', None)
+    return _train_window(window, int(plan.size), what)
+
+
+def apply_train_aug(img, masks, plan, window=None):
     """The pixel half of `train_aug` on the device: img [H,W,3] BGR (uint8 / float32) and masks [n,H,W] (uint8 / float32) CUDA
-    tensors + an AugPlan -> (image [3,S,S] float32 normalised RGB, masks [k,S,S] float32), two HIP launches."""
+    tensors + an AugPlan -> (image [3,S,S] float32 normalised RGB, masks [k,S,S] float32), two HIP launches.
+    `window=(Hn, Wn)` (default: the plan's own): `[3, Hn, Wn]` and `[k, Hn, Wn]`, the square result's `[:Hn, :Wn]` bit for bit."""
+    window = _plan_window(plan, window, 'apply_train_aug')
+    if window is not None:
+        images, views = apply_train_aug_batch([img], [masks], [plan], window=window)
+        return images[0], views[0]
     if not (torch.is_tensor(img) and img.is_cuda and masks.is_cuda):
         raise RuntimeError('yolact_minimal_amd.utils.augmentations.train_aug expects CUDA tensors (there is no CPU path)')
     if img.dtype not in (torch.uint8, torch.float32) or masks.dtype not in (torch.uint8, torch.float32):
@@ -249,11 +279,12 @@ def apply_train_aug(img, masks, plan):
     return out, mout
 
 
-def train_aug(img, masks, boxes, labels, train_size, rng=_random):
+def train_aug(img, masks, boxes, labels, train_size, rng=_random, window=None):
     """Reference call shape (`train_aug(img, masks, boxes, labels, train_size)`, utils/augmentations.py:230-252) with CUDA
     tensors for `img` / `masks` and host arrays for `boxes` (pixels) / `labels`: returns (img [3,S,S], masks [k,S,S], boxes [k,4]
-    in 0..1, labels [k]) — the arrays as numpy float64 / like the reference — or four Nones when the sample is rejected."""
-    plan = sample_train_aug(img.shape[0], img.shape[1], boxes, labels, train_size, rng)
+    in 0..1, labels [k]) — the arrays as numpy float64 / like the reference — or four Nones when the sample is rejected.
+    `window=(Hn, Wn)`: the top-left window of that sample, `[3, Hn, Wn]` / `[k, Hn, Wn]`, boxes in 0..1 of the square."""
+    plan = sample_train_aug(img.shape[0], img.shape[1], boxes, labels, train_size, rng, window=window)
     if plan is None:
         return None, None, None, None
     out, mout = apply_train_aug(img, masks, plan)
@@ -268,16 +299,17 @@ def train_aug(img, masks, boxes, labels, train_size, rng=_random):
 # upload of all the `keep` indices.  The single-sample entries are the one-item instances of the same two kernels: row b of a batch
 # equals `train_aug` of sample b bit for bit.
 # ------------------------------------------------------------------------------------------------------------------------
-def sample_train_aug_batch(sizes, boxes, labels, train_size, rng=_random):
+def sample_train_aug_batch(sizes, boxes, labels, train_size, rng=_random, window=None):
     """The host half for B samples (no device, no library): `sizes` = [(h, w), ...], `boxes[b]` [n_b, 4] pixels or None (a sample
     without a valid annotation: rejected WITHOUT a draw, as `COCODetection.finish` does), `labels[b]` [n_b].  One `sample_train_aug`
     per sample, in order, on the one `rng`.  Returns `(plans, order)`: `plans[b]` an AugPlan or None (rejected); `order` the
     batch `train_collate` makes of them -- the valid samples in order, then `valid_batch[i]` for each missing slot i (that list
-    grows while it is read, so one valid sample can fill several slots).  RuntimeError when no sample survives."""
+    grows while it is read, so one valid sample can fill several slots).  RuntimeError when no sample survives.
+    `window=(Hn, Wn)`: every plan is drawn for that window (`sample_train_aug`)."""
     sizes, boxes, labels = list(sizes), list(boxes), list(labels)
     if not (len(sizes) == len(boxes) == len(labels)):
         raise RuntimeError(f'sample_train_aug_batch: {len(sizes)} sizes, {len(boxes)} box arrays and {len(labels)} label arrays')
-    plans = [None if bx is None else sample_train_aug(int(h), int(w), bx, lb, train_size, rng)
+    plans = [None if bx is None else sample_train_aug(int(h), int(w), bx, lb, train_size, rng, window=window)
              for (h, w), bx, lb in zip(sizes, boxes, labels)]
     order = [b for b, p in enumerate(plans) if p is not None]
     if not order:
@@ -296,14 +328,16 @@ def _one_dtype(tensors, what, fn):
         raise RuntimeError(f'{fn}: the {what} of a batch are all uint8 or all float32')
 
 
-def apply_train_aug_batch(imgs, masks, plans, out=None):
+def apply_train_aug_batch(imgs, masks, plans, out=None, window=None):
     """The pixel half for B samples: `imgs` a `FrameBatch` or a list of device HWC BGR tensors (all uint8 or all float32; they need
     not share an allocation and are not repacked), `masks` a list of device `[n_b, H_b, W_b]` tensors (all uint8 or all float32),
     `plans` B AugPlans (no None: the caller has applied `order`; a repeated sample is the same item twice).  Returns
     `(images [B, 3, S, S] float32, [masks_b [k_b, S, S] float32])`, the masks B views into ONE `[K, S, S]` allocation.  `out`: a
     contiguous float32 device tensor `[>= B, 3, S, S]` whose first B rows are written (the result is then `out[:B]`).  One launch
     per 16 samples for the images, one for the masks; every `keep` index of the batch goes up in one non-blocking copy from pinned
-    memory after being checked against n_b on the host.  No host synchronisation."""
+    memory after being checked against n_b on the host.  No host synchronisation.
+    `window=(Hn, Wn)` (default: the window the plans were drawn for, which they must share): the results are `[B, 3, Hn, Wn]` and
+    `[k_b, Hn, Wn]`, the square results' `[:Hn, :Wn]` bit for bit (`ym_train_aug_*_batch_window`, the same kernels)."""
     from .frames import FrameBatch
     fn = 'apply_train_aug_batch'
     if isinstance(imgs, FrameBatch):
@@ -327,6 +361,10 @@ def apply_train_aug_batch(imgs, masks, plans, out=None):
     if masks[0].device != dev:
         raise RuntimeError(f'{fn}: images on {dev}, masks on {masks[0].device}')
     size = int(plans[0].size)
+    if window is None and any(getattr(p, 'window', None) != getattr(plans[0], 'window', None) for p in plans):
+        raise RuntimeError(f'{fn}: the plans of a batch are drawn for one window')
+    window = _plan_window(plans[0], window, fn)
+    hn, wn = window if window is not None else (size, size)
     items = (hip.AugItemC * batch)()
     keep_all, alive = [], []
     for b, (img, m, plan) in enumerate(zip(imgs, masks, plans)):
@@ -346,16 +384,24 @@ def apply_train_aug_batch(imgs, masks, plans, out=None):
         keep_all += keep
     total = len(keep_all)
     if out is None:
-        out = torch.empty(batch, 3, size, size, dtype=torch.float32, device=dev)
+        out = torch.empty(batch, 3, hn, wn, dtype=torch.float32, device=dev)
     elif not torch.is_tensor(out) or not out.is_cuda or out.device != dev or out.dtype != torch.float32 or out.dim() != 4 or \
-            out.shape[0] < batch or tuple(out.shape[1:]) != (3, size, size) or not out.is_contiguous():
-        raise RuntimeError(f'{fn}: out is a contiguous float32 [>= {batch}, 3, {size}, {size}] tensor on the device of the images')
-    mout = torch.empty(total, size, size, dtype=torch.float32, device=dev)
+            out.shape[0] < batch or tuple(out.shape[1:]) != (3, hn, wn) or not out.is_contiguous():
+        raise RuntimeError(f'{fn}: out is a contiguous float32 [>= {batch}, 3, {hn}, {wn}] tensor on the device of the images')
+    mout = torch.empty(total, hn, wn, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         keep_dev = None
         if total:
             keep_dev = torch.tensor(keep_all, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
         L = hip.lib()
+        if window is not None:
+            hip.check(L.ym_train_aug_image_batch_window(items, batch, size, hn, wn, int(imgs[0].dtype == torch.uint8), hip.ptr(out),
+                                                        hip.stream_ptr()), 'ym_train_aug_image_batch_window')
+            hip.check(L.ym_train_aug_masks_batch_window(items, batch, size, hn, wn, int(masks[0].dtype == torch.uint8),
+                                                        hip.ptr(keep_dev, torch.int32), total, hip.ptr(mout), hip.stream_ptr()),
+                      'ym_train_aug_masks_batch_window')
+            views = [mout[it.row0:it.row0 + it.k] for it in items]
+            return out[:batch], views
         hip.check(L.ym_train_aug_image_batch(items, batch, size, int(imgs[0].dtype == torch.uint8), hip.ptr(out), hip.stream_ptr()),
                   'ym_train_aug_image_batch')
         hip.check(L.ym_train_aug_masks_batch(items, batch, size, int(masks[0].dtype == torch.uint8), hip.ptr(keep_dev, torch.int32),
@@ -364,10 +410,11 @@ def apply_train_aug_batch(imgs, masks, plans, out=None):
     return out[:batch], views
 
 
-def train_aug_batch(imgs, masks, boxes, labels, train_size, rng=_random):
+def train_aug_batch(imgs, masks, boxes, labels, train_size, rng=_random, window=None):
     """`train_aug` for a batch: `imgs` / `masks` as for `apply_train_aug_batch`, `boxes[b]` (pixels; None = no valid annotation) and
     `labels[b]` host arrays.  Returns `(images [B, 3, S, S], [masks_b [k_b, S, S]], [boxes_b [k_b, 4] in 0..1], [labels_b [k_b]])`
-    in `train_collate`'s batch composition: rejected samples are replaced by repeated valid ones."""
+    in `train_collate`'s batch composition: rejected samples are replaced by repeated valid ones.
+    `window=(Hn, Wn)`: the top-left windows of those samples, `[B, 3, Hn, Wn]` / `[k_b, Hn, Wn]`, boxes in 0..1 of the square."""
     from .frames import FrameBatch
     frames = imgs.frames if isinstance(imgs, FrameBatch) else imgs
     if isinstance(frames, torch.Tensor) or not hasattr(frames, '__len__') or isinstance(masks, torch.Tensor) or not hasattr(masks, '__len__'):
@@ -380,6 +427,6 @@ def train_aug_batch(imgs, masks, boxes, labels, train_size, rng=_random):
                            f'{len(labels)} label arrays')
     _one_dtype(frames, 'images', 'train_aug_batch')
     _one_dtype([m for m in masks if m is not None] or frames, 'masks', 'train_aug_batch')
-    plans, order = sample_train_aug_batch([(f.shape[0], f.shape[1]) for f in frames], boxes, labels, train_size, rng)
+    plans, order = sample_train_aug_batch([(f.shape[0], f.shape[1]) for f in frames], boxes, labels, train_size, rng, window=window)
     images, mviews = apply_train_aug_batch([frames[b] for b in order], [masks[b] for b in order], [plans[b] for b in order])
     return images, mviews, [plans[b].boxes for b in order], [plans[b].labels for b in order]

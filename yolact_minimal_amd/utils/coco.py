@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from .augmentations import train_aug, train_aug_batch, val_aug
+from .augmentations import _train_window, train_aug, train_aug_batch, val_aug
 
 
 def _rle_string_to_counts(s):
@@ -344,8 +344,13 @@ def detect_collate(batch):
 class COCODetection:
     """`COCODetection(cfg, mode)` of the reference (utils/coco.py:47-134), samples produced on `device`."""
 
-    def __init__(self, cfg, mode='train', device='cuda', rng=_random):
+    def __init__(self, cfg, mode='train', device='cuda', rng=_random, window=None):
+        """`window=(Hn, Wn)` (mode 'train' only): samples are the top-left window of the `cfg.img_size` square ones, the input of
+        window training (utils/rect.py): images `[3, Hn, Wn]`, masks `[k, Hn, Wn]`, boxes in 0..1 of the square."""
         self.mode, self.cfg, self.device, self.rng = mode, cfg, torch.device(device), rng
+        if window is not None and mode != 'train':
+            raise RuntimeError(f"COCODetection(window=) serves mode 'train' only, got '{mode}'")
+        self.window = _train_window(window, int(cfg.img_size), 'COCODetection')
         if mode in ('train', 'val'):
             self.image_path = cfg.train_imgs if mode == 'train' else cfg.val_imgs
             self.coco = COCO(cfg.train_ann if mode == 'train' else cfg.val_ann, device=self.device)
@@ -401,7 +406,7 @@ class COCODetection:
         masks = self.coco.annsToMasks(rec['anns'])
         assert tuple(masks.shape) == (boxes.shape[0], height, width), 'Unmatched annotations.'
         if self.mode == 'train':
-            img_out, masks_out, boxes, labels = train_aug(img_dev, masks, boxes, labels, self.cfg.img_size, self.rng)
+            img_out, masks_out, boxes, labels = train_aug(img_dev, masks, boxes, labels, self.cfg.img_size, self.rng, window=self.window)
             if img_out is None:
                 return None, None, None
             return img_out, np.hstack((boxes, np.expand_dims(labels, axis=1))), masks_out
@@ -436,7 +441,8 @@ class COCODetection:
             masks.append(m)
             boxes.append(bx)
             labels.append(np.array(rec['labels']))
-        images, masks_out, boxes_out, labels_out = train_aug_batch(frames, masks, boxes, labels, self.cfg.img_size, self.rng)
+        images, masks_out, boxes_out, labels_out = train_aug_batch(frames, masks, boxes, labels, self.cfg.img_size, self.rng,
+                                                                    window=self.window)
         rows = [np.hstack((b, np.expand_dims(l, axis=1))) for b, l in zip(boxes_out, labels_out)]
         host = torch.from_numpy(np.concatenate(rows, 0).astype(np.float32)).pin_memory()
         targets = list(host.to(images.device, non_blocking=True).split([r.shape[0] for r in rows], 0))
