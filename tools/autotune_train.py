@@ -10,7 +10,7 @@ os.environ['YM_TUNE_TRAIN'] = '1'
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from yolact_minimal_amd.utils.synthetic import synth_targets  # noqa: E402
-from yolact_minimal_amd import train_engine  # noqa: E402
+from yolact_minimal_amd import conv_tuning  # noqa: E402
 from yolact_minimal_amd.config import build_cfg  # noqa: E402
 from yolact_minimal_amd.modules.yolact import Yolact  # noqa: E402
 
@@ -32,12 +32,12 @@ def main():
         losses = net(img, [b.to(dev) for b in boxes], [m.to(dev) for m in masks])
         sum(losses).backward()
         torch.cuda.synchronize()
-        print(name, size, 'entries so far', len(train_engine._new_entries), flush=True)
+        print(name, size, 'entries so far', len(conv_tuning._new_entries), flush=True)
         del net, losses
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
-    train_engine.dump_new_entries(args.out)
-    print('wrote', args.out, len(train_engine._new_entries))
+    conv_tuning.dump_new_entries(args.out)
+    print('wrote', args.out, len(conv_tuning._new_entries))
 
 
 if __name__ == '__main__':

@@ -7,7 +7,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from yolact_minimal_amd import hip  # noqa: E402
+from yolact_minimal_amd import conv_tuning, hip  # noqa: E402
 
 
 def make_desc(b, h, w, cin, cout, k, stride, residual, dev):
@@ -35,7 +35,6 @@ def main():
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     ws = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for spec in args.shapes.split(';'):
         b, h, w, cin, cout, k, stride, res = (int(v) for v in spec.split(','))
         d, keep = make_desc(b, h, w, cin, cout, k, stride, res, dev)
@@ -55,22 +54,9 @@ def main():
                     cands.append((t, 1, kw, 0))
         for tile, ks, kw, stg in cands:
             d.tile_m, d.tile_n, d.ksplit, d.kwaves, d.stages = tile[0], tile[1], ks, kw, stg
-            if hip.conv_workspace_bytes(d) > ws.numel():
-                continue
-            try:
-                for _ in range(3):
-                    hip.conv2d_fwd(d, ws)
-            except RuntimeError:
-                continue
-            best = 1e9
-            for _ in range(3):
-                e0.record()
-                for _ in range(args.iters):
-                    hip.conv2d_fwd(d, ws)
-                e1.record()
-                torch.cuda.synchronize()
-                best = min(best, e0.elapsed_time(e1) / args.iters * 1e3)
-            rows.append((best, tile, ks, kw, stg))
+            best = conv_tuning.time_conv(d, ws, iters=args.iters, reps=3, warmup=3)
+            if best is not None:
+                rows.append((best, tile, ks, kw, stg))
         rows.sort()
         print(f'== M={M} N={cout} K={d.k_pad} k={k} s={stride} res={res}: {flops / 1e9:.2f} GFLOP')
         for t, tile, ks, kw, stg in rows[:12]:

@@ -13,7 +13,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
-from yolact_minimal_amd import hip  # noqa: E402
+from yolact_minimal_amd import conv_tuning, hip  # noqa: E402
 from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 from tools.conv_sweep import make_desc  # noqa: E402
 
@@ -22,7 +22,6 @@ TUNED = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tuned = json.load(open(TUNED))
 ws = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
 counters = torch.zeros(hip.TILE_COUNTERS, dtype=torch.int32, device=dev)
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 CUS = 256
 
 
@@ -72,19 +71,9 @@ def make_dgrad_desc(b, h, w, cin, cout, k, stride):
 
 def time_desc(d, iters=30, reps=3):
     try:
-        for _ in range(3):
-            hip.conv2d_fwd(d, ws)
-    except RuntimeError as ex:
+        return conv_tuning.time_launch(lambda: hip.conv2d_fwd(d, ws), iters=iters, reps=reps, warmup=3)
+    except RuntimeError:
         return None
-    best = 1e9
-    for _ in range(reps):
-        e0.record()
-        for _ in range(iters):
-            hip.conv2d_fwd(d, ws)
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) / iters * 1e3)
-    return best
 
 
 def main():

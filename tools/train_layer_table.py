@@ -18,7 +18,7 @@ from yolact_minimal_amd.utils.synthetic import synth_targets  # noqa: E402
 from yolact_minimal_amd.config import build_cfg  # noqa: E402
 from yolact_minimal_amd.modules.yolact import Yolact  # noqa: E402
 from yolact_minimal_amd.trainer import Trainer  # noqa: E402
-from yolact_minimal_amd import train_engine as T, hip  # noqa: E402
+from yolact_minimal_amd import conv_tuning, train_engine as T, hip  # noqa: E402
 from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -49,21 +49,10 @@ opa = torch.randn(1 << 28, device=dev)       # 1 GiB of floats
 opb = torch.randn(1 << 26, device=dev)
 out = torch.empty(1 << 28, device=dev)
 stats = torch.zeros(1 << 20, dtype=torch.float64, device=dev)
-ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
 
 def timeit(fn):
-    fn(); fn()
-    best = 1e30
-    for _ in range(2):
-        torch.cuda.synchronize()
-        ev0.record()
-        for _ in range(args.iters):
-            fn()
-        ev1.record()
-        torch.cuda.synchronize()
-        best = min(best, ev0.elapsed_time(ev1) / args.iters * 1e3)
-    return best
+    return conv_tuning.time_launch(fn, iters=args.iters, reps=2, warmup=2, sync_each_rep=True)
 
 
 rows = []
@@ -96,15 +85,11 @@ for key, n in counts.items():
                 d.Cin <= 256 and d.seg[0].act in (0, 1)):
             keep = ConvPlan.of(d)
             best = (us, None)
-            for tm, tn in ((64, 256), (128, 128), (256, 64)):
-                if tn * d.Cin * 4 > 64 * 1024:
-                    continue
-                for st in (52, 53, 54):
-                    cand = ConvPlan(tm, tn, 1, 0, st)
-                    cand.apply(d)
-                    t = timeit(lambda: hip.conv2d_fwd(d, big))
-                    if t < best[0]:
-                        best = (t, cand.to_row())
+            for cand in conv_tuning.weight_stationary_candidates(d.Cin):
+                cand.apply(d)
+                t = timeit(lambda: hip.conv2d_fwd(d, big))
+                if t < best[0]:
+                    best = (t, cand.to_row())
             keep.apply(d)
             name = f'M{M}_N{N}_C{d.Cin}_k1_s1_seg1_r{int(bool(d.residual))}_st'
             print(f'  ws: {name:44s} x{n:2d} {us:7.1f} -> {best[0]:7.1f} us {best[1]}', flush=True)

@@ -16,7 +16,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
-from yolact_minimal_amd import hip, engine as E, plan_transfer  # noqa: E402
+from yolact_minimal_amd import conv_tuning, engine as E, plan_transfer  # noqa: E402
 from yolact_minimal_amd.conv_plan import ConvPlan, from_entry  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -48,27 +48,10 @@ else:
     eng.run(img)
 torch.cuda.synchronize()
 big = torch.empty(1 << 28, device=dev, dtype=torch.uint8)
-ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
 
 def launch_time(d, iters=20):
-    if hip.conv_workspace_bytes(d) > big.numel():
-        return None
-    try:
-        for _ in range(2):
-            hip.conv2d_fwd(d, big)
-    except RuntimeError:
-        return None
-    best = 1e30
-    for _ in range(3):
-        torch.cuda.synchronize()
-        ev0.record()
-        for _ in range(iters):
-            hip.conv2d_fwd(d, big)
-        ev1.record()
-        torch.cuda.synchronize()
-        best = min(best, ev0.elapsed_time(ev1) / iters * 1e3)
-    return best
+    return conv_tuning.time_conv(d, big, iters=iters, reps=3, warmup=2, sync_each_rep=True)
 
 
 def forward_ms():
@@ -91,15 +74,7 @@ def forward_ms():
         return best
     eng.run(img)                      # (re)captures the graph after a retune
     torch.cuda.synchronize()
-    best = 1e30
-    for _ in range(2):
-        ev0.record()
-        for _ in range(args.replays):
-            eng.run(img)
-        ev1.record()
-        torch.cuda.synchronize()
-        best = min(best, ev0.elapsed_time(ev1) / args.replays)
-    return best
+    return conv_tuning.time_launch(lambda: eng.run(img), iters=args.replays, reps=2, warmup=0) / 1e3
 
 
 def put(sig, v):
@@ -130,26 +105,15 @@ for _, sig, t0 in sorted(order):
     cur = c.plan
     M = d.B * d.Ho * d.Wo
     cands = []
-    for tm, tn in ((32, 32), (64, 32), (32, 64)):
-        for kwv in (1, 2, 4):
-            if kwv > d.k_pad // 32:
-                continue
-            vs = [ConvPlan(tm, tn, 1, kwv, 22)]
-            if kwv < 4:                                   # fewer waves per workgroup: single tiles are balanced over the CUs
-                vs += [ConvPlan(tm, tn, 1, kwv, 22, grid_wgs=wpb) for wpb in (1, 2) if wpb >= kwv]
-            tiles = -(-M // 32) * -(-d.Cout // 32)
-            if (tm, tn, kwv) == (32, 32, 4) and tiles > 256 and d.nseg == 1 and d.tile_counters:
-                # tail split: the tiles past the last full round of 256 CUs are computed as K slices in the CUs' second slots
-                for ts in (4, 6, 8):
-                    if ts * 2 <= d.k_pad // 32:
-                        vs.append(ConvPlan(tm, tn, 1, kwv, 22, tiles % 256 or 256, ts))
-            for v in vs:
-                keep = ConvPlan.of(d)
-                v.apply(d)
-                t = launch_time(d)
-                keep.apply(d)
-                if t is not None:
-                    cands.append((t, v))
+    # (fewer waves per workgroup: single tiles are balanced over the CUs; tail split: the tiles past the last full round of 256 CUs
+    #  are computed as K slices in the CUs' second slots)
+    for v in conv_tuning.wave_dma_candidates(M, d.Cout, d.k_pad // 32, tail=d.nseg == 1 and bool(d.tile_counters)):
+        keep = ConvPlan.of(d)
+        v.apply(d)
+        t = launch_time(d)
+        keep.apply(d)
+        if t is not None:
+            cands.append((t, v))
     if pipe is not None:              # the latency entry is a candidate too (the slot may currently run a `_tp` row)
         alt = from_entry(E.tuned_table().get(sig))
         if alt is not None:

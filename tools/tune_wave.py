@@ -14,7 +14,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
-from yolact_minimal_amd import hip, engine as E  # noqa: E402
+from yolact_minimal_amd import conv_tuning, hip, engine as E  # noqa: E402
 from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -33,27 +33,10 @@ eng = net._engine(img)
 eng.run(img)
 torch.cuda.synchronize()
 big = torch.empty(1 << 28, device=dev, dtype=torch.uint8)
-ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
 
 def time_desc(d):
-    if hip.conv_workspace_bytes(d) > big.numel():
-        return None
-    try:
-        for _ in range(3):
-            hip.conv2d_fwd(d, big)
-    except RuntimeError:
-        return None
-    best = 1e30
-    for _ in range(4):
-        torch.cuda.synchronize()
-        ev0.record()
-        for _ in range(args.iters):
-            hip.conv2d_fwd(d, big)
-        ev1.record()
-        torch.cuda.synchronize()
-        best = min(best, ev0.elapsed_time(ev1) / args.iters * 1e3)
-    return best
+    return conv_tuning.time_conv(d, big, iters=args.iters, reps=4, warmup=3, sync_each_rep=True)
 
 
 table = E.tuned_table()
@@ -83,30 +66,23 @@ for c in eng.convs:
             ref = None
     base = time_desc(d)
     best = (base, keep)
-    for tm, tn in ((32, 32), (64, 32), (32, 64)):
-        for kwv in (1, 2, 4):
-            if kwv > d.k_pad // 32:
+    for cand in conv_tuning.wave_dma_candidates(M, d.Cout, d.k_pad // 32, tail=False, rings=(22, 23, 24), waves_per_wg=()):
+        cand.apply(d)
+        t = time_desc(d)
+        if t is None:
+            continue
+        if ref is not None:
+            hip.conv2d_fwd(d, big)
+            torch.cuda.synchronize()
+            err = float((view - ref).abs().max()) / max(1e-30, float(ref.abs().max()))
+            worst = max(worst, err)
+            if not err < 1e-5:
+                print(f'  MISMATCH {c.sig} {tuple(cand)}: max rel err {err:.3e}', flush=True)
                 continue
-            for stg in (22, 23, 24):
-                if stg == 24 and (tm, tn) != (32, 32):
-                    continue
-                cand = ConvPlan(tm, tn, 1, kwv, stg)
-                cand.apply(d)
-                t = time_desc(d)
-                if t is None:
-                    continue
-                if ref is not None:
-                    hip.conv2d_fwd(d, big)
-                    torch.cuda.synchronize()
-                    err = float((view - ref).abs().max()) / max(1e-30, float(ref.abs().max()))
-                    worst = max(worst, err)
-                    if not err < 1e-5:
-                        print(f'  MISMATCH {c.sig} {tuple(cand)}: max rel err {err:.3e}', flush=True)
-                        continue
-                if os.environ.get('YM_TUNE_VERBOSE') and c.sig in os.environ['YM_TUNE_VERBOSE']:
-                    print(f'      {cand[:5]} {t:7.2f} us', flush=True)
-                if t < best[0] * args.margin:
-                    best = (t, cand)
+        if os.environ.get('YM_TUNE_VERBOSE') and c.sig in os.environ['YM_TUNE_VERBOSE']:
+            print(f'      {cand[:5]} {t:7.2f} us', flush=True)
+        if t < best[0] * args.margin:
+            best = (t, cand)
     keep.apply(d)
     tot0 += base
     tot1 += best[0]

@@ -14,7 +14,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
-from yolact_minimal_amd import hip, engine as E  # noqa: E402
+from yolact_minimal_amd import conv_tuning, engine as E  # noqa: E402
 from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -26,27 +26,10 @@ ap.add_argument('--iters', type=int, default=20)
 args = ap.parse_args()
 dev = torch.device('cuda:0')
 big = torch.empty(1 << 28, device=dev, dtype=torch.uint8)
-ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
 
 def launch_time(d):
-    if hip.conv_workspace_bytes(d) > big.numel():
-        return None
-    try:
-        for _ in range(3):
-            hip.conv2d_fwd(d, big)
-    except RuntimeError:
-        return None
-    best = 1e30
-    for _ in range(3):
-        torch.cuda.synchronize()
-        ev0.record()
-        for _ in range(args.iters):
-            hip.conv2d_fwd(d, big)
-        ev1.record()
-        torch.cuda.synchronize()
-        best = min(best, ev0.elapsed_time(ev1) / args.iters * 1e3)
-    return best
+    return conv_tuning.time_conv(d, big, iters=args.iters, reps=3, warmup=3, sync_each_rep=True)
 
 
 rows, seen = {}, set()
@@ -68,15 +51,11 @@ for cfg_name in args.cfgs.split(','):
         keep = ConvPlan.of(d)
         t0 = launch_time(d)
         best = (t0, None)
-        for tm, tn in ((64, 256), (128, 128), (256, 64)):
-            if tn * d.Cin * 4 > 64 * 1024:
-                continue
-            for st in (52, 53, 54):
-                cand = ConvPlan(tm, tn, 1, 0, st)
-                cand.apply(d)
-                t = launch_time(d)
-                if t is not None and t < best[0]:
-                    best = (t, cand.to_row())
+        for cand in conv_tuning.weight_stationary_candidates(d.Cin):
+            cand.apply(d)
+            t = launch_time(d)
+            if t is not None and t < best[0]:
+                best = (t, cand.to_row())
         keep.apply(d)
         gain = best[1] is not None and best[0] < 0.97 * t0
         gf = c.flops / 1e9

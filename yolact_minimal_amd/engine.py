@@ -23,7 +23,7 @@ import sys
 import torch
 import torch.nn as nn
 
-from . import conv_launch, hip, plan_transfer
+from . import conv_launch, conv_tuning, hip, plan_transfer
 from .conv_plan import ConvPlan
 from .hip import ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU
 
@@ -574,7 +574,6 @@ class InferEngine:
         results = {}
         self.autotune_detail = {}
         big_ws = torch.empty(1 << 28, device=self.device, dtype=torch.uint8)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ncopy = int(concurrent) if concurrent else 1        # True = 2 copies
         if ncopy == 1 and concurrent:
             ncopy = 2
@@ -592,6 +591,10 @@ class InferEngine:
                     with torch.cuda.stream(side):
                         hip.conv2d_fwd(d2[i], big_ws2[i])
 
+        def join():                              # the copies' streams end inside the timed interval
+            for side in sides:
+                main.wait_stream(side)
+
         def time_cfg(c, plan):
             d = c.desc
             plan.apply(d)                        # (never the previous table entry's grid; wave kernel with DMA rings: waves per workgroup)
@@ -608,23 +611,10 @@ class InferEngine:
                     if d.tile_counters:
                         dd.tile_counters = counters2[i].data_ptr()
             try:
-                for _ in range(2):
-                    launch(d, d2)
+                return conv_tuning.time_launch(lambda: launch(d, d2), iters=iters, reps=3, warmup=2, sync_each_rep=True,
+                                               join=join if concurrent else None)
             except RuntimeError:
                 return None
-            best = 1e30
-            for _ in range(3):
-                torch.cuda.synchronize()
-                ev0.record()
-                for _ in range(iters):
-                    launch(d, d2)
-                if concurrent:
-                    for side in sides:
-                        main.wait_stream(side)
-                ev1.record()
-                torch.cuda.synchronize()
-                best = min(best, ev0.elapsed_time(ev1) / iters * 1e3)
-            return best
 
         def split_ok(c):
             return mma in (3, 6) and not c.stem and c.desc.Cin % 32 == 0 and c.desc.nlevels == 0
@@ -640,71 +630,11 @@ class InferEngine:
                 c.mma = mma if (mma and not c.plan.wave) else 0
                 continue
             d = c.desc
-            M, nkt = d.B * d.Ho * d.Wo, d.k_pad // 32
-            if d.nlevels:
-                M = sum(d.B * d.level_h[l] * d.level_w[l] for l in range(d.nlevels))
+            M = sum(d.B * d.level_h[l] * d.level_w[l] for l in range(d.nlevels)) if d.nlevels else d.B * d.Ho * d.Wo
             base = time_cfg(c, ConvPlan())
-            cands, wave_cands = [], []
-            tiles = [(128, 64)] if c.stem else [(128, 128), (128, 64), (64, 128), (64, 64)]
-            for tm, tn in tiles:
-                wgs = -(-M // tm) * -(-d.Cout // tn)
-                for ks in (1, 2, 3, 4, 6, 8, 12, 16, 24):
-                    if ks > 1 and (wgs >= 1024 or ks * 2 > nkt or wgs * ks > 8192):
-                        continue
-                    cands.append(ConvPlan(tm, tn, ks, 0, 2))
-                    if (tm, tn) != (128, 128) and nkt // ks >= 3:
-                        cands.append(ConvPlan(tm, tn, ks, 0, 3))
-                    if not c.stem:                       # direct-to-LDS staging, ring of 2 / 3 (/ 4)
-                        cands.append(ConvPlan(tm, tn, ks, 0, 22))
-                        if nkt // ks >= 3:
-                            cands.append(ConvPlan(tm, tn, ks, 0, 23))
-                        if (tm, tn) == (64, 64) and nkt // ks >= 4:
-                            cands.append(ConvPlan(tm, tn, ks, 0, 24))
-                        if (tm, tn) == (64, 64) and nkt // ks >= 2:    # + software-pipelined fragments
-                            cands.append(ConvPlan(tm, tn, ks, 0, 33))
-                            cands.append(ConvPlan(tm, tn, ks, 0, 34))
-                        if (tm, tn) == (64, 64) and d.nseg == 1 and d.tile_counters and c.act in (ACT_NONE, ACT_RELU):
-                            cands.append(ConvPlan(tm, tn, ks, 0, 43))    # persistent kernel (conv_persist.hip), ring of 3 / 6
-                            cands.append(ConvPlan(tm, tn, ks, 0, 46))
-                # workgroup-quantisation fix: split the tiles of the last partial round (over 256 CUs x 1 or 2 workgroups)
-                if not c.stem and d.nseg == 1 and d.tile_counters and cus < wgs <= hip.TILE_COUNTERS:
-                    for r in sorted({wgs % cus, wgs % (2 * cus)} - {0}):
-                        for ts in (2, 3, 4, 6, 8):
-                            if ts * 2 > nkt or r * ts > 2048:
-                                continue
-                            for stg in ((2, 3, 22, 23) + ((33, 34) if (tm, tn) == (64, 64) else ()) if (tm, tn) != (128, 128) and nkt // ts >= 3 else (2, 22)):
-                                cands.append(ConvPlan(tm, tn, 1, 0, stg, r, ts))
-            if not c.stem:
-                for tm, tn in ((32, 32), (64, 32), (32, 64), (64, 64)):
-                    waves = -(-M // tm) * -(-d.Cout // tn)
-                    for kwv in (1, 2, 4, 8):
-                        if kwv > 1 and (waves >= 4096 or kwv > nkt):
-                            continue
-                        if kwv == 8 and tm * tn == 4096:
-                            continue
-                        if waves * kwv > 65536:
-                            continue
-                        cands.append(ConvPlan(tm, tn, 1, kwv))
-                # the wave kernel with private DMA rings (conv_wdma_f32): K split inside the workgroup, no K-slice exchange; one- and
-                # two-wave workgroups where the waves share nothing; the tail split of a 32x32 / four-K-wave plan.  (A launch repeated
-                # back to back undervalues it against the kernels with a cross-workgroup exchange: tools/tune_forward.py judges the
-                # candidates by the plan's forward time.)
-                if d.Cin % 32 == 0 and d.nlevels == 0:
-                    for tm, tn in ((32, 32), (64, 32), (32, 64)):
-                        for kwv in (1, 2, 4):
-                            if kwv <= nkt:
-                                wave_cands.append(ConvPlan(tm, tn, 1, kwv, 22))
-                                wave_cands += [ConvPlan(tm, tn, 1, kwv, 22, grid_wgs=wpb) for wpb in (1, 2) if wpb >= kwv and kwv < 4]
-                    tiles32 = -(-M // 32) * -(-d.Cout // 32)
-                    if cus < tiles32 <= hip.TILE_COUNTERS and d.nseg == 1 and d.tile_counters:
-                        wave_cands += [ConvPlan(32, 32, 1, 4, 22, tiles32 % cus or cus, ts) for ts in (4, 6, 8) if ts * 2 <= nkt]
-            if mma:                                          # split-bf16: register staging with one (0) or two (3) register sets
-                cands = sorted({p._replace(stages=st) for p in cands for st in ((0, 3) if not p.wave else (0,))})
-            best, p = base, ConvPlan()
-            for cand in cands + ([] if mma else wave_cands):
-                t = time_cfg(c, cand)
-                if t is not None and t < best * 0.98:
-                    best, p = t, cand
+            cands = conv_tuning.infer_candidates(M, d.Cout, d.k_pad // 32, d.nseg, c.stem, bool(d.tile_counters), c.act, cus, mma,
+                                                 d.Cin % 32 == 0 and d.nlevels == 0)
+            best, p = conv_tuning.fastest(cands, lambda cand: time_cfg(c, cand), base, ConvPlan())
             c.plan = seen[c.sig] = p
             c.mma = mma if (mma and not p.wave) else 0
             results[c.sig + (f'_mma{mma}' if mma else '')] = p.to_row()

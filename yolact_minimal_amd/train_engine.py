@@ -17,8 +17,8 @@ import weakref
 import torch
 import torch.nn.functional as F
 
-from . import conv_launch, hip, plan_transfer
-from .conv_plan import ConvPlan, WgradPlan
+from . import conv_launch, conv_tuning, hip, plan_transfer
+from .conv_plan import ConvPlan
 from .hip import WgradDesc, ACT_NONE, ACT_RELU, ACT_TANH
 
 _scratch = {}
@@ -30,23 +30,7 @@ def _count(key):
     if launch_counts is not None:
         launch_counts[key] = launch_counts.get(key, 0) + 1
 
-# ---- per-shape kernel configuration (measured on MI355X; same JSON as the inference engine) ---------------------
-_TUNING = os.environ.get('YM_TUNE_TRAIN', '0') == '1'     # sweep unseen shapes inline and remember the winner
-_new_entries = {}
-
-
-def _tuning():
-    """Inline sweeps: tools/autotune_train.py (YM_TUNE_TRAIN=1 at import) or the opt-in tune-on-first-use mode (YM_AUTOTUNE=1, read
-    per call like engine.autotune_on)."""
-    return _TUNING or os.environ.get('YM_AUTOTUNE', '0') == '1'
-
-
-def _remember(key, hit):
-    """A row the inline sweep measured: kept for tools/autotune_train.py (dump_new_entries) and, with YM_AUTOTUNE=1, written through
-    to the per-user cache that later processes overlay on the shipped table (engine.tuned_table)."""
-    from .engine import record_rows
-    _new_entries[key] = hit
-    record_rows({key: hit})
+# ---- per-shape kernel configuration (measured on MI355X; same JSON as the inference engine; inline sweeps: conv_tuning.py) ------
 
 
 def train_mma():
@@ -64,93 +48,27 @@ def tuned_table_changed():
     _desc_cache.clear()
 
 
-def _time_launch(fn, iters=5):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn(); fn()
-    best = 1e30
-    for _ in range(2):
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) / iters)
-    return best
-
-
 def _configure_conv(d, key, stats=False):
     """Set the plan of a forward / data-gradient ConvDesc: the tuned table's (conv_launch.train_plan), else a sweep where those are
-    on (YM_TUNE_TRAIN=1 / YM_AUTOTUNE=1), then the overrides (conv_launch.train_overrides).  `stats`: fused BatchNorm sums."""
-    plan = conv_launch.train_plan(_table(), key, (d.B * d.Ho * d.Wo, d.Cout, d.k_pad // 32, d.nseg), stats, _tuning())
-    if plan is None and _tuning():
-        M, nkt = d.B * d.Ho * d.Wo, d.k_pad // 32
-        big = scratch(torch.device('cuda', torch.cuda.current_device()), 1 << 28)
-        d.tile_counters = _tile_counters(torch.device('cuda', torch.cuda.current_device()))
-        cands = [ConvPlan()]
-        for tm, tn in ((128, 128), (128, 64), (64, 128), (64, 64)):
-            wgs = -(-M // tm) * -(-d.Cout // tn)
-            for ks in (1, 2, 3, 4, 6, 8, 12, 16):
-                if ks > 1 and (wgs >= 1024 or ks * 2 > nkt or wgs * ks > 8192):
-                    continue
-                cands.append(ConvPlan(tm, tn, ks, 0, 2))
-                cands.append(ConvPlan(tm, tn, ks, 0, 22))         # direct-to-LDS staging
-                if (tm, tn) == (64, 64) and nkt // ks >= 3:
-                    cands.append(ConvPlan(tm, tn, ks, 0, 3))
-                    cands.append(ConvPlan(tm, tn, ks, 0, 23))
-            if 256 < wgs <= hip.TILE_COUNTERS:          # split the last partial round of tiles (ym_conv_desc.tail_tiles)
-                for r in sorted({wgs % 256, wgs % 512} - {0}):
-                    for ts in (2, 3, 4, 6, 8):
-                        if ts * 2 <= nkt and r * ts <= 2048:
-                            cands.append(ConvPlan(tm, tn, 1, 0, 2, r, ts))
-                            cands.append(ConvPlan(tm, tn, 1, 0, 22, r, ts))
-        best, plan = 1e30, ConvPlan()
-        for cand in cands:
-            cand.apply(d)
-            if hip.conv_workspace_bytes(d) > big.numel():
-                continue
-            try:
-                t = _time_launch(lambda: hip.conv2d_fwd(d, big))
-            except RuntimeError:
-                continue
-            if t < best * 0.98:
-                best, plan = t, cand
-        _remember(key, plan.to_row())
+    on (YM_TUNE_TRAIN=1 / YM_AUTOTUNE=1: conv_tuning.sweep_train_conv), then the overrides (conv_launch.train_overrides).  `stats`:
+    fused BatchNorm sums."""
+    tuning = conv_tuning.tuning()
+    plan = conv_launch.train_plan(_table(), key, (d.B * d.Ho * d.Wo, d.Cout, d.k_pad // 32, d.nseg), stats, tuning)
+    if plan is None and tuning:
+        dev = torch.device('cuda', torch.cuda.current_device())
+        d.tile_counters = _tile_counters(dev)
+        plan = conv_tuning.sweep_train_conv(d, key, scratch(dev, 1 << 28))
     plan, d.mma = conv_launch.train_overrides(plan or ConvPlan.of(d), _table(), key, train_mma(), d.Cin % 32 == 0 and d.nlevels == 0)
     plan.apply(d)
 
 
 def _configure_wgrad(d, key):
-    plan = conv_launch.wgrad_plan(_table(), key, _tuning())
-    if plan is None and _tuning():
-        big = scratch(torch.device('cuda', torch.cuda.current_device()), 1 << 28)
-        best, plan = 1e30, WgradPlan(0, 2)
-        tbn = 64 if d.Cout_real <= 64 else 128
-        tiles = -(-d.Cout // tbn) * -(-(d.KH * d.KW * d.Cin) // 128)
-        # (22 / 23 / 24: the DMA rings; layers with <= 64 output channels have the 32-pixel ring only, at 48 KB = 3 workgroups per CU)
-        for nb, slots in ((2, 512), (1, 768)) + (((22, 512), (23, 768), (24, 512)) if d.Cout_real > 64 else ((22, 768),)):
-            # pixel splits that make the grid a whole number of rounds of the chip (2 workgroups of 68 KB LDS per CU = 512 slots,
-            # 3 of 34 KB with the single-buffer variant = 768): power-of-two splits alone left e.g. 756 workgroups = 1.5 rounds
-            # for the layer3 3x3 (msplit 14 -> 504 = one round)
-            half = slots // 2
-            fill = {max(1, round(half * j / tiles)) for j in (1, 2, 3, 4, 6, 8, 12, 16)} | {max(1, (half * j) // tiles) for j in (2, 4, 6, 8)}
-            for ms in sorted({0, 1, 2, 4, 8, 16, 32, 64, 128, 256} | {m_ for m_ in fill if m_ <= 256}):
-                WgradPlan(ms, nb).apply(d)
-                need = hip.lib().ym_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
-                if need == 0 or need > big.numel():
-                    continue
-                t = _time_launch(lambda: hip.check(hip.lib().ym_conv2d_wgrad(ctypes.byref(d), ctypes.c_void_p(big.data_ptr()),
-                                                                            big.numel(), hip.stream_ptr()), 'wgrad'))
-                if t < best * 0.98:
-                    best, plan = t, WgradPlan(ms, nb)
-        _remember(key, plan.to_row())
+    tuning = conv_tuning.tuning()
+    plan = conv_launch.wgrad_plan(_table(), key, tuning)
+    if plan is None and tuning:
+        plan = conv_tuning.sweep_wgrad(d, key, scratch(torch.device('cuda', torch.cuda.current_device()), 1 << 28))
     if plan is not None:
         plan.apply(d)
-
-
-def dump_new_entries(path):
-    import json
-    with open(path, 'w') as f:
-        json.dump(_new_entries, f, indent=0, sort_keys=True)
 
 
 def scratch(device, nbytes):
