@@ -764,6 +764,13 @@ int ym_after_nms_ragged(const float* proto, const float* coefs, float* boxes, co
 int ym_after_nms_ragged_packed(const float* proto, const float* coefs, float* boxes, const int32_t* counts, int B, int max_det, int Hp,
                                int Wp, int K, const ym_ragged_image* images, int do_crop, uint64_t* mask_bits, int32_t* boxes_px,
                                void* workspace, size_t workspace_bytes, ym_stream_t s);
+/* ym_pack_masks_ragged: ym_pack_masks for the dense blocks of B <= YM_RAGGED_MAX_IMAGES images of different sizes in ONE launch.
+ * `src` is a HOST array of B device pointers, block b = [rows[b]][img_h_b][img_w_b] float32 (uint8 when is_uint8; nonzero =
+ * foreground); `rows` is a HOST array; both travel to the kernel by value with the table.  Output block b = [rows[b]][img_h_b]
+ * [ceil(img_w_b / 64)] words at bits + images[b].offset, bit for bit what ym_pack_masks writes for that block alone (pad bits zero);
+ * the table rules are those above (offsets in words).  A block of 0 rows is skipped; nothing outside the blocks is written. */
+int ym_pack_masks_ragged(const void* const* src, int is_uint8, const int32_t* rows, const ym_ragged_image* images, int B,
+                         uint64_t* bits, ym_stream_t s);
 
 /* ---- window mode: a network that ran on the top-left Hn x Wn of its square input ---------------------------------------------------
  * The square input of a non-square frame is picture at the top-left and norm_mean (normalised: exactly 0.0) below / right of it.
@@ -879,6 +886,37 @@ int ym_eval_match_log(const int64_t* ids, const float* scores, const int32_t* co
 size_t ym_eval_ap_workspace_bytes(int64_t rows);
 int ym_eval_ap(const uint32_t* log_flags, const int64_t* order, int64_t rows, const int64_t* seg, const int64_t* gt_count, int T,
                int num_classes, double* ap, uint8_t* empty, void* workspace, size_t workspace_bytes, ym_stream_t s);
+/* ym_eval_add_ragged_packed: the metric stage of a whole request -- ym_mask_iou_packed + ym_box_iou + ym_eval_match_log for B <=
+ * YM_RAGGED_MAX_IMAGES images of different sizes in at most THREE launches; the log, gt_count and class_rows end up exactly as after
+ * B single-image calls.
+ *   ids int64 / scores fp32 [B][max_det], boxes_px int32 [B][max_det][4], counts int32 [B] on the device (clamped to 0..max_det);
+ *   det_bits + det_blocks: the packed masks and the table that ym_after_nms_ragged_packed was given;
+ *   gt fp32 [gt_first[B]][5] = x1 y1 x2 y2 in 0..1 and the class, NOT modified: the boxes are scaled in the kernel, x * (float)img_w_b
+ *   and y * (float)img_h_b with one rounding each (what an in-place fp32 scaling of the tensor leaves);
+ *   gt_first: HOST int32 [B + 1], ascending: image b owns rows gt_first[b] .. gt_first[b + 1], g_b of them, 0 <= g_b <= 512;
+ *   gt_bits + gt_blocks: block b = [g_b][img_h_b][ceil(img_w_b / 64)] words, sizes equal to det_blocks';
+ *   image_index: HOST int64 [B], image b's rows are log_*[image_index[b] * max_det ..); < 0 = the entry is padding: nothing of it is
+ *   read, written or counted; log_rows = rows of the three log arrays.
+ * The tables are read during the call and travel to the kernels by value: no device copy, no synchronisation, no host read.
+ *   launch 1 (skipped when no image has ground truth): one workgroup per (20-word chunk of an image's mask rows, group of 128 gt rows),
+ *     grid.x = sum of ceil(words_b / 20) over the images that are not padding and have g_b > 0; a workgroup finds its image from the
+ *     prefix of that sum, loads only the detection rows below counts[b], in passes of 128, and writes its own exact integer partials;
+ *   launch 2: per pair (row below the count, gt) the mask IoU from the summed partials -- ym_mask_iou_packed's finalize step -- and
+ *     the box IoU -- ym_box_iou's formula on (float)boxes_px and the scaled gt box;
+ *   launch 3: workgroup b is ym_eval_match_log's workgroup for image b (one device function: same matching, same log writes, same
+ *     integer atomics; an image whose count is 0 adds no data point and no gt positives, g_b = 0 logs the rows without flags).
+ * No floating-point atomics.  YM_EINVAL, before any launch, for B outside 1..YM_RAGGED_MAX_IMAGES, max_det outside
+ * 1..YM_EVAL_MAX_DET, T outside 1..YM_EVAL_MAX_THRESHOLDS, g_b > 512 or a descending gt_first, table entries that differ in size,
+ * lie at no multiple of YM_RAGGED_ALIGN_BYTES or overlap, img_h_b * ceil(img_w_b / 64) >= 2^18, (image_index[b] + 1) * max_det >
+ * log_rows, two equal indices >= 0, null pointers; YM_ENOSPC for workspace_bytes < ym_eval_add_ragged_workspace_bytes(...) (the
+ * partials and the IoUs of every image; a host function of the sizes; 0 for arguments the entry refuses). */
+size_t ym_eval_add_ragged_workspace_bytes(const ym_ragged_image* det_blocks, const int32_t* gt_first, int B, int max_det);
+int ym_eval_add_ragged_packed(const int64_t* ids, const float* scores, const int32_t* boxes_px, const int32_t* counts, int B, int max_det,
+                              const uint64_t* det_bits, const ym_ragged_image* det_blocks, const float* gt, const int32_t* gt_first,
+                              const uint64_t* gt_bits, const ym_ragged_image* gt_blocks, const int64_t* image_index,
+                              const double* thresholds, int T, int num_classes, float* log_score, int32_t* log_class,
+                              uint32_t* log_flags, int64_t log_rows, int64_t* gt_count, int32_t* class_rows, void* workspace,
+                              size_t workspace_bytes, ym_stream_t s);
 
 /* ---- device-resident COCO evaluator (eval.py:90-104: pycocotools COCOeval on the dumped detections) --------------------------
  * The protocol is the published cocoapi's (cocoeval.py evaluate / computeIoU / evaluateImg / accumulate, maskApi.c bbIou / rleIou)

@@ -11,7 +11,11 @@ Three legs, alternated `--rounds` times in ONE process, each on a pipeline built
 GPU_MAX_HW_QUEUES is raised to 8 before the first HIP call, as tests/conftest.py does.  Every leg evaluates the same samples and
 ends synchronised; its clock includes `drain()` and `calc_map`.
 Also: device and wall time of ONE `after_nms_batch` over 8 of those sizes (packed and dense) against the same eight images through
-eight `after_nms` calls, each over windows of at least `--window-ms` of back-to-back calls.  Prints one JSON line."""
+eight `after_nms` calls, each over windows of at least `--window-ms` of back-to-back calls.
+The metric stage (`--sections metrics`): the b8_d2 pipeline with `batched_metrics=False` (one `DeviceAPData.add` per image: the
+yardstick) and `True` (one `add_batch` per request), alternated `--rounds` times in the same process; and device and wall time of ONE
+`add_batch` over 8 of those sizes against eight `add` calls on the same rows, at ~100 and at 10 detections per image x 15 gt.
+`--sections` picks among legs, after_nms and metrics (default: all).  Prints one JSON line."""
 import argparse
 import gc
 import json
@@ -60,12 +64,56 @@ def summary(rows):
     return {k: {'median': float(np.median(v)), 'range': [min(v), max(v)]} for k, v in rows.items()}
 
 
+def metric_stage(padded, sizes8, gts, cfg, nc, dev, args):
+    """ONE `add_batch` over the eight images of `padded` (the ragged packed `after_nms_batch` result) against eight `add` calls on the
+    same rows, with the counts as they are and clamped to 10: device (HIP events) and wall milliseconds per 8 images.  Every call
+    writes fresh image slots of an accumulator that was sized before the window; the gts `add` scales in place are cloned before it."""
+    from yolact_minimal_amd.evaluate import IOU_THRES
+    from yolact_minimal_amd.utils.device_metrics import DeviceAPData
+    ids, scores, boxes_px, masks, counts = padded
+    gt8, gm8 = [gts[s][0] for s in sizes8], [gts[s][1] for s in sizes8]
+    out = {}
+    for label, cnt in (('n100', counts), ('n10', torch.clamp(counts, max=10))):
+        out[label + '_counts'] = cnt.tolist()
+
+        def window(batched, iters, cnt=cnt):
+            acc = DeviceAPData(nc, IOU_THRES, dev, max_det=cfg.max_detections, capacity_images=8 * iters)
+            pool = [[g.clone() for g in gt8] for _ in range(iters)]
+            step = iter(range(iters))
+
+            def once():
+                i = next(step)
+                if batched:
+                    acc.add_batch(ids, scores, boxes_px, masks, cnt, pool[i], gm8, sizes8, list(range(8 * i, 8 * i + 8)))
+                else:
+                    for b in range(8):
+                        acc.add(ids[b], scores[b], boxes_px[b], masks[b], cnt[b:b + 1], pool[i][b], gm8[b], sizes8[b][0], sizes8[b][1],
+                                image_index=8 * i + b)
+            return timed(once, iters), acc
+        (_, wall), a = window(False, 4)
+        _, b = window(True, 4)
+        assert all(torch.equal(getattr(a, n), getattr(b, n)) for n in ('score', 'cls', 'flags', 'gt_count', 'class_rows'))
+        iters = {False: max(10, int(math.ceil(args.window_ms / max(wall, 1e-3)))), True: 0}
+        iters[True] = iters[False]
+        rows = {f'{label}_{k}_{unit}_ms': [] for k in ('eight_add', 'add_batch') for unit in ('device', 'wall')}
+        for _ in range(args.rounds):
+            for batched, k in ((False, 'eight_add'), (True, 'add_batch')):
+                (d, w_), _ = window(batched, iters[batched])
+                rows[f'{label}_{k}_device_ms'].append(round(d, 4))
+                rows[f'{label}_{k}_wall_ms'].append(round(w_, 4))
+        out.update(summary(rows))
+        out[label + '_calls_per_window'] = iters[False]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--images', type=int, default=192, help='images per pass of a leg')
     ap.add_argument('--window-ms', type=float, default=300.0, help='least wall time of a timed window of calls')
+    ap.add_argument('--sections', default='legs,after_nms,metrics', help='comma-separated: legs, after_nms, metrics')
     args = ap.parse_args()
+    sections = set(args.sections.split(','))
     assert torch.cuda.is_available(), 'ragged_eval_bench measures on the GPU; there is nothing to measure without one'
     import bench
     from yolact_minimal_amd.evaluate import eval_pipeline, evaluate_pipelined
@@ -90,14 +138,19 @@ def main():
         return [(img, gts[s][0].clone(), gts[s][1], s[0], s[1]) for s in (SIZES[i % len(SIZES)] for i in range(n))]
 
     legs = {'b1_d4': (1, 4), 'b8_d2': (8, 2), 'b4_d2': (4, 2)}
+    if 'legs' not in sections:
+        legs = {'b8_d2': (8, 2)} if 'metrics' in sections else {}
     pipes = {k: eval_pipeline(net, cfg, img, 480, 640, depth=d, batch=b) for k, (b, d) in legs.items()}
 
-    def leg(name, samples, step=None):
+    def leg(name, samples, step=None, batched_metrics=False, keep=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        table, _ = evaluate_pipelined(net, cfg, samples, pipe=pipes[name], step=step)
+        table, acc = evaluate_pipelined(net, cfg, samples, pipe=pipes[name], step=step, batched_metrics=batched_metrics)
         torch.cuda.synchronize()
-        return len(samples) / (time.perf_counter() - t0), table
+        rate = len(samples) / (time.perf_counter() - t0)
+        if keep is not None:
+            keep.append(acc)
+        return rate, table
     tables = {}
     for name in legs:                                             # warm-up: allocator, clocks; and what the legs report
         leg(name, loader(32))
@@ -111,7 +164,22 @@ def main():
               'GPU_MAX_HW_QUEUES': os.environ.get('GPU_MAX_HW_QUEUES'), 'img_per_s_rounds': rows, 'img_per_s': summary(rows),
               'detections': detections, 'gt': G, 'window_ms': args.window_ms,
               # (a batch-8 forward reads other plan rows than a batch-1 forward: another rounding, so equality is reported, not required)
-              'tables_equal_b1_d4': {k: tables[k] == tables['b1_d4'] for k in legs}}
+              'tables_equal_b1_d4': {k: tables[k] == tables['b1_d4'] for k in legs if 'b1_d4' in legs}}
+    if 'metrics' in sections:
+        # the metric stage inside the whole loop: same pipeline, same samples, per-image `add` against one `add_batch` per request
+        accs = []
+        for flag in (False, True):
+            leg('b8_d2', loader(32), batched_metrics=flag)
+            leg('b8_d2', loader(24), step=0, batched_metrics=flag, keep=accs)
+        same = all(torch.equal(getattr(accs[0], n), getattr(accs[1], n)) for n in ('score', 'cls', 'flags', 'gt_count', 'class_rows'))
+        assert same, 'add_batch and add disagree on the same requests'
+        loop = {'b8_d2_add': [], 'b8_d2_add_batch': []}
+        for _ in range(args.rounds):
+            loop['b8_d2_add'].append(round(leg('b8_d2', loader())[0], 2))
+            loop['b8_d2_add_batch'].append(round(leg('b8_d2', loader(), batched_metrics=True)[0], 2))
+        result['metric_stage_loop_img_per_s_rounds'] = loop
+        result['metric_stage_loop_img_per_s'] = summary(loop)
+        result['metric_stage_logs_equal'] = same
     for p in pipes.values():
         p.drain()
     del pipes
@@ -137,6 +205,11 @@ def main():
             bx.copy_(s[2])
             out.append(after_nms(s[0], s[1], bx, s[3], s[4], h, w, cfg, packed=packed))
         return out
+    if 'metrics' in sections:
+        result['metric_stage_8_images_ms'] = metric_stage(ragged(True), sizes8, gts, cfg, nc, dev, args)
+    if 'after_nms' not in sections:
+        print(json.dumps(result))
+        return
     for packed in (False, True):                                  # the two must agree before either is timed
         got, want = ragged(packed), per_image(packed)
         for b, w_ in enumerate(want):

@@ -363,11 +363,14 @@ __global__ __launch_bounds__(256) void k_masks_fused(const float* __restrict__ p
 // dense {0, nonzero} rows -> words.  A wave takes PK consecutive words of the flat [rows][wq] output (PK row pieces of 64 pixels in
 // flight per lane), lane u keeps word u: one 8 * PK byte store per wave.
 constexpr int PK = 8;
+// (workgroup `block` of the `nblocks` that share one [rows][W] tensor: k_pack_masks' whole grid, or one block's share of
+// k_pack_masks_ragged's)
 template <typename T>
-__global__ __launch_bounds__(256) void k_pack_masks(const T* __restrict__ m, long long rows, int W, unsigned long long* __restrict__ out) {
+__device__ __forceinline__ void pack_rows(const T* __restrict__ m, long long rows, int W, unsigned long long* __restrict__ out, int block,
+                                          int nblocks) {
     const int wq = (W + 63) >> 6, lane = threadIdx.x & 63;
     const long long total = rows * wq;
-    for (long long g = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * PK; g < total; g += (long long)gridDim.x * 4 * PK) {
+    for (long long g = ((long long)block * 4 + (threadIdx.x >> 6)) * PK; g < total; g += (long long)nblocks * 4 * PK) {
         T v[PK];
 #pragma unroll
         for (int u = 0; u < PK; ++u) {
@@ -384,6 +387,28 @@ __global__ __launch_bounds__(256) void k_pack_masks(const T* __restrict__ m, lon
         }
         if (lane < PK && g + lane < total) out[g + lane] = mine;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_pack_masks(const T* __restrict__ m, long long rows, int W, unsigned long long* __restrict__ out) {
+    pack_rows(m, rows, W, out, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The dense blocks of B images of different sizes in one launch: the sources and the table travel BY VALUE in the kernel arguments,
+// a workgroup finds its image from the prefix of the images' workgroup counts and is then a workgroup of k_pack_masks for that block.
+struct PackRaggedTable {
+    const void* src[YM_RAGGED_MAX_IMAGES];
+    long long rows[YM_RAGGED_MAX_IMAGES];          // rows_b * img_h_b
+    long long out_off[YM_RAGGED_MAX_IMAGES];       // words from `bits` to the image's block
+    int W[YM_RAGGED_MAX_IMAGES];
+    int block_first[YM_RAGGED_MAX_IMAGES + 1];
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_pack_masks_ragged(const PackRaggedTable t, int B, unsigned long long* __restrict__ out) {
+    int b = 0;
+    while (b + 1 < B && (int)blockIdx.x >= t.block_first[b + 1]) ++b;
+    pack_rows(static_cast<const T*>(t.src[b]), t.rows[b], t.W[b], out + t.out_off[b], (int)blockIdx.x - t.block_first[b],
+              t.block_first[b + 1] - t.block_first[b]);
 }
 
 // words -> the reference's float tensor (exactly 0.0f / 1.0f): a thread owns 4 consecutive pixels (never across a word boundary)
@@ -614,6 +639,32 @@ extern "C" int ym_pack_masks(const void* masks, int is_u8, int n, int H, int W, 
     if (is_u8) hipLaunchKernelGGL(k_pack_masks<uint8_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const uint8_t*)masks, rows, W, out);
     else hipLaunchKernelGGL(k_pack_masks<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)masks, rows, W, out);
     return ym_check_launch("pack_masks");
+}
+
+extern "C" int ym_pack_masks_ragged(const void* const* src, int is_uint8, const int32_t* rows, const ym_ragged_image* images, int B,
+                                    uint64_t* bits, ym_stream_t s) {
+    const char* what = "pack_masks_ragged";
+    YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
+    YM_REQUIRE(src && rows && images && bits, "%s: null pointer", what);
+    for (int b = 0; b < B; ++b) YM_REQUIRE(rows[b] >= 0 && (rows[b] == 0 || src[b]), "%s: image %d: %d rows from %p", what, b, rows[b], src[b]);
+    const int rc = ym_check_ragged_table(what, images, B, 8, [&](const ym_ragged_image& im) {
+        return (int64_t)rows[&im - images] * im.img_h * (int64_t)ym_mask_row(true, im.img_w);
+    });
+    if (rc != YM_OK) return rc;
+    PackRaggedTable t = {};
+    for (int b = 0; b < B; ++b) {
+        t.src[b] = src[b];
+        t.rows[b] = (long long)rows[b] * images[b].img_h;
+        t.out_off[b] = images[b].offset;
+        t.W[b] = images[b].img_w;
+        const long long groups = (t.rows[b] * ym_cdiv(images[b].img_w, 64) + PK - 1) / PK;     // (k_pack_masks' grid, per block)
+        t.block_first[b + 1] = t.block_first[b] + (int)((groups + 3) / 4 > 16384 ? 16384 : (groups + 3) / 4);
+    }
+    if (t.block_first[B] == 0) return YM_OK;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(bits);
+    if (is_uint8) hipLaunchKernelGGL(k_pack_masks_ragged<uint8_t>, dim3((unsigned)t.block_first[B]), dim3(256), 0, (hipStream_t)s, t, B, out);
+    else hipLaunchKernelGGL(k_pack_masks_ragged<float>, dim3((unsigned)t.block_first[B]), dim3(256), 0, (hipStream_t)s, t, B, out);
+    return ym_check_launch(what);
 }
 
 extern "C" int ym_unpack_masks(const uint64_t* bits, int n, int H, int W, float* masks, ym_stream_t s) {

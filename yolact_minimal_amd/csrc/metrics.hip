@@ -111,18 +111,21 @@ __global__ __launch_bounds__(512) void k_mask_inter(const float* __restrict__ A,
 // loop.  PWORDS words per chunk: 480x640 masks = 4800 words = 240 chunks, one round over the 256 CUs.  Same partial-count layout,
 // same finalize kernel, no global atomics.
 constexpr int PWORDS = 20;
-__global__ __launch_bounds__(512) void k_mask_inter_packed(const unsigned long long* __restrict__ A, int n,
-                                                           const unsigned long long* __restrict__ Bm, int g, long long Pw,
-                                                           int* __restrict__ inter, int* __restrict__ area_a, int* __restrict__ area_b) {
+// One workgroup's share: chunk `chunk` of the rows, gt group `gy`.  `n` rows of A are loaded and paired (the ragged stage passes an
+// image's count here); `nstride` >= n is the row count the partial arrays are laid out for.  The ONE pair loop on bit rows:
+// k_mask_inter_packed and k_eval_inter_ragged both call it.
+__device__ __forceinline__ void inter_packed_chunk(const unsigned long long* __restrict__ A, int n, int nstride,
+                                                   const unsigned long long* __restrict__ Bm, int g, long long Pw, int chunk, int gy,
+                                                   int* __restrict__ inter, int* __restrict__ area_a, int* __restrict__ area_b) {
     __shared__ unsigned long long sa[MAXR][PWORDS + 1];
     __shared__ unsigned long long sb[MAXR][PWORDS + 1];
     const int tid = threadIdx.x;
-    const long long w0 = (long long)blockIdx.x * PWORDS;
+    const long long w0 = (long long)chunk * PWORDS;
     const int nwd = (int)min((long long)PWORDS, Pw - w0);
-    const int g0 = blockIdx.y * MAXR, gn = min(MAXR, g - g0);
-    inter += (size_t)blockIdx.x * n * g;
-    area_a += (size_t)blockIdx.x * n;
-    area_b += (size_t)blockIdx.x * g;
+    const int g0 = gy * MAXR, gn = min(MAXR, g - g0);
+    inter += (size_t)chunk * nstride * g;
+    area_a += (size_t)chunk * nstride;
+    area_b += (size_t)chunk * g;
     for (int a0 = 0; a0 < n; a0 += MAXR) {
         const int an = min(MAXR, n - a0);
         __syncthreads();
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(512) void k_mask_inter_packed(const unsigned long l
             int c = 0;
 #pragma unroll
             for (int q = 0; q < PWORDS; ++q) c += __popcll(w[q]);
-            if (is_a) { if (blockIdx.y == 0) area_a[a0 + rr] = c; }
+            if (is_a) { if (gy == 0) area_a[a0 + rr] = c; }
             else area_b[g0 + rr - an] = c;
         }
         for (int pr = tid; pr < an * gn; pr += 512) {
@@ -154,48 +157,68 @@ __global__ __launch_bounds__(512) void k_mask_inter_packed(const unsigned long l
     }
 }
 
+__global__ __launch_bounds__(512) void k_mask_inter_packed(const unsigned long long* __restrict__ A, int n,
+                                                           const unsigned long long* __restrict__ Bm, int g, long long Pw,
+                                                           int* __restrict__ inter, int* __restrict__ area_a, int* __restrict__ area_b) {
+    inter_packed_chunk(A, n, n, Bm, g, Pw, blockIdx.x, blockIdx.y, inter, area_a, area_b);
+}
+
 // sum the per-chunk partials (exact integers) and apply the reference's formula; 64 pairs x FSL chunk slices per workgroup (the
 // slices' loads are independent: 4 slices took 16.5 us for 300 chunks -- a serial chain of 75 L2 round trips per thread)
 constexpr int FSL = 16;
-__global__ __launch_bounds__(64 * FSL) void k_mask_iou_finalize(const int* __restrict__ inter, const int* __restrict__ area_a,
-                                                                const int* __restrict__ area_b, int chunks, int n, int g, float* __restrict__ iou) {
+// Pair (i, j) of one 64-pair workgroup: the chunk sums of its three counts, split over the FSL slices and joined in LDS (every
+// thread of the workgroup calls it; `live` = the pair exists).  The result is the reference's quotient, valid in slice 0.  `nstride`
+// = the row count the partials are laid out for (inter_packed_chunk).  The ONE statement of the mask IoU's finalize step.
+__device__ __forceinline__ float mask_iou_from_partials(const int* __restrict__ inter, const int* __restrict__ area_a,
+                                                        const int* __restrict__ area_b, int chunks, int nstride, int g, int i, int j,
+                                                        bool live) {
     __shared__ int s_i[FSL][64], s_a[FSL][64], s_b[FSL][64];
     const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + lane;
     int it = 0, aa = 0, ab = 0;
-    if (e < n * g) {
-        const int i = e / g, j = e - i * g;
+    if (live) {
 #pragma unroll 4
         for (int c = sl; c < chunks; c += FSL) {
-            it += inter[(size_t)c * n * g + e];
-            aa += area_a[(size_t)c * n + i];
+            it += inter[((size_t)c * nstride + i) * g + j];
+            aa += area_a[(size_t)c * nstride + i];
             ab += area_b[(size_t)c * g + j];
         }
     }
     s_i[sl][lane] = it; s_a[sl][lane] = aa; s_b[sl][lane] = ab;
     __syncthreads();
-    if (sl == 0 && e < n * g) {
-        int ti = 0, ta = 0, tb = 0;
+    int ti = 0, ta = 0, tb = 0;
+    if (sl == 0) {
 #pragma unroll
         for (int q = 0; q < FSL; ++q) { ti += s_i[q][lane]; ta += s_a[q][lane]; tb += s_b[q][lane]; }
-        const float fi = (float)ti, fa = (float)ta, fb = (float)tb;
-        iou[e] = __fdiv_rn(fi, (fa + fb) - fi);          // inter / ((area1.t() + area2) - inter); 0/0 -> NaN like the reference
     }
+    const float fi = (float)ti, fa = (float)ta, fb = (float)tb;
+    return __fdiv_rn(fi, (fa + fb) - fi);                // inter / ((area1.t() + area2) - inter); 0/0 -> NaN like the reference
 }
 
-__global__ void k_box_iou(const float* __restrict__ a, const float* __restrict__ b, int n, int g, float* __restrict__ iou) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * g) return;
-    const int i = e / g, j = e - i * g;
-    const float* p = a + (size_t)i * 4;
-    const float* q = b + (size_t)j * 4;
+__global__ __launch_bounds__(64 * FSL) void k_mask_iou_finalize(const int* __restrict__ inter, const int* __restrict__ area_a,
+                                                                const int* __restrict__ area_b, int chunks, int n, int g, float* __restrict__ iou) {
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+    const bool live = e < n * g;
+    const int i = live ? e / g : 0, j = live ? e - i * g : 0;
+    const float v = mask_iou_from_partials(inter, area_a, area_b, chunks, n, g, i, j, live);
+    if (threadIdx.x < 64 && live) iou[e] = v;
+}
+
+// Pixel-box IoU of p = [x1 y1 x2 y2] and q (utils/box_utils.py:8-37).  The ONE statement of the formula.
+__device__ __forceinline__ float box_iou_pair(const float* p, const float* q) {
     float w = fminf(p[2], q[2]) - fmaxf(p[0], q[0]);
     float h = fminf(p[3], q[3]) - fmaxf(p[1], q[1]);
     w = w < 0.f ? 0.f : w;
     h = h < 0.f ? 0.f : h;
     const float inter = w * h;
     const float aa = (p[2] - p[0]) * (p[3] - p[1]), ab = (q[2] - q[0]) * (q[3] - q[1]);
-    iou[e] = __fdiv_rn(inter, (aa + ab) - inter);
+    return __fdiv_rn(inter, (aa + ab) - inter);
+}
+
+__global__ void k_box_iou(const float* __restrict__ a, const float* __restrict__ b, int n, int g, float* __restrict__ iou) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * g) return;
+    const int i = e / g, j = e - i * g;
+    iou[e] = box_iou_pair(a + (size_t)i * 4, b + (size_t)j * 4);
 }
 
 // prep_metrics' matching (utils/common_utils.py:186-216): block = (iou type, threshold), thread = class.  Predictions are
@@ -243,13 +266,14 @@ __global__ __launch_bounds__(128) void k_match_detections(const float* __restric
 // class are NEIGHBOURING lanes: a wave executes the gt loop of a prediction whenever one of its lanes owns that prediction's class,
 // so with 2T lanes per class a wave holds ~3 classes (T = 10) and walks only their predictions.
 constexpr int EVAL_THREADS = 1024;
-__global__ __launch_bounds__(EVAL_THREADS) void k_eval_match_log(const long long* __restrict__ ids, const float* __restrict__ scores,
-                                                                 const int* __restrict__ count, int n, const float* __restrict__ iou_box,
-                                                                 const float* __restrict__ iou_mask, const float* __restrict__ gt, int g,
-                                                                 const double* __restrict__ thr, int T, int num_classes,
-                                                                 float* __restrict__ log_score, int* __restrict__ log_class,
-                                                                 unsigned* __restrict__ log_flags, unsigned long long* __restrict__ gt_count,
-                                                                 int* __restrict__ class_rows) {
+// (the body of one image's workgroup: k_eval_match_log runs it for its one image, k_eval_match_log_ragged for image blockIdx.x)
+__device__ __forceinline__ void eval_match_log_image(const long long* __restrict__ ids, const float* __restrict__ scores,
+                                                     const int* __restrict__ count, int n, const float* __restrict__ iou_box,
+                                                     const float* __restrict__ iou_mask, const float* __restrict__ gt, int g,
+                                                     const double* __restrict__ thr, int T, int num_classes,
+                                                     float* __restrict__ log_score, int* __restrict__ log_class,
+                                                     unsigned* __restrict__ log_flags, unsigned long long* __restrict__ gt_count,
+                                                     int* __restrict__ class_rows) {
     __shared__ int s_pred[YM_EVAL_MAX_DET];
     __shared__ unsigned s_flags[YM_EVAL_MAX_DET];
     __shared__ int s_gt[MAXG];
@@ -282,6 +306,103 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_eval_match_log(const long long
         log_flags[i] = s_flags[i];
         if (c >= 0) atomicAdd(&class_rows[c], 1);
     }
+}
+
+__global__ __launch_bounds__(EVAL_THREADS) void k_eval_match_log(const long long* __restrict__ ids, const float* __restrict__ scores,
+                                                                 const int* __restrict__ count, int n, const float* __restrict__ iou_box,
+                                                                 const float* __restrict__ iou_mask, const float* __restrict__ gt, int g,
+                                                                 const double* __restrict__ thr, int T, int num_classes,
+                                                                 float* __restrict__ log_score, int* __restrict__ log_class,
+                                                                 unsigned* __restrict__ log_flags, unsigned long long* __restrict__ gt_count,
+                                                                 int* __restrict__ class_rows) {
+    eval_match_log_image(ids, scores, count, n, iou_box, iou_mask, gt, g, thr, T, num_classes, log_score, log_class, log_flags, gt_count,
+                         class_rows);
+}
+
+// ---- the metric stage of a whole request (include/yolact_hip.h "ym_eval_add_ragged_packed") ------------------------------------
+// What the three launches know about their images, BY VALUE in the kernel arguments (like YmRaggedTable).  Image b's partial counts
+// are inter [chunks_b][max_det][g_b], area_a [chunks_b][max_det], area_b [chunks_b][g_b] ints at part_off[b] of the workspace
+// (chunks_b = chunk_first[b + 1] - chunk_first[b]); its IoUs are box [max_det][g_b], then mask [max_det][g_b] floats at iou_off[b].
+// An image that is padding, or has no ground truth, owns no chunk.
+struct EvalRaggedTable {
+    int chunk_first[YM_RAGGED_MAX_IMAGES + 1];   // prefix sum of ceil(words_b / PWORDS): which image a workgroup of the first launch serves
+    int gt_first[YM_RAGGED_MAX_IMAGES + 1];      // first row of image b in `gt` (and g_b as the difference)
+    int words[YM_RAGGED_MAX_IMAGES];             // img_h_b * ceil(img_w_b / 64)
+    int img_h[YM_RAGGED_MAX_IMAGES], img_w[YM_RAGGED_MAX_IMAGES];
+    long long det_off[YM_RAGGED_MAX_IMAGES], gt_off[YM_RAGGED_MAX_IMAGES];   // words from det_bits / gt_bits to the image's block
+    long long part_off[YM_RAGGED_MAX_IMAGES], iou_off[YM_RAGGED_MAX_IMAGES];
+    long long log_row[YM_RAGGED_MAX_IMAGES];     // image_index * max_det; < 0 = padding
+};
+
+__device__ __forceinline__ int eval_ragged_count(const int* __restrict__ counts, int b, int max_det) { return min(max(counts[b], 0), max_det); }
+
+// grid: (all chunks of all images, the largest number of gt groups of an image).  Rows at or past the image's count are not loaded.
+__global__ __launch_bounds__(512) void k_eval_inter_ragged(const unsigned long long* __restrict__ det_bits,
+                                                           const unsigned long long* __restrict__ gt_bits, const int* __restrict__ counts,
+                                                           int B, int max_det, const EvalRaggedTable t, int* __restrict__ part) {
+    int b = 0;
+    while (b + 1 < B && (int)blockIdx.x >= t.chunk_first[b + 1]) ++b;
+    const int g = t.gt_first[b + 1] - t.gt_first[b];
+    if ((int)blockIdx.y * MAXR >= g) return;
+    const int n = eval_ragged_count(counts, b, max_det);
+    if (n == 0) return;
+    const int chunks = t.chunk_first[b + 1] - t.chunk_first[b];
+    int* inter = part + t.part_off[b];
+    int* area_a = inter + (size_t)chunks * max_det * g;
+    int* area_b = area_a + (size_t)chunks * max_det;
+    inter_packed_chunk(det_bits + t.det_off[b], n, max_det, gt_bits + t.gt_off[b], g, (long long)t.words[b], (int)blockIdx.x - t.chunk_first[b],
+                       (int)blockIdx.y, inter, area_a, area_b);
+}
+
+// grid: (groups of 64 pairs of the largest image, B).  Pair e = i * g_b + j, i below the image's count: slice 0 writes the mask IoU
+// from the partial counts, slice 1 the box IoU of (float)boxes_px against the gt box scaled in fp32 (one rounding per product: what
+// the in-place `gt_boxes[:, 0::2] *= width` of DeviceAPData.add leaves; this file is compiled without contraction).
+__global__ __launch_bounds__(64 * FSL) void k_eval_iou_ragged(const int* __restrict__ boxes_px, const float* __restrict__ gt,
+                                                              const int* __restrict__ counts, int max_det, const EvalRaggedTable t,
+                                                              const int* __restrict__ part, float* __restrict__ iou) {
+    const int b = blockIdx.y;
+    const int g = t.gt_first[b + 1] - t.gt_first[b];
+    if (t.log_row[b] < 0 || g == 0) return;
+    const int n = eval_ragged_count(counts, b, max_det);
+    if ((int)blockIdx.x * 64 >= n * g) return;              // (n == 0 as well)
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63), sl = threadIdx.x >> 6;
+    const bool live = e < n * g;
+    const int i = live ? e / g : 0, j = live ? e - i * g : 0;
+    const int chunks = t.chunk_first[b + 1] - t.chunk_first[b];
+    const int* inter = part + t.part_off[b];
+    const int* area_a = inter + (size_t)chunks * max_det * g;
+    const int* area_b = area_a + (size_t)chunks * max_det;
+    float* iou_box = iou + t.iou_off[b];
+    float* iou_mask = iou_box + (size_t)max_det * g;
+    const float v = mask_iou_from_partials(inter, area_a, area_b, chunks, max_det, g, i, j, live);
+    if (sl == 0 && live) iou_mask[e] = v;
+    if (sl == 1 && live) {
+        const int* pb = boxes_px + ((size_t)b * max_det + i) * 4;
+        const float* qb = gt + (size_t)(t.gt_first[b] + j) * 5;
+        const float fw = (float)t.img_w[b], fh = (float)t.img_h[b];
+        const float p[4] = {(float)pb[0], (float)pb[1], (float)pb[2], (float)pb[3]};
+        const float q[4] = {qb[0] * fw, qb[1] * fh, qb[2] * fw, qb[3] * fh};
+        iou_box[e] = box_iou_pair(p, q);
+    }
+}
+
+// grid: B.  Workgroup b is k_eval_match_log's workgroup for image b: its max_det padded rows, its count, its rows of `gt`, its
+// IoUs from the launch before, its log rows.  A padding entry exits at once.
+__global__ __launch_bounds__(EVAL_THREADS) void k_eval_match_log_ragged(const long long* __restrict__ ids, const float* __restrict__ scores,
+                                                                        const int* __restrict__ counts, int max_det,
+                                                                        const EvalRaggedTable t, const float* __restrict__ iou,
+                                                                        const float* __restrict__ gt, const double* __restrict__ thr, int T,
+                                                                        int num_classes, float* __restrict__ log_score,
+                                                                        int* __restrict__ log_class, unsigned* __restrict__ log_flags,
+                                                                        unsigned long long* __restrict__ gt_count, int* __restrict__ class_rows) {
+    const int b = blockIdx.x;
+    const long long row = t.log_row[b];
+    if (row < 0) return;
+    const int g = t.gt_first[b + 1] - t.gt_first[b];
+    const float* iou_box = iou + t.iou_off[b];
+    eval_match_log_image(ids + (size_t)b * max_det, scores + (size_t)b * max_det, counts + b, max_det, iou_box, iou_box + (size_t)max_det * g,
+                         gt + (size_t)t.gt_first[b] * 5, g, thr, T, num_classes, log_score + row, log_class + row, log_flags + row,
+                         gt_count, class_rows);
 }
 
 // The flags in sorted order, once: the 2T workgroups of a class then read consecutive words.
@@ -519,6 +640,124 @@ extern "C" int ym_eval_match_log(const int64_t* ids, const float* scores, const 
                        count, n, iou_box, iou_mask, gt, g, thresholds, T, num_classes, log_score + log_offset, log_class + log_offset,
                        log_flags + log_offset, reinterpret_cast<unsigned long long*>(gt_count), class_rows);
     return ym_check_launch("eval_match_log");
+}
+
+// Where image b's partial counts (ints) and IoUs (floats, behind all the partials) lie in the workspace of ym_eval_add_ragged_packed:
+// a function of the sizes alone, so a padding entry keeps its (unused) room and the workspace query needs no image_index.
+// false for arguments the entry refuses.
+static bool eval_ragged_layout(const ym_ragged_image* det_blocks, const int32_t* gt_first, int B, int max_det, long long* part_off,
+                               long long* iou_off, size_t* part_ints, size_t* iou_floats) {
+    if (!det_blocks || !gt_first || B < 1 || B > YM_RAGGED_MAX_IMAGES || max_det < 1 || max_det > YM_EVAL_MAX_DET) return false;
+    size_t parts = 0, ious = 0;
+    for (int b = 0; b < B; ++b) {
+        const long long g = (long long)gt_first[b + 1] - gt_first[b];
+        if (g < 0 || g > MAXG || det_blocks[b].img_h <= 0 || det_blocks[b].img_w <= 0) return false;
+        const long long words = (long long)det_blocks[b].img_h * (long long)ym_mask_row(true, det_blocks[b].img_w);
+        if (words >= (1ll << 18)) return false;
+        const size_t chunks = (size_t)((words + PWORDS - 1) / PWORDS);
+        if (part_off) part_off[b] = (long long)parts;
+        if (iou_off) iou_off[b] = (long long)ious;
+        if (g > 0) {
+            parts += chunks * ((size_t)max_det * g + max_det + g);
+            ious += 2 * (size_t)max_det * g;
+        }
+    }
+    *part_ints = parts;
+    *iou_floats = ious;
+    return true;
+}
+
+extern "C" size_t ym_eval_add_ragged_workspace_bytes(const ym_ragged_image* det_blocks, const int32_t* gt_first, int B, int max_det) {
+    size_t parts = 0, ious = 0;
+    if (!eval_ragged_layout(det_blocks, gt_first, B, max_det, nullptr, nullptr, &parts, &ious)) return 0;
+    return (parts + ious) * sizeof(int) + 256;
+}
+
+extern "C" int ym_eval_add_ragged_packed(const int64_t* ids, const float* scores, const int32_t* boxes_px, const int32_t* counts, int B,
+                                         int max_det, const uint64_t* det_bits, const ym_ragged_image* det_blocks, const float* gt,
+                                         const int32_t* gt_first, const uint64_t* gt_bits, const ym_ragged_image* gt_blocks,
+                                         const int64_t* image_index, const double* thresholds, int T, int num_classes, float* log_score,
+                                         int32_t* log_class, uint32_t* log_flags, int64_t log_rows, int64_t* gt_count, int32_t* class_rows,
+                                         void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    const char* what = "eval_add_ragged_packed";
+    YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
+    YM_REQUIRE(max_det >= 1 && max_det <= YM_EVAL_MAX_DET, "%s: need 0 < max_det <= %d, got %d", what, YM_EVAL_MAX_DET, max_det);
+    YM_REQUIRE(T >= 1 && T <= YM_EVAL_MAX_THRESHOLDS, "%s: 1 .. %d thresholds (2T flag bits per row), got %d", what,
+               YM_EVAL_MAX_THRESHOLDS, T);
+    YM_REQUIRE(num_classes > 0, "%s: num_classes = %d", what, num_classes);
+    YM_REQUIRE(ids && scores && boxes_px && counts && det_bits && det_blocks && gt_first && gt_blocks && image_index && thresholds &&
+                   log_score && log_class && log_flags && gt_count && class_rows && workspace,
+               "%s: null pointer", what);
+    YM_REQUIRE(gt_first[0] >= 0, "%s: gt_first[0] = %d", what, gt_first[0]);
+    for (int b = 0; b < B; ++b) {
+        const long long g = (long long)gt_first[b + 1] - gt_first[b];
+        YM_REQUIRE(g >= 0, "%s: gt_first is not ascending at image %d", what, b);
+        YM_REQUIRE(g <= MAXG, "%s: image %d has %lld gt instances, at most %d are matched", what, b, g, MAXG);
+    }
+    YM_REQUIRE(gt_first[B] == 0 || (gt && gt_bits), "%s: null pointer", what);
+    const int rc_det = ym_check_ragged_table(what, det_blocks, B, 8, [&](const ym_ragged_image& im) {
+        return (int64_t)max_det * im.img_h * (int64_t)ym_mask_row(true, im.img_w);
+    });
+    if (rc_det != YM_OK) return rc_det;
+    const int rc_gt = ym_check_ragged_table(what, gt_blocks, B, 8, [&](const ym_ragged_image& im) {
+        const int64_t b = &im - gt_blocks;
+        return (int64_t)(gt_first[b + 1] - gt_first[b]) * im.img_h * (int64_t)ym_mask_row(true, im.img_w);
+    });
+    if (rc_gt != YM_OK) return rc_gt;
+    bool any = false, any_gt = false;
+    for (int b = 0; b < B; ++b) {
+        YM_REQUIRE(gt_blocks[b].img_h == det_blocks[b].img_h && gt_blocks[b].img_w == det_blocks[b].img_w,
+                   "%s: image %d: gt masks of %d x %d for detection masks of %d x %d", what, b, gt_blocks[b].img_h, gt_blocks[b].img_w,
+                   det_blocks[b].img_h, det_blocks[b].img_w);
+        YM_REQUIRE((long long)det_blocks[b].img_h * (long long)ym_mask_row(true, det_blocks[b].img_w) < (1ll << 18),
+                   "%s: image %d: need img_h * ceil(img_w / 64) < 2^18 words (exact fp32 counts)", what, b);
+        if (image_index[b] < 0) continue;
+        YM_REQUIRE(image_index[b] < log_rows && (image_index[b] + 1) * max_det <= log_rows,
+                   "%s: image index %lld: its %d rows end past the %lld rows of the log", what, (long long)image_index[b], max_det,
+                   (long long)log_rows);
+        for (int a = 0; a < b; ++a)
+            YM_REQUIRE(image_index[a] != image_index[b], "%s: image index %lld twice in one call", what, (long long)image_index[b]);
+        any = true;
+        any_gt = any_gt || gt_first[b + 1] > gt_first[b];
+    }
+    EvalRaggedTable t = {};
+    size_t parts = 0, ious = 0;
+    YM_REQUIRE(eval_ragged_layout(det_blocks, gt_first, B, max_det, t.part_off, t.iou_off, &parts, &ious), "%s: bad sizes", what);
+    if (workspace_bytes < (parts + ious) * sizeof(int) + 256) { ym_set_error("%s: workspace too small", what); return YM_ENOSPC; }
+    if (!any) return YM_OK;                                  // (padding only)
+    int max_groups = 1, max_pairs = 0;
+    for (int b = 0; b < B; ++b) {
+        const int g = gt_first[b + 1] - gt_first[b];
+        const bool live = image_index[b] >= 0;
+        t.gt_first[b] = gt_first[b];
+        t.img_h[b] = det_blocks[b].img_h;
+        t.img_w[b] = det_blocks[b].img_w;
+        t.words[b] = det_blocks[b].img_h * (int)ym_mask_row(true, det_blocks[b].img_w);
+        t.det_off[b] = det_blocks[b].offset;
+        t.gt_off[b] = gt_blocks[b].offset;
+        t.log_row[b] = live ? image_index[b] * max_det : -1;
+        t.chunk_first[b + 1] = t.chunk_first[b] + (live && g > 0 ? ym_cdiv(t.words[b], PWORDS) : 0);
+        if (live && g > 0) {
+            max_groups = max_groups > ym_cdiv(g, MAXR) ? max_groups : ym_cdiv(g, MAXR);
+            max_pairs = max_pairs > max_det * g ? max_pairs : max_det * g;
+        }
+    }
+    t.gt_first[B] = gt_first[B];
+    for (int b = B; b < YM_RAGGED_MAX_IMAGES; ++b) { t.chunk_first[b + 1] = t.chunk_first[B]; t.gt_first[b + 1] = gt_first[B]; t.log_row[b] = -1; }
+    hipStream_t st = (hipStream_t)s;
+    int* part = (int*)workspace;
+    float* iou = (float*)workspace + parts;
+    if (any_gt) {
+        hipLaunchKernelGGL(k_eval_inter_ragged, dim3((unsigned)t.chunk_first[B], (unsigned)max_groups), dim3(512), 0, st,
+                           reinterpret_cast<const unsigned long long*>(det_bits), reinterpret_cast<const unsigned long long*>(gt_bits), counts, B,
+                           max_det, t, part);
+        hipLaunchKernelGGL(k_eval_iou_ragged, dim3((unsigned)ym_cdiv(max_pairs, 64), (unsigned)B), dim3(64 * FSL), 0, st, boxes_px, gt, counts,
+                           max_det, t, (const int*)part, iou);
+    }
+    hipLaunchKernelGGL(k_eval_match_log_ragged, dim3((unsigned)B), dim3(EVAL_THREADS), 0, st, reinterpret_cast<const long long*>(ids), scores,
+                       counts, max_det, t, (const float*)iou, gt, thresholds, T, num_classes, log_score, log_class, log_flags,
+                       reinterpret_cast<unsigned long long*>(gt_count), class_rows);
+    return ym_check_launch(what);
 }
 
 extern "C" size_t ym_eval_ap_workspace_bytes(int64_t rows) { return rows > 0 ? (size_t)rows * sizeof(uint32_t) : 0; }

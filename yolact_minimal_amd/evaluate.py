@@ -4,7 +4,8 @@ device-resident accumulator (`utils/device_metrics.DeviceAPData`).
 The reference evaluates one image at a time and its `prep_metrics` reads the detections on the host, so every image is a
 synchronisation point.  Here every image is one pipeline request (forward -> nms -> after_nms on the slot's stream) whose consumer
 is `DeviceAPData.add(..., image_index=i)` on that same stream: nothing of an image is read on the host, and the log keeps the
-sample order whatever order the slots finish in.  The one download is `calc_map`'s AP grid at the end.
+sample order whatever order the slots finish in.  The one download is `calc_map`'s AP grid at the end.  Requests of several images
+(`batch` > 1) add image by image by default, or with `batched_metrics=True` through one `DeviceAPData.add_batch` per request.
 """
 import torch
 
@@ -28,9 +29,10 @@ def eval_pipeline(net, cfg, img, img_h, img_w, depth=4, packed_masks=True, batch
     return pipe
 
 
-def _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe):
+def _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe, batched_metrics=False):
     """`batch` consecutive samples per request, every image at its own output size; a short last group is padded by repeating its
-    last image, and a padded entry is never added."""
+    last image, and a padded entry is never added.  `batched_metrics`: one `DeviceAPData.add_batch` per request instead of one
+    `add` per image (packed masks only)."""
     device = acc.device
     group = []
 
@@ -49,6 +51,10 @@ def _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe):
             slot_stream = torch.cuda.current_stream(device)
             for t in held:                                      # made on the caller's stream, read on the slot's
                 t.record_stream(slot_stream)
+            if batched_metrics:                                 # (the whole request, padding marked by an index of None)
+                acc.add_batch(ids, scores, boxes_px, masks, counts, [e[2] for e in entries], [e[3] for e in entries], sizes,
+                              [first + b if b < real else None for b in range(batch)])
+                return
             for b in range(real):                               # (one image's padded rows and its count: what `add` takes)
                 acc.add(ids[b], scores[b], boxes_px[b], masks[b], counts[b:b + 1], gts[b][0], gts[b][1], sizes[b][0], sizes[b][1],
                         image_index=first + b)
@@ -66,18 +72,22 @@ def _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe):
     return pipe
 
 
-def evaluate_pipelined(net, cfg, samples, depth=4, packed_masks=True, step=None, pipe=None, batch=1):
+def evaluate_pipelined(net, cfg, samples, depth=4, packed_masks=True, step=None, pipe=None, batch=1, batched_metrics=False):
     """`samples` yields eval.py's `(img [1,3,H,W], gt [g,5], gt_masks [g,h,w], img_h, img_w)`; all images share one input size.
     `pipe`: an idle pipeline of `eval_pipeline` to run on (`depth`, `packed_masks` and `batch` are then the pipeline's); by default
     one is built on the first sample.  `batch` > 1: `batch` consecutive samples form one request, each image post-processed at its own
     `(img_h, img_w)` (`after_nms_batch` with per-image sizes) and added on the slot's stream image by image; a short last request is
-    padded with copies of its last image, which are not added.  Returns ((table text, box row, mask row), the DeviceAPData)."""
+    padded with copies of its last image, which are not added.  `batched_metrics=True` (with `batch` > 1 and packed masks; dense
+    masks raise before anything runs): the metric stage of a request is ONE `DeviceAPData.add_batch` on the slot's stream instead
+    of one `add` per image; the log is the same.  Returns ((table text, box row, mask row), the DeviceAPData)."""
     device = next(net.parameters()).device
-    acc = DeviceAPData(len(cfg.class_names), IOU_THRES, device, max_det=cfg.max_detections)
     if pipe is not None:
-        batch = pipe.batch
+        batch, packed_masks = pipe.batch, pipe.packed_masks
+    if batched_metrics and batch > 1 and not packed_masks:
+        raise RuntimeError('evaluate_pipelined: batched_metrics=True needs packed masks (the batched metric stage is packed-only)')
+    acc = DeviceAPData(len(cfg.class_names), IOU_THRES, device, max_det=cfg.max_detections)
     if batch > 1:
-        pipe = _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe)
+        pipe = _evaluate_batched(net, cfg, samples, acc, batch, depth, packed_masks, pipe, batched_metrics)
         if pipe is not None:
             pipe.drain()
         return acc.calc_map(step), acc

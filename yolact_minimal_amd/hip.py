@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     'ym_ann_to_mask_ragged_workspace_bytes', 'ym_ann_to_mask_ragged',
     'ym_val_preprocess_window', 'ym_after_nms_window_workspace_bytes', 'ym_after_nms_window', 'ym_after_nms_window_packed',
     'ym_mask_loss_batch_window', 'ym_mask_loss_fwd_bwd_window', 'ym_train_aug_image_batch_window', 'ym_train_aug_masks_batch_window',
+    'ym_pack_masks_ragged', 'ym_eval_add_ragged_workspace_bytes', 'ym_eval_add_ragged_packed',
 )
 
 
@@ -326,6 +327,13 @@ def lib():
         L.ym_eval_ap_workspace_bytes.argtypes = [i64]
         L.ym_eval_ap_workspace_bytes.restype = sz
         L.ym_eval_ap.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, vp, vp, sz, vp]
+        L.ym_pack_masks_ragged.argtypes = [ctypes.POINTER(ctypes.c_void_p), i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(RaggedImage),
+                                           i32, vp, vp]
+        L.ym_eval_add_ragged_workspace_bytes.argtypes = [ctypes.POINTER(RaggedImage), ctypes.POINTER(ctypes.c_int32), i32, i32]
+        L.ym_eval_add_ragged_workspace_bytes.restype = sz
+        L.ym_eval_add_ragged_packed.argtypes = [vp, vp, vp, vp, i32, i32, vp, ctypes.POINTER(RaggedImage), vp, ctypes.POINTER(ctypes.c_int32),
+                                                vp, ctypes.POINTER(RaggedImage), ctypes.POINTER(ctypes.c_int64), vp, i32, i32, vp, vp, vp,
+                                                i64, vp, vp, vp, sz, vp]
         L.ym_coco_iou_box.argtypes = [vp, i32, vp, i32, vp, vp, vp]
         L.ym_coco_iou_mask_packed.argtypes = [vp, i32, vp, i32, i64, vp, vp, vp, vp]
         L.ym_coco_match_log.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
@@ -340,7 +348,8 @@ def lib():
                             'ym_ann_to_mask_workspace_bytes', 'ym_draw_workspace_bytes', 'ym_mask_iou_packed_workspace_bytes',
                             'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes',
                             'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes',
-                            'ym_ann_to_mask_ragged_workspace_bytes', 'ym_after_nms_window_workspace_bytes'):
+                            'ym_ann_to_mask_ragged_workspace_bytes', 'ym_after_nms_window_workspace_bytes',
+                            'ym_eval_add_ragged_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

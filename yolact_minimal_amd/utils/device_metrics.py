@@ -6,7 +6,8 @@ flags back and extends 2 x T x classes python lists, so every image is a synchro
 several requests in flight.  `DeviceAPData` keeps what those lists hold in a device LOG instead (`include/yolact_hip.h`,
 "device-resident mAP accumulator"): one row per (image slot, detection row) with the score, the class (-1 = no data point) and the
 2T match flags, plus the ground-truth instances per class.  `add` is `ym_mask_iou(_packed)` + `ym_box_iou` + `ym_eval_match_log`
-on the caller's stream; `calc_map` is one stable device sort, `ym_eval_ap` and ONE download of the AP grid.  `to_ap_data()` rebuilds
+on the caller's stream (`add_batch`: the images of one mixed-size request in one `ym_eval_add_ragged_packed` call, packed masks
+only, same log); `calc_map` is one stable device sort, `ym_eval_ap` and ONE download of the AP grid.  `to_ap_data()` rebuilds
 the host accumulator from the log (the bridge to everything that takes `ap_data`).
 
 Not covered: merging accumulators across ranks, more than 512 gt instances per image, NaN scores as data points (a NaN below the
@@ -139,6 +140,140 @@ class DeviceAPData:
             self._seen.add(index)
             self._writers[cur.cuda_stream] = cur
         return index
+
+    def add_batch(self, ids, scores, boxes_px, masks, counts, gts, gt_masks, sizes, image_indices, mask_table=None):
+        """One request of B <= 32 images of different sizes in ONE call (`ym_eval_add_ragged_packed`: at most three launches, plus one
+        `torch.cat` of the gt rows and one `ym_pack_masks_ragged` launch when gt masks arrive dense); the log and the counters end
+        up exactly as after `add` on each image.  Runs on the current stream; no host read.
+          ids / scores `[B, max_det]`, boxes_px `[B, max_det, 4]`, counts int32 `[B]`: `after_nms_batch(..., sync=False)` rows, with
+          `max_det` the accumulator's;
+          masks: the list of B `PackedMasks` views that `after_nms_batch(dets, hs, ws, ..., packed=True)` returns -- or, with
+          `mask_table` (their `hip.ragged_table`), view 0 alone: the two forms `draw_batch` and its launch take.  Dense masks raise;
+          gts: B tensors `[g_b, 5]` (normalised boxes, class).  Unlike `add`, this call does NOT scale them in place: the kernel
+          scales the boxes as it reads them, to the same fp32 values;
+          gt_masks: B dense `[g_b, h_b, w_b]` tensors (float32 / uint8 / bool) or `PackedMasks`;
+          sizes: B `(h_b, w_b)`; image_indices: B image slots, `None` = the entry is padding (its gts and gt_masks are not looked at).
+        A refused call (bad arguments, more than 512 gt instances in an image) leaves the accumulator as it was."""
+        from .draw import _ragged_mask_table
+        what = 'DeviceAPData.add_batch'
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        batch, md = len(sizes), self.max_det
+        if not 1 <= batch <= hip.RAGGED_MAX_IMAGES:
+            raise RuntimeError(f'{what}: 1 .. {hip.RAGGED_MAX_IMAGES} images per call, got {batch}')
+        if tuple(ids.shape) != (batch, md) or tuple(scores.shape) != (batch, md) or tuple(boxes_px.shape) != (batch, md, 4) or \
+                counts is None or counts.numel() != batch:
+            raise RuntimeError(f'{what}: ids / scores [{batch}, {md}], boxes_px [{batch}, {md}, 4] and {batch} counts expected (max_det is the '
+                               f"accumulator's), got {tuple(ids.shape)} / {tuple(scores.shape)} / {tuple(boxes_px.shape)}")
+        if len(gts) != batch or len(gt_masks) != batch or len(image_indices) != batch:
+            raise RuntimeError(f'{what}: {batch} sizes but {len(gts)} gts / {len(gt_masks)} gt_masks / {len(image_indices)} image indices')
+        if mask_table is None:
+            first = masks[0] if isinstance(masks, (list, tuple)) and len(masks) else masks
+            if not isinstance(first, PackedMasks):
+                raise RuntimeError(f'{what}: the batched metric stage takes packed masks only (after_nms_batch(..., packed=True))')
+            masks, mask_table = _ragged_mask_table(masks, sizes, md, what)
+        elif not isinstance(masks, PackedMasks):
+            raise RuntimeError(f'{what}: the batched metric stage takes packed masks only (after_nms_batch(..., packed=True))')
+        index = [-1 if i is None else int(i) for i in image_indices]
+        live = [i for i in index if i >= 0]
+        if any(i < 0 for i, given in zip(index, image_indices) if given is not None) or len(set(live)) != len(live) or \
+                any(i in self._seen for i in live):
+            raise RuntimeError(f'{what}: image indices {live} are negative, repeated or were added before')
+        if not live:
+            return []
+        gt_rows, gt_first = [], [0]
+        for b in range(batch):
+            g = 0
+            if index[b] >= 0:
+                gt = gts[b]
+                if gt.dim() != 2 or (gt.shape[0] and gt.shape[1] != 5):
+                    raise RuntimeError(f'{what}: image {b}: gt [g, 5] expected, got {tuple(gt.shape)}')
+                g = int(gt.shape[0])
+                if len(gt_masks[b]) != g:
+                    raise RuntimeError(f'{what}: image {b}: {g} gt instances but {len(gt_masks[b])} gt masks')
+                if g:
+                    gt_rows.append(gt if gt.dtype == torch.float32 else gt.float())
+            gt_first.append(gt_first[-1] + g)
+        L = hip.lib()
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            first_c = (ctypes.c_int32 * (batch + 1))(*gt_first)
+            index_c = (ctypes.c_int64 * batch)(*index)
+            nbytes = L.ym_eval_add_ragged_workspace_bytes(mask_table, first_c, batch, md)
+            if nbytes == 0:
+                raise RuntimeError(f'{what}: ym_eval_add_ragged_workspace_bytes refuses these sizes (at most 512 gt instances per image and '
+                                   f'h * ceil(w / 64) < 2^18 words per mask): {sizes}, gt rows {gt_first}')
+            gt_all = (gt_rows[0].contiguous() if len(gt_rows) == 1 else torch.cat(gt_rows, 0)) if gt_rows else None
+            gt_bits, gt_table, held = self._gt_blocks(gt_masks, sizes, gt_first, what)   # (`held`: alive until the launch is enqueued)
+            from .output_utils import _scratch
+            ws = _scratch(self.device, nbytes)
+            # (the log grows for the largest index first; like `add`, the indices are consumed only behind the launch that writes them)
+            if max(live) >= self.capacity:
+                cap = self.capacity
+                while cap <= max(live):
+                    cap *= 2
+                self._grow(cap)
+            elif self._grown is not None and cur.cuda_stream not in self._synced:
+                cur.wait_event(self._grown)
+                self._synced.add(cur.cuda_stream)
+            hip.check(L.ym_eval_add_ragged_packed(
+                hip.ptr(ids, torch.int64), hip.ptr(scores), hip.ptr(boxes_px, torch.int32), hip.ptr(counts, torch.int32), batch, md,
+                hip.ptr(masks.bits, torch.int64), mask_table, hip.ptr(gt_all), first_c,
+                ctypes.c_void_p(gt_bits) if gt_bits else None, gt_table, index_c, hip.ptr(self.thr, torch.float64), len(self.iou_thres),
+                self.num_classes, hip.ptr(self.score), hip.ptr(self.cls, torch.int32), hip.ptr(self.flags, torch.int32),
+                self.capacity * md, hip.ptr(self.gt_count, torch.int64), hip.ptr(self.class_rows, torch.int32),
+                ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()), 'ym_eval_add_ragged_packed')
+            del held
+            self._seen.update(live)
+            self._writers[cur.cuda_stream] = cur
+        return live
+
+    def _gt_blocks(self, gt_masks, sizes, gt_first, what):
+        """The gt masks of a request as `ym_eval_add_ragged_packed` takes them -> (address of `gt_bits`, the `gt_blocks` table, the
+        tensors behind the two).  A
+        `PackedMasks` stays where it is (copied only if it starts at no multiple of 256 bytes); the dense tensors are packed into one
+        new allocation by ONE `ym_pack_masks_ragged` launch.  The table's offsets count from the lowest block."""
+        batch = len(sizes)
+        g = [gt_first[b + 1] - gt_first[b] for b in range(batch)]
+        keep = []
+        at = [0] * batch
+        dense = [b for b in range(batch) if g[b] and not isinstance(gt_masks[b], PackedMasks)]
+        for b in range(batch):
+            if not g[b] or b in dense:
+                continue
+            pm, (h, w) = gt_masks[b], sizes[b]
+            if (pm.height, pm.width) != (h, w) or pm.bits.dim() != 3 or pm.bits.device != self.device:
+                raise RuntimeError(f'{what}: image {b}: packed gt masks {pm.shape} on {pm.device} for a {h} x {w} image on {self.device}')
+            bits = pm.bits.contiguous()
+            if bits.data_ptr() % hip.RAGGED_ALIGN_BYTES:
+                bits = bits.clone()
+            keep.append(bits)
+            at[b] = bits.data_ptr()
+        if dense:
+            src = []
+            for b in dense:
+                m, (h, w) = gt_masks[b], sizes[b]
+                if not torch.is_tensor(m) or not m.is_cuda or m.device != self.device or tuple(m.shape) != (g[b], h, w):
+                    raise RuntimeError(f'{what}: image {b}: gt masks [{g[b]}, {h}, {w}] on {self.device} expected, got '
+                                       f'{tuple(m.shape) if torch.is_tensor(m) else type(m).__name__}')
+                if m.dtype == torch.bool:
+                    m = m.contiguous().view(torch.uint8)
+                src.append(m)
+            u8 = all(m.dtype == torch.uint8 for m in src)
+            src = [m.contiguous() if m.dtype == (torch.uint8 if u8 else torch.float32) else m.float().contiguous() for m in src]
+            rows = iter([g[b] for b in dense])                 # (aligned_layout asks for the extents in image order)
+            offsets, total = hip.aligned_layout(what, [sizes[b] for b in dense], 8, lambda h, w: next(rows) * h * ((w + 63) // 64))
+            packed = torch.empty(max(total, 1), dtype=torch.int64, device=self.device)
+            hip.check(hip.lib().ym_pack_masks_ragged(
+                (ctypes.c_void_p * len(dense))(*[m.data_ptr() for m in src]), int(u8), (ctypes.c_int32 * len(dense))(*[g[b] for b in dense]),
+                hip.ragged_table([sizes[b] for b in dense], offsets), len(dense), hip.ptr(packed, torch.int64), hip.stream_ptr()),
+                'ym_pack_masks_ragged')
+            keep.append(packed)
+            for b, o in zip(dense, offsets):
+                at[b] = packed.data_ptr() + 8 * o
+        used = [a for a in at if a]
+        base = min(used) if used else 0
+        # (an image without ground truth owns an empty block: it may lie anywhere, so it lies at the base)
+        return base, hip.ragged_table(sizes, [(a - base) // 8 if a else 0 for a in at]), keep
 
     # ---- calc_map ----------------------------------------------------------------------------------------------------------
     def _sorted_order(self):

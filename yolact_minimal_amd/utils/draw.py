@@ -180,30 +180,30 @@ def cutout_mattes(ids_p, box_p, mask_p, img_origin, cfg):
     return total[0], objs
 
 
-def _ragged_mask_table(masks, sizes, max_det):
+def _ragged_mask_table(masks, sizes, max_det, what='draw_batch'):
     """The list of per-image mask views of the ragged `after_nms_batch` -> (view 0, the `ym_after_nms_ragged` table rebuilt from the
     views' data pointers relative to view 0).  Raises unless the views are `[max_det, h_b, w_b]` blocks of ONE allocation in
     `ragged_layout` order."""
     from .output_utils import ragged_layout
     if not isinstance(masks, (list, tuple)) or len(masks) != len(sizes):
-        raise RuntimeError(f'draw_batch: with a FrameBatch the masks are the list of {len(sizes)} per-image views that '
+        raise RuntimeError(f'{what}: with images of different sizes the masks are the list of {len(sizes)} per-image views that '
                            f'after_nms_batch(dets, hs, ws, ..., sync=False) returns')
     packed = isinstance(masks[0], PackedMasks)
     words = []
     for b, (m, (h, w)) in enumerate(zip(masks, sizes)):
         if isinstance(m, PackedMasks) != packed:
-            raise RuntimeError('draw_batch: dense and packed mask views in one batch')
+            raise RuntimeError(f'{what}: dense and packed mask views in one batch')
         t = m.bits if packed else m
         if not torch.is_tensor(t) or tuple(m.shape) != (max_det, h, w) or t.dtype != (torch.int64 if packed else torch.float32) or \
                 not t.is_contiguous():
-            raise RuntimeError(f'draw_batch: image {b}: masks {tuple(m.shape)} do not fit {max_det} rows on a {h} x {w} frame')
+            raise RuntimeError(f'{what}: image {b}: masks {tuple(m.shape)} do not fit {max_det} rows on a {h} x {w} frame')
         words.append(t)
     offsets, _ = ragged_layout(sizes, max_det, packed)
     esz = 8 if packed else 4
     base = words[0].data_ptr()
     for b, t in enumerate(words):
         if t.device != words[0].device or t.data_ptr() - base != offsets[b] * esz:
-            raise RuntimeError(f'draw_batch: the mask view of image {b} is not at its place in one ragged_layout allocation')
+            raise RuntimeError(f'{what}: the mask view of image {b} is not at its place in one ragged_layout allocation')
     return masks[0], hip.ragged_table(sizes, offsets)
 
 
