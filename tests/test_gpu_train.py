@@ -608,8 +608,8 @@ def test_train_step_256_well_conditioned_under_split_bf16(golden_dir, monkeypatc
     np.testing.assert_allclose(got, np.array(l64), rtol=256 * 1e-5)
     assert worst[0] <= 1.0, sorted(tail, reverse=True)[:5]
     # the mode under test did run: descriptors of this mode (the cache key carries it), split-bf16 where eligible and nowhere else
-    fwd = [v[0] for k, v in T._desc_cache.items() if k[0] == 'f' and k[-2] == 3]
-    dgrad = [v[0] for k, v in T._desc_cache.items() if k[0] == 'd' and k[14] == 3]
+    fwd = [ent.desc for k, ent in T._desc_cache.items() if k.kind == 'f' and k.mma == 3]
+    dgrad = [ent.desc for k, ent in T._desc_cache.items() if k.kind == 'd' and k.mma == 3]
     assert any(d.mma == 3 for d in fwd) and any(d.mma == 3 and d.transposed for d in dgrad)
     stem = [d for d in fwd if d.Cin == 4]
     assert stem and all(d.mma == 0 for d in stem)

@@ -82,8 +82,9 @@ def test_every_tuned_data_gradient_launch_at_full_size(shard, train_mma, monkeyp
         link.gamma, link.beta, link.relu, link.c, link.m = gamma.data_ptr(), beta.data_ptr(), 1, cin, b * h * h
         T._stats_pool.begin(torch.device(DEV))
         dx = T._conv_dgrad(dz, w, cout_pad, (b, h, h, cin), stride, pad, bn_bwd=link)
-        cached = [v[0] for ck, v in T._desc_cache.items()
-                  if ck[0] == 'd' and ck[2:] == (b, ho, ho, cout_pad, cin, k, k, stride, pad, h, h, False, train_mma, True, bool(T._DETERMINISTIC))]
+        want = T.ConvKey(kind='d', device=None, b=b, h=ho, w=ho, cin=cout_pad, cout=cin, kh=k, kw=k, stride=stride, pad=pad, ho=h, wo=h, act=None,
+                         residual=False, stats=True, segs=None, mma=train_mma, ordered=bool(T._DETERMINISTIC))
+        cached = [ent.desc for ck, ent in T._desc_cache.items() if ck._replace(device=None) == want]
         assert len(cached) == 1, key
         assert cached[0].mma == (train_mma if cached[0].Cin % 32 == 0 and cached[0].kwaves == 0 else 0), (key, cached[0].mma)
         # ---- sampled fp64 reference of dx ----

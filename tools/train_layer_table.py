@@ -58,13 +58,12 @@ def timeit(fn):
 rows = []
 ws_rows = {}
 for key, n in counts.items():
-    ent = T._desc_cache[key]
-    d = ent[0]
-    if key[0] in ('f', 'd'):
+    d = T._desc_cache[key].desc
+    if key.kind in ('f', 'd'):
         M = d.B * d.Ho * d.Wo
         N, K = d.Cout, d.KH * d.KW * d.Cin
         # a dgrad with stride 2 only multiplies 1/4 of the taps per pixel (parity classes)
-        gflop = 2.0 * M * N * K / 1e9 / (d.stride * d.stride if key[0] == 'd' else 1)
+        gflop = 2.0 * M * N * K / 1e9 / (d.stride * d.stride if key.kind == 'd' else 1)
         d.inp, d.weight = opa.data_ptr(), opb.data_ptr()
         for i in range(d.nseg):
             d.seg[i].out = out.data_ptr()
@@ -81,7 +80,7 @@ for key, n in counts.items():
             d.bnb_beta = opb.data_ptr() if d.bnb_beta else None
         us = timeit(lambda: hip.conv2d_fwd(d, big))
         cfg_s = f'{d.tile_m}x{d.tile_n} ks{d.ksplit} st{d.stages} tail{d.tail_tiles}x{d.tail_ksplit}' + (' +bnsum' if d.bn_sum else '') + (' +bnb' if d.bnb_y else '')
-        if (args.tune_ws and key[0] == 'f' and d.bn_sum and (d.KH, d.KW, d.stride, d.pad, d.nseg) == (1, 1, 1, 0, 1) and d.Cin % 32 == 0 and
+        if (args.tune_ws and key.kind == 'f' and d.bn_sum and (d.KH, d.KW, d.stride, d.pad, d.nseg) == (1, 1, 1, 0, 1) and d.Cin % 32 == 0 and
                 d.Cin <= 256 and d.seg[0].act in (0, 1)):
             keep = ConvPlan.of(d)
             best = (us, None)
@@ -97,7 +96,7 @@ for key, n in counts.items():
                 ws_rows[name] = best[1]
                 us = best[0]
                 cfg_s = f'{best[1][0]}x{best[1][1]} st{best[1][4]} (weight-stationary) +bnsum'
-        kind = 'fwd' if key[0] == 'f' else 'dgrad'
+        kind = 'fwd' if key.kind == 'f' else 'dgrad'
         shape = f'M{M} N{N} K{K} k{d.KH} s{d.stride}'
     else:
         M = d.B * d.Ho * d.Wo

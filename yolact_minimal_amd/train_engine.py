@@ -10,6 +10,7 @@ used only as the tape that orders those kernels and hands parameter gradients to
 RCCL) — no ATen convolution, batch-norm or pooling kernel is ever called.  The loss bookkeeping on the [B,N,*]
 head outputs (matching, OHEM ranking, cross-entropy, smooth-L1, mask BCE) is `yolact_minimal_amd/loss.py`.
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -21,8 +22,17 @@ from . import conv_launch, conv_tuning, hip, plan_transfer
 from .conv_plan import ConvPlan
 from .hip import WgradDesc, ACT_NONE, ACT_RELU, ACT_TANH
 
-_scratch = {}
-_desc_cache = {}      # shape key -> (descriptor with every shape-dependent field set, ...): see _conv_forward
+
+# Keys of `_desc_cache` (and of `launch_counts`): everything a descriptor's shape-dependent fields and its plan depend on.  ConvKey: a
+# forward ('f') or data-gradient ('d') launch in the descriptor's terms (a data gradient reads dz [b,h,w,cin], writes dx [b,ho,wo,cout]);
+# `residual`: something is added in the epilogue, `stats`: the caller wants BatchNorm sums from it, `ordered`: as ordered partials,
+# `mma`: YM_TRAIN_MMA.  A field a kind does not use is None: ho, wo of 'f' (they follow from the rest), act and segs of 'd'.
+ConvKey = collections.namedtuple('ConvKey', 'kind device b h w cin cout kh kw stride pad ho wo act residual stats segs mma ordered')
+WgradKey = collections.namedtuple('WgradKey', 'kind device b h w cin_pad cin ho wo cout_pad cout kh kw stride pad segs')      # kind 'w'
+# What a shape's first launch resolved: the descriptor with all but its pointers set, whether its epilogue carries the BatchNorm sums
+# the key asks for, the workspace it needs, the rows of its ordered partials (0: atomics, or no sums).  'w': fuses=False, part_rows=0.
+CacheEntry = collections.namedtuple('CacheEntry', 'desc fuses ws_bytes part_rows')
+_desc_cache = {}      # ConvKey / WgradKey -> CacheEntry: see _launch_conv
 launch_counts = None  # tools/train_layer_table.py sets this to a dict: desc-cache key -> launches (per-shape accounting of a step)
 
 
@@ -71,14 +81,20 @@ def _configure_wgrad(d, key):
         plan.apply(d)
 
 
-def scratch(device, nbytes):
-    """Stream-ordered scratch: one buffer per (device, stream), grown on demand (kernels on one stream never overlap)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _scratch[key] = buf
+_stream_buffers = {}
+
+
+def _stream_buffer(kind, device, n, dtype, least):
+    """Stream-ordered: one buffer per (kind, device, stream), grown on demand (kernels on one stream never overlap)."""
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
+    buf = _stream_buffers.get(key)
+    if buf is None or buf.numel() < n:
+        buf = _stream_buffers[key] = torch.empty(max(n, least), dtype=dtype, device=device)
     return buf
+
+
+def scratch(device, nbytes):
+    return _stream_buffer('scratch', device, nbytes, torch.uint8, 1 << 20)
 
 
 def _ru(x, m):
@@ -94,7 +110,6 @@ def _ru(x, m):
 # loss scalars are not part of that.  A runtime switch like the others here (tools/train_ab.py --set ..:_DETERMINISTIC=1), default
 # from YM_DETERMINISTIC=1; it is part of every `_desc_cache` key it affects.
 _DETERMINISTIC = os.environ.get('YM_DETERMINISTIC', '0') == '1'
-_part_scratch = {}
 
 
 def set_deterministic(on):
@@ -106,13 +121,9 @@ def set_deterministic(on):
 
 
 def _partials(device, rows, c):
-    """Partial-sum buffer of one ordered launch, [rows][2][c] fp64: one per (device, stream), grown on demand, never zeroed (every
-    entry is written); the finish runs right behind the conv on the same stream, so the next launch may reuse it."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    buf = _part_scratch.get(key)
-    if buf is None or buf.numel() < rows * 2 * c:
-        buf = _part_scratch[key] = torch.empty(max(rows * 2 * c, 1 << 16), device=device, dtype=torch.float64)
-    return buf
+    """Partial-sum buffer of one ordered launch, [rows][2][c] fp64, next to its workspace; never zeroed (every entry is written); the
+    finish runs right behind the conv on the same stream, so the next launch may reuse it."""
+    return _stream_buffer('partials', device, rows * 2 * c, torch.float64, 1 << 16)
 
 
 def _finish_partials(part, rows, c, stats):
@@ -184,7 +195,7 @@ class _PackCache:
     def get(self, weight, kind, pad_a, pad_b, rows):
         """Packed image of `weight` (kind 0: forward, 1: dgrad), or None when the parameter is not trainer-owned."""
         owner = self._owner(weight)
-        if owner is None or not weight.is_contiguous() or os.environ.get('YM_PACK_CACHE', '1') == '0':
+        if owner is None or not weight.is_contiguous():
             return None
         cout, cin, kh, kw = weight.shape
         key = (weight.data_ptr(), cout, cin, kh, kw, kind, pad_a, pad_b, rows)
@@ -194,7 +205,6 @@ class _PackCache:
             if e['stamp'] != stamp:
                 self.refresh()
             return e['dst']
-        import weakref
         n = rows * pad_b if kind == 0 else cin * kh * kw * pad_a
         e = dict(ref=weakref.ref(owner),
                  dst=torch.empty(n, device=weight.device, dtype=torch.float32), src=weight.data_ptr(), dims=(cout, cin, kh, kw),
@@ -290,60 +300,80 @@ def _pack_dgrad(weight, cout_pad):
     return wd
 
 
-def _conv_forward(x, wp, k_pad, cout_pad, kh, kw, stride, pad, shift, act, residual=None, bn_stats=None, out=None, segs=None):
-    """`out`: write into this [B,Ho,Wo,cout_pad] tensor instead of a fresh one.  `segs`: [(n0, n1, tensor_ptr, batch_stride, pitch,
-    act)] routes output-channel ranges to separate tensors (the fused prediction head); then nothing is returned."""
-    b, h, w, cin = x.shape
-    ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-    y = None
-    # Everything of the descriptor that depends only on the layer's SHAPE (sizes, tile / split-K choice, workspace size, whether
-    # the BN statistics fuse) is built once per shape and reused: per call only the pointers change.  (The host spends ~35 us per
-    # launch in a step of ~1100 launches; with the convs on the bf16 pipe the step is host-bound.)
-    key = ('f', x.device.index, b, h, w, cin, cout_pad, kh, kw, stride, pad, act, residual is not None, bn_stats is not None,
-           None if segs is None else tuple((n0, n1, bs, pt, a) for n0, n1, _, bs, pt, a in segs), train_mma(),
-           bool(_DETERMINISTIC) and bn_stats is not None)
-    ordered = key[-1]
+def _resolve_conv(d, key, device, bnb):
+    """First use of a forward / data-gradient shape: the plan (not for the stem), the arrival counters and the library's three
+    answers -> the shape's CacheEntry.  `d` carries this call's pointers: the inline sweep (YM_TUNE_TRAIN=1) launches
+    with them and the queries look at their alignment (torch allocations are 256-byte aligned: every later call answers the same).
+    Of the optional operands the queries see no bn_sum / bn_sumsq (chosen from the answers; the planner reads bn_sum only to keep
+    such a launch off the persistent kernel, on which no answer depends) and of bnb_* only bnb_y, in the row and workspace queries
+    of an ordered launch (the planner keeps a launch with bnb_y off the weight-stationary kernel, whose tile and rows differ)."""
+    if d.Cin != 4:
+        shape = (d.B * d.Ho * d.Wo, d.Cout, d.Cin, d.KH, d.stride)
+        _configure_conv(d, plan_transfer.forward_key(*shape, d.nseg, key.residual) if key.kind == 'f' else plan_transfer.dgrad_key(*shape),
+                        stats=key.kind == 'f' and key.stats)
+    d.tile_counters = _tile_counters(device)
+    fuses = key.stats and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
+    d.bn_ordered = int(fuses and key.ordered)
+    if d.bn_ordered and bnb is not None:
+        d.bnb_y = bnb.y
+    part_rows = hip.lib().ym_conv2d_bn_partial_rows(ctypes.byref(d)) if d.bn_ordered else 0
+    return _desc_cache.setdefault(key, CacheEntry(d, fuses, hip.conv_workspace_bytes(d), part_rows))
+
+
+def _launch_conv(key, first, device, inp, weight, outs, shift=None, residual=None, stats=None, bnb=None):
+    """Every forward / data-gradient conv.  What depends only on the layer's SHAPE (sizes, tile / split-K choice, workspace size,
+    whether the BN sums fuse) is built once per `key` and reused: per call only the pointers change.  (The host spends ~35 us per
+    launch in a step of ~1100 launches; with the convs on the bf16 pipe the step is host-bound.)  `first()`: the descriptor of
+    the shape's first use; `outs`: one pointer per output segment; `stats()`: the zeroed [2][Cout] fp64 slice for the BatchNorm
+    sums (of the output; with `bnb`, a BnGradLink, that BatchNorm's backward sums), taken only by a launch that fuses them.  Returns
+    that slice, or None."""
     ent = _desc_cache.get(key)
-    if ent is None:
-        d = conv_launch.conv_desc(b, h, w, cin, cout_pad, kh, kw, stride, pad, ho, wo, k_pad,
-                                  [(0, cout_pad, None, ho * wo * cout_pad, cout_pad, act)] if segs is None else segs)
-    else:
-        d, fused, ws_bytes, part_rows = ent
-    d.inp, d.weight, d.k_pad = x.data_ptr(), wp.data_ptr(), k_pad
+    d = first() if ent is None else ent.desc
+    d.inp, d.weight = inp.data_ptr(), weight.data_ptr()
     d.shift = shift.data_ptr() if shift is not None else None
     d.residual = residual.data_ptr() if residual is not None else None
-    if segs is None:
-        y = out if out is not None else torch.empty(b, ho, wo, cout_pad, device=x.device, dtype=torch.float32)
-        d.seg[0].out = y.data_ptr()
-    else:
-        for i, sg in enumerate(segs):
-            d.seg[i].out = sg[2]
+    for i, out in enumerate(outs):
+        d.seg[i].out = out
     if ent is None:
-        # first use of the shape: the inline sweep (YM_TUNE_TRAIN=1) launches with this call's pointers, and the two queries below
-        # look at their alignment (torch allocations are 256-byte aligned, so every later call answers the same)
-        if cin != 4:
-            _configure_conv(d, plan_transfer.forward_key(b * ho * wo, cout_pad, cin, kh, stride, d.nseg, residual is not None),
-                            stats=bn_stats is not None)
-        d.tile_counters = _tile_counters(x.device)
-        fused = bn_stats is not None and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
-        ws_bytes = hip.conv_workspace_bytes(d)
-        d.bn_ordered = int(fused and ordered)
-        part_rows = hip.lib().ym_conv2d_bn_partial_rows(ctypes.byref(d)) if d.bn_ordered else 0
-        _desc_cache[key] = (d, fused, ws_bytes, part_rows)
-    part = None
-    if fused and part_rows:
-        part = _partials(x.device, part_rows, cout_pad)
-        d.bn_sum, d.bn_sumsq = part.data_ptr(), None
-    elif fused:
-        d.bn_sum, d.bn_sumsq = bn_stats.data_ptr(), bn_stats.data_ptr() + cout_pad * 8
-    ws = scratch(x.device, ws_bytes)
+        ent = _resolve_conv(d, key, device, bnb)
+    sums = part = None
+    if ent.fuses:
+        c = d.Cout
+        sums = stats()
+        d.bn_sum, d.bn_sumsq = sums.data_ptr(), sums.data_ptr() + c * 8
+        if ent.part_rows:
+            part = _partials(device, ent.part_rows, c)
+            d.bn_sum, d.bn_sumsq = part.data_ptr(), None
+        if bnb is not None:
+            d.bnb_y, d.bnb_out, d.bnb_mean, d.bnb_invstd = bnb.y, bnb.out, bnb.mean, bnb.invstd
+            d.bnb_gamma, d.bnb_beta, d.bnb_relu = bnb.gamma, bnb.beta, bnb.relu
+    ws = scratch(device, ent.ws_bytes)
     _count(key)
     hip.conv2d_fwd(d, ws)
     if part is not None:
-        _finish_partials(part, part_rows, cout_pad, bn_stats)
-    if bn_stats is not None:
-        return y, fused
-    return y
+        _finish_partials(part, ent.part_rows, c, sums)
+    return sums
+
+
+def _conv_forward(x, wp, k_pad, cout_pad, kh, kw, stride, pad, shift, act, residual=None, bn_stats=None, out=None, segs=None):
+    """`out`: write into this [B,Ho,Wo,cout_pad] tensor instead of a fresh one.  `segs`: [(n0, n1, tensor_ptr, batch_stride, pitch,
+    act)] routes output-channel ranges to separate tensors (the fused prediction head); then nothing is returned.  With `bn_stats`
+    (zeroed [2][cout_pad] fp64): (y, whether the epilogue summed the statistics into it)."""
+    b, h, w, cin = x.shape
+    ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    key = ConvKey('f', x.device.index, b, h, w, cin, cout_pad, kh, kw, stride, pad, None, None, act, residual is not None,
+                  bn_stats is not None, None if segs is None else tuple((n0, n1, bs, pt, a) for n0, n1, _, bs, pt, a in segs), train_mma(),
+                  bool(_DETERMINISTIC) and bn_stats is not None)
+    y = None
+    if segs is None:
+        y = out if out is not None else torch.empty(b, ho, wo, cout_pad, device=x.device, dtype=torch.float32)
+
+    def first():
+        return conv_launch.conv_desc(b, h, w, cin, cout_pad, kh, kw, stride, pad, ho, wo, k_pad,
+                                     [(0, cout_pad, None, ho * wo * cout_pad, cout_pad, act)] if segs is None else segs)
+    sums = _launch_conv(key, first, x.device, x, wp, [y.data_ptr()] if segs is None else [sg[2] for sg in segs], shift, residual,
+                        None if bn_stats is None else lambda: bn_stats)
+    return (y, sums is not None) if bn_stats is not None else y
 
 
 def _conv_dgrad(dz, weight, cout_pad, x_shape, stride, pad, add=None, out=None, bn_bwd=None):
@@ -354,46 +384,21 @@ def _conv_dgrad(dz, weight, cout_pad, x_shape, stride, pad, add=None, out=None, 
     cout, cin, kh, kw = weight.shape
     b, h, w, cin_x = x_shape
     assert cin_x == cin and cout_pad % 32 == 0
+    assert add is None or (tuple(add.shape) == (b, h, w, cin) and add.is_contiguous())
+    assert bn_bwd is None or (bn_bwd.c == cin and bn_bwd.m == b * h * w)
     wd = _pack_dgrad(weight, cout_pad)
     dx = out if out is not None else torch.empty(b, h, w, cin, device=dz.device, dtype=torch.float32)
-    key = ('d', dz.device.index, b, dz.shape[1], dz.shape[2], cout_pad, cin, kh, kw, stride, pad, h, w, add is not None, train_mma(),
-           bn_bwd is not None, bool(_DETERMINISTIC) and bn_bwd is not None)
-    ent = _desc_cache.get(key)
-    if ent is None:
-        d = conv_launch.conv_desc(b, dz.shape[1], dz.shape[2], cout_pad, cin, kh, kw, stride, pad, h, w, kh * kw * cout_pad,
-                                  [(0, cin, dx.data_ptr(), h * w * cin, cin, ACT_NONE)], transposed=True)
-        d.inp, d.weight = dz.data_ptr(), wd.data_ptr()
-        d.residual = add.data_ptr() if add is not None else None
-        _configure_conv(d, plan_transfer.dgrad_key(b * h * w, cin, cout_pad, kh, stride))
-        d.tile_counters = _tile_counters(dz.device)
-        fuses = bn_bwd is not None and hip.lib().ym_conv2d_fuses_bn_stats(ctypes.byref(d)) == 1
-        d.bn_ordered = int(fuses and key[-1])
-        if d.bn_ordered:                 # (the row query looks at the descriptor as it will be launched: with its bnb_* sums)
-            d.bnb_y = bn_bwd.y
-        part_rows = hip.lib().ym_conv2d_bn_partial_rows(ctypes.byref(d)) if d.bn_ordered else 0
-        ent = _desc_cache[key] = (d, hip.conv_workspace_bytes(d), fuses, part_rows)
-    d, ws_bytes, fuses, part_rows = ent
-    d.inp, d.weight, d.seg[0].out = dz.data_ptr(), wd.data_ptr(), dx.data_ptr()
-    if add is not None:
-        assert tuple(add.shape) == (b, h, w, cin) and add.is_contiguous()
-        d.residual = add.data_ptr()
-    if fuses:
-        assert bn_bwd.c == cin and bn_bwd.m == b * h * w
-        stats = _stats_pool.take(2 * cin, dz.device)                 # zeroed
-        d.bn_sum, d.bn_sumsq = stats.data_ptr(), stats.data_ptr() + cin * 8
-        part = None
-        if part_rows:
-            part = _partials(dz.device, part_rows, cin)
-            d.bn_sum, d.bn_sumsq = part.data_ptr(), None
-        d.bnb_y, d.bnb_out, d.bnb_mean, d.bnb_invstd = bn_bwd.y, bn_bwd.out, bn_bwd.mean, bn_bwd.invstd
-        d.bnb_gamma, d.bnb_beta, d.bnb_relu = bn_bwd.gamma, bn_bwd.beta, bn_bwd.relu
-    ws = scratch(dz.device, ws_bytes)
-    _count(key)
-    hip.conv2d_fwd(d, ws)
-    if fuses:
-        if part is not None:
-            _finish_partials(part, part_rows, cin, stats)
-        bn_bwd.stats, bn_bwd.dout_ptr = stats, dx.data_ptr()
+    hz, wz = dz.shape[1], dz.shape[2]
+    key = ConvKey('d', dz.device.index, b, hz, wz, cout_pad, cin, kh, kw, stride, pad, h, w, None, add is not None, bn_bwd is not None,
+                  None, train_mma(), bool(_DETERMINISTIC) and bn_bwd is not None)
+
+    def first():
+        return conv_launch.conv_desc(b, hz, wz, cout_pad, cin, kh, kw, stride, pad, h, w, kh * kw * cout_pad,
+                                     [(0, cin, None, h * w * cin, cin, ACT_NONE)], transposed=True)
+    sums = _launch_conv(key, first, dz.device, dz, wd, [dx.data_ptr()], residual=add,
+                        stats=None if bn_bwd is None else lambda: _stats_pool.take(2 * cin, dz.device), bnb=bn_bwd)      # (take: zeroed)
+    if sums is not None:
+        bn_bwd.stats, bn_bwd.dout_ptr = sums, dx.data_ptr()
     return dx
 
 
@@ -507,38 +512,22 @@ def _dev_key(device):
 
 
 def wgrad_stream_if_used(device):
-    """The (first) side stream if a weight gradient was ever enqueued, after making it wait for the other side streams — None
-    otherwise.  Collectives over gradients are issued from it (trainer.FlatGradReducer)."""
+    """The side stream if a weight gradient was ever enqueued — None otherwise.  Collectives over gradients are issued from it
+    (trainer.FlatGradReducer)."""
     s = _side_streams.get(_dev_key(device))
     if s is not None:
         flush_wgrad_reduces(device)                  # the bucket about to be all-reduced must hold finished gradients
-        for e in _extra_streams.get(_dev_key(device), ()):
-            s.wait_stream(e)
     return s
 
 
-# YM_WGRAD_STREAMS=n takes n side streams in turn (consecutive layers' weight gradients are independent of each other as well).
-# Measured with 2, same box: res101 bs=8 45.4 -> 44.6 ms/step, but bs=16 83.3 -> 84.4 and Swin-T 35.6 -> 35.8; a third brings
-# nothing -> the default stays one.  Launches into a caller-owned destination (the shared head's accumulating gradients) always use
-# the first stream, which keeps them ordered.
-_N_SIDE = int(os.environ.get('YM_WGRAD_STREAMS', '1'))
-# YM_WGRAD_STREAM_PRIORITY=-1 creates the side stream(s) on a high-priority hardware queue (0 = like any other stream):
-# both orders were measured in round 4 (the data-gradient chain ahead of the weight gradients and the reverse): no change.
-_SIDE_PRIO = int(os.environ.get('YM_WGRAD_STREAM_PRIORITY', '0'))
-_extra_streams = {}
-_rr = [0]
-
-
-def wgrad_stream(device, ordered=True):
+def wgrad_stream(device):
+    """The one side stream of the device, of default priority (several streams in turn and a high-priority queue were measured and
+    dropped: docs/experiments.md, "Side-stream options that were removed")."""
     device = _dev_key(device)
     s = _side_streams.get(device)
     if s is None:
-        s = _side_streams[device] = torch.cuda.Stream(device=device, priority=_SIDE_PRIO)
-    if ordered or _N_SIDE <= 1:
-        return s
-    ex = _extra_streams.setdefault(device, [torch.cuda.Stream(device=device, priority=_SIDE_PRIO) for _ in range(_N_SIDE - 1)])
-    _rr[0] = (_rr[0] + 1) % _N_SIDE
-    return s if _rr[0] == 0 else ex[_rr[0] - 1]
+        s = _side_streams[device] = torch.cuda.Stream(device=device)
+    return s
 
 
 def join_wgrad_stream(device):
@@ -547,9 +536,7 @@ def join_wgrad_stream(device):
     s = _side_streams.get(_dev_key(device))
     if s is not None:
         torch.cuda.current_stream(_dev_key(device)).wait_stream(s)
-    for e in _extra_streams.get(_dev_key(device), ()):
-        torch.cuda.current_stream(_dev_key(device)).wait_stream(e)
-    _side_keep.pop(_dev_key(device), None)         # everything the side streams read is ordered before the main stream from here on
+    _side_keep.pop(_dev_key(device), None)         # everything the side stream read is ordered before the main stream from here on
 
 
 # Operands of a side-stream launch (x, dz, y) are OWNED by the main stream's autograd pass, which may
@@ -563,13 +550,24 @@ _side_keep = {}
 
 
 def _keep_for_side(device, side, *tensors):
-    import collections
     q = _side_keep.setdefault(_dev_key(device), collections.deque())
     ev = torch.cuda.Event()
     ev.record(side)
     q.append((ev, tensors))
     while len(q) > 1 and q[0][0].query():
         q.popleft()
+
+
+def _on_side_stream(device, fn, keep, owners):
+    """Enqueue `fn()` on the side stream, behind everything the current stream has enqueued (its operands are ready); `keep`: the
+    tensors it reads (`_keep_for_side`); `owners`: the parameters whose gradient slots it writes (`_grad_slot` joins for them)."""
+    side = wgrad_stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        fn()
+    _keep_for_side(device, side, *keep)                # neither recycled nor summed into in place until the side stream is past
+    for o in owners:
+        getattr(o, '_ym_owner', o)._ym_side_written = True
 
 
 # ---- batched slab reductions ----------------------------------------------------------------------------------------------------
@@ -630,29 +628,29 @@ def _conv_wgrad(x, dz, weight_shape, stride, pad, weight_param=None, dw=None, ac
     _auto_backward_begin(weight_param if weight_param is not None else (owners[0] if owners else None))
     if not _side_active[0] or not x.is_cuda:
         return _conv_wgrad_now(x, dz, weight_shape, stride, pad, weight_param, dw, accumulate, segments)
-    cout, cin, kh, kw = weight_shape
-    shared_dst = dw is not None                      # a caller-owned destination may be written by several launches: keep them ordered
+    shared_dst = dw is not None                      # a caller-owned destination is accumulated into by several launches of one step
     if dw is None:                                   # (allocated / adopted on the main stream, written on the side stream)
-        dw = _grad_slot(weight_param, (cout, cin, kh, kw)) if weight_param is not None else \
-            torch.empty(cout, cin, kh, kw, device=x.device, dtype=torch.float32)
+        dw = _default_dw(weight_param, weight_shape, x.device)
     owners = owners if owners is not None else (weight_param,)
     dsts = (dw,) if segments is None else (dw, segments[2], segments[3])
     if len(owners) != len(dsts) or not all(_side_ok(o, d) for o, d in zip(owners, dsts)):
         # a fresh tensor (second use of a parameter in this step, a non-leaf weight, no flat optimizer): autograd reads it on the
         # main stream right after this node returns -> produce it there
         return _conv_wgrad_now(x, dz, weight_shape, stride, pad, weight_param, dw, accumulate, segments)
-    side = wgrad_stream(x.device, ordered=shared_dst)
-    side.wait_stream(torch.cuda.current_stream(x.device))          # x, dz (and earlier accumulations into dw) are ready
-    # (a caller-owned destination is accumulated into by several launches of one step: those reduce at once, in order)
-    defer = _REDUCE_BATCH > 0 and _N_SIDE <= 1 and not shared_dst and segments is None and not accumulate
-    with torch.cuda.stream(side):
+    defer = _REDUCE_BATCH > 0 and not shared_dst and segments is None and not accumulate      # (those reduce at once, in order)
+
+    def enqueue():                                   # x, dz (and earlier accumulations into dw) are ready
         _conv_wgrad_now(x, dz, weight_shape, stride, pad, weight_param, dw, accumulate, segments, defer=defer)
-    if defer and len(_pending_reduce.get(_dev_key(x.device), ())) >= _REDUCE_BATCH:
-        flush_wgrad_reduces(x.device)
-    _keep_for_side(x.device, side, x, dz)                          # neither recycled nor summed into in place until the side stream is past
-    for o in owners:
-        getattr(o, '_ym_owner', o)._ym_side_written = True
+        if defer and len(_pending_reduce.get(_dev_key(x.device), ())) >= _REDUCE_BATCH:
+            flush_wgrad_reduces(x.device)
+    _on_side_stream(x.device, enqueue, (x, dz), owners)
     return dw
+
+
+def _default_dw(weight_param, weight_shape, device):
+    if weight_param is not None:
+        return _grad_slot(weight_param, tuple(weight_shape))
+    return torch.empty(*weight_shape, device=device, dtype=torch.float32)
 
 
 def _conv_wgrad_now(x, dz, weight_shape, stride, pad, weight_param=None, dw=None, accumulate=False, segments=None, defer=False):
@@ -662,30 +660,27 @@ def _conv_wgrad_now(x, dz, weight_shape, stride, pad, weight_param=None, dw=None
     cout, cin, kh, kw = weight_shape
     b, h, w, cin_p = x.shape
     if dw is None:
-        dw = _grad_slot(weight_param, (cout, cin, kh, kw)) if weight_param is not None else \
-            torch.empty(cout, cin, kh, kw, device=x.device, dtype=torch.float32)
-    key = ('w', x.device.index, b, h, w, cin_p, cin, dz.shape[1], dz.shape[2], dz.shape[3], cout, kh, kw, stride, pad,
-           None if segments is None else (segments[0], segments[1]))
+        dw = _default_dw(weight_param, weight_shape, x.device)
+    key = WgradKey('w', x.device.index, b, h, w, cin_p, cin, dz.shape[1], dz.shape[2], dz.shape[3], cout, kh, kw, stride, pad,
+                   None if segments is None else (segments[0], segments[1]))
     ent = _desc_cache.get(key)
-    if ent is None:
-        d = WgradDesc()
-        d.x, d.dy, d.dw = x.data_ptr(), dz.data_ptr(), dw.data_ptr()
+    d = WgradDesc() if ent is None else ent.desc
+    d.x, d.dy, d.dw = x.data_ptr(), dz.data_ptr(), dw.data_ptr()
+    if segments is not None:
+        d.dw_seg[0], d.dw_seg[1] = segments[2].data_ptr(), segments[3].data_ptr()
+    if ent is None:                                      # (the inline sweep launches with this call's pointers)
         d.B, d.H, d.W, d.Cin, d.Cin_real, d.Cout, d.Cout_real = b, h, w, cin_p, cin, dz.shape[3], cout
         d.KH, d.KW, d.stride, d.pad, d.Ho, d.Wo, d.msplit = kh, kw, stride, pad, dz.shape[1], dz.shape[2], 0
         if segments is not None:
             d.row_end[0], d.row_end[1] = segments[0], segments[1]
-            d.dw_seg[0], d.dw_seg[1] = segments[2].data_ptr(), segments[3].data_ptr()
         _configure_wgrad(d, plan_transfer.wgrad_key(b * dz.shape[1] * dz.shape[2], dz.shape[3], cin_p, kh, stride))
         nbytes = hip.lib().ym_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
         if nbytes == 0:
             raise RuntimeError('ym_conv2d_wgrad_workspace_bytes: ' + hip.lib().ym_last_error().decode())
-        ent = _desc_cache[key] = (d, nbytes)
-    d, nbytes = ent
-    d.x, d.dy, d.dw = x.data_ptr(), dz.data_ptr(), dw.data_ptr()
+        ent = _desc_cache[key] = CacheEntry(d, False, nbytes, 0)
+    nbytes = ent.ws_bytes
     d.accumulate = int(accumulate)
     _count(key)
-    if segments is not None:
-        d.dw_seg[0], d.dw_seg[1] = segments[2].data_ptr(), segments[3].data_ptr()
     if defer:
         dev = _dev_key(x.device)
         akey = (dev, dw.data_ptr())                      # per DESTINATION (= per layer: layers of one shape share `key`)
@@ -744,12 +739,7 @@ class ConvBias(torch.autograd.Function):
                                                 ws.numel(), hip.stream_ptr()), 'ym_act_bias_bwd')
         if has_bias and cout_pad == weight.shape[0] and _side_ok(bias_param, dbias):
             # like the weight gradient, the bias gradient is off the critical path: side stream (it lands in the optimizer's slot)
-            side = wgrad_stream(dy.device)
-            side.wait_stream(torch.cuda.current_stream(dy.device))
-            with torch.cuda.stream(side):
-                bias_grad()
-            _keep_for_side(dy.device, side, dy, y)
-            bias_param._ym_side_written = True
+            _on_side_stream(dy.device, bias_grad, (dy, y), (bias_param,))
         elif has_bias:
             bias_grad()
         if act != ACT_NONE:
