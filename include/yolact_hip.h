@@ -972,6 +972,45 @@ int ym_coco_accumulate(const uint32_t* log_flags, const int32_t* log_rank, const
                        const int64_t* npig, const double* rec_thrs, int R, const int32_t* max_dets, int M, int T,
                        int num_classes, double eps, int kinds, double* precision, double* recall, void* workspace,
                        size_t workspace_bytes, ym_stream_t s);
+/* ym_eval_coco_add_ragged_packed: evaluateImg for a whole request -- ym_coco_iou_box + ym_coco_iou_mask_packed + ym_coco_match_log
+ * for B <= YM_RAGGED_MAX_IMAGES images of different sizes in at most THREE launches; log_score, log_class, log_rank, log_flags, npig
+ * and class_rows end up exactly as after B single-image calls.
+ *   ids int64 / scores fp32 [B][max_det], boxes_px int32 [B][max_det][4], counts int32 [B] on the device (clamped to 0..max_det);
+ *   det_bits + det_blocks: the packed masks and the table that ym_after_nms_ragged_packed was given;
+ *   gt_class int32 [G], gt_iscrowd uint8 [G], gt_area fp64 [G], gt_xywh fp64 [G][4] on the device, G = gt_first[B];
+ *   gt_first: HOST int32 [B + 1], ascending: image b owns the gts gt_first[b] .. gt_first[b + 1], g_b of them, 0 <= g_b <= YM_COCO_MAX_GT;
+ *   gt_bits + gt_blocks: block b = [g_b][img_h_b][ceil(img_w_b / 64)] words, sizes equal to det_blocks';
+ *   image_index: HOST int64 [B], image b's rows are log_*[image_index[b] * max_det ..); < 0 = the entry is padding: nothing of it is
+ *   read, written or counted; log_rows = rows of the log arrays (log_flags has YM_COCO_WORDS_PER_ROW words per row);
+ *   thresholds, T, area_rng, num_classes, max_rank: as for ym_coco_match_log;
+ *   kinds: bit 0 = bbox, bit 1 = segm.  An IoU type that is off is not evaluated and needs none of its inputs: without bbox gt_xywh
+ *   may be NULL (and boxes_px, then every row below its count is a detection); without segm det_bits, det_blocks, gt_bits and
+ *   gt_blocks may be NULL.
+ * The tables are read during the call and travel to the kernels by value: no device copy, no synchronisation, no host read.
+ *   launch 1 (segm only): one workgroup per (20-word chunk of an image's mask rows, group of 128 gt rows), grid.x = sum of
+ *     ceil(words_b / 20) over the images that are not padding -- ALSO those with g_b = 0: an unmatched detection whose own area is
+ *     outside the range is ignored, so its popcount is needed without any gt; a workgroup finds its image from the prefix of that
+ *     sum, loads only the detection rows below counts[b], in passes of 128, and writes its own exact integer partials (the pair
+ *     loop of ym_mask_iou_packed);
+ *   launch 2, fp64 without contraction: per row below the count area_mask = the sum of its partials and area_box = w * h; per pair
+ *     (row below the count, gt) the mask IoU of ym_coco_iou_mask_packed from the summed partials and the box IoU by
+ *     ym_coco_iou_box's formula on (x1, y1, x2 - x1, y2 - y1) of boxes_px (exact in fp64);
+ *   launch 3: workgroup b is ym_coco_match_log's workgroup for image b (one device function: same ordering, same matching, same log
+ *     writes, same integer atomics; an image whose count is 0 only counts its gts).
+ * Integer atomics only.  YM_EINVAL, before any launch, for B outside 1..YM_RAGGED_MAX_IMAGES, max_det outside 1..YM_EVAL_MAX_DET, T
+ * outside 1..YM_EVAL_MAX_THRESHOLDS, kinds outside 1..3, g_b > YM_COCO_MAX_GT or a descending gt_first, table entries that differ in
+ * size, lie at no multiple of YM_RAGGED_ALIGN_BYTES or overlap, img_h_b * ceil(img_w_b / 64) >= 2^24, (image_index[b] + 1) * max_det >
+ * log_rows, two equal indices >= 0, null pointers of an enabled kind; YM_ENOSPC for workspace_bytes <
+ * ym_eval_coco_add_ragged_workspace_bytes(...) (the IoUs, areas and partials of every image; a host function of the sizes; det_blocks
+ * may be NULL without segm; 0 for arguments the entry refuses). */
+size_t ym_eval_coco_add_ragged_workspace_bytes(const ym_ragged_image* det_blocks, const int32_t* gt_first, int B, int max_det, int kinds);
+int ym_eval_coco_add_ragged_packed(const int64_t* ids, const float* scores, const int32_t* boxes_px, const int32_t* counts, int B,
+                                   int max_det, const uint64_t* det_bits, const ym_ragged_image* det_blocks, const int32_t* gt_class,
+                                   const uint8_t* gt_iscrowd, const double* gt_area, const double* gt_xywh, const int32_t* gt_first,
+                                   const uint64_t* gt_bits, const ym_ragged_image* gt_blocks, const int64_t* image_index,
+                                   const double* thresholds, int T, const double* area_rng, int num_classes, int max_rank, int kinds,
+                                   float* log_score, int32_t* log_class, int32_t* log_rank, uint32_t* log_flags, int64_t log_rows,
+                                   int64_t* npig, int32_t* class_rows, void* workspace, size_t workspace_bytes, ym_stream_t s);
 
 #ifdef __cplusplus
 }

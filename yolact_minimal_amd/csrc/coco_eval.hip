@@ -2,6 +2,7 @@
 // from pycocotools.cocoeval.COCOeval after the dump (eval.py:90-104), restated from the published cocoapi algorithm:
 //   maskApi.c  bbIou / rleIou                     -> k_coco_iou_box, k_coco_iou_mask
 //   cocoeval.py computeIoU / evaluateImg          -> k_coco_match_log (one image, every category, area range, threshold, IoU type)
+//   the three of them for a whole request       -> k_coco_inter_ragged, k_coco_iou_ragged, k_coco_match_log_ragged
 //   cocoeval.py accumulate                        -> k_coco_gather + k_coco_accumulate (precision / recall grids)
 // `summarize` is host numpy on the one downloaded grid (utils/coco_eval.py).  Everything floating-point is fp64 without contraction,
 // sums are integer counts, the only atomics are integer ones: the grids repeat bit for bit.
@@ -13,15 +14,11 @@ namespace {
 constexpr int MAXG = YM_COCO_MAX_GT;
 constexpr int AREAS = YM_COCO_AREAS;
 constexpr int WORDS_PER_ROW = 2 * AREAS;          // flag words of a log row: [IoU type][area range]
+#include "packed_inter.h"                         // MAXR, PWORDS and inter_packed_chunk: the pair loop on bit rows, shared with metrics.hip
 
 // ---- maskApi.c bbIou: boxes are [x, y, w, h] doubles -------------------------------------------------------------------------
-__global__ void k_coco_iou_box(const double* __restrict__ dt, int n, const double* __restrict__ gt, int g,
-                               const uint8_t* __restrict__ crowd, double* __restrict__ iou) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * g) return;
-    const int i = e / g, j = e - i * g;
-    const double* D = dt + (size_t)i * 4;
-    const double* G = gt + (size_t)j * 4;
+// (the ONE statement of bbIou's formula: k_coco_iou_box and k_coco_iou_ragged both call it)
+__device__ __forceinline__ double coco_bb_iou(const double* D, const double* G, bool crowd) {
     const double da = D[2] * D[3], ga = G[2] * G[3];
     double o = 0.0;
     const double w = fmin(D[2] + D[0], G[2] + G[0]) - fmax(D[0], G[0]);
@@ -29,11 +26,19 @@ __global__ void k_coco_iou_box(const double* __restrict__ dt, int n, const doubl
         const double h = fmin(D[3] + D[1], G[3] + G[1]) - fmax(D[1], G[1]);
         if (h > 0.0) {
             const double in = w * h;
-            const double u = crowd[j] ? da : da + ga - in;
+            const double u = crowd ? da : da + ga - in;
             o = in / u;
         }
     }
-    iou[e] = o;
+    return o;
+}
+
+__global__ void k_coco_iou_box(const double* __restrict__ dt, int n, const double* __restrict__ gt, int g,
+                               const uint8_t* __restrict__ crowd, double* __restrict__ iou) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * g) return;
+    const int i = e / g, j = e - i * g;
+    iou[e] = coco_bb_iou(dt + (size_t)i * 4, gt + (size_t)j * 4, crowd[j] != 0);
 }
 
 // ---- maskApi.c rleIou on bit rows: i = |d & g|, 0 when i == 0, else i / (crowd ? |d| : |d| + |g| - i) --------------------------
@@ -102,7 +107,8 @@ __global__ __launch_bounds__(IM_THREADS) void k_coco_iou_mask(const unsigned lon
 // (head, IoU type, area range, threshold) is one greedy chain of evaluateImg, one lane each, neighbouring lanes in one category; its
 // matched-gt bitmap lives in LDS ([word][lane]: no bank conflicts); the result is OR-ed into the row's flag word.
 constexpr int MATCH_THREADS = 512, USED_WORDS = MAXG / 32;
-__global__ __launch_bounds__(MATCH_THREADS) void k_coco_match_log(
+// (the body of one image's workgroup: k_coco_match_log runs it for its one image, k_coco_match_log_ragged for image blockIdx.x)
+__device__ __forceinline__ void coco_match_log_image(
         const long long* __restrict__ ids, const float* __restrict__ scores, const int* __restrict__ count, int n,
         const int* __restrict__ boxes_px, const double* __restrict__ iou_box, const double* __restrict__ iou_mask,
         const double* __restrict__ area_box, const int* __restrict__ area_mask, const int* __restrict__ gt_cls,
@@ -241,6 +247,150 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_coco_match_log(
         log_score[i] = c >= 0 ? scores[i] : 0.f;
         if (c >= 0) atomicAdd(&class_rows[c], 1);
     }
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_coco_match_log(
+        const long long* __restrict__ ids, const float* __restrict__ scores, const int* __restrict__ count, int n,
+        const int* __restrict__ boxes_px, const double* __restrict__ iou_box, const double* __restrict__ iou_mask,
+        const double* __restrict__ area_box, const int* __restrict__ area_mask, const int* __restrict__ gt_cls,
+        const uint8_t* __restrict__ gt_crowd, const double* __restrict__ gt_area, int g, const double* __restrict__ thr, int T,
+        const double* __restrict__ area_rng, int num_classes, int max_rank, float* __restrict__ log_score, int* __restrict__ log_class,
+        int* __restrict__ log_rank, unsigned* __restrict__ log_flags, unsigned long long* __restrict__ npig, int* __restrict__ class_rows) {
+    coco_match_log_image(ids, scores, count, n, boxes_px, iou_box, iou_mask, area_box, area_mask, gt_cls, gt_crowd, gt_area, g, thr, T,
+                         area_rng, num_classes, max_rank, log_score, log_class, log_rank, log_flags, npig, class_rows);
+}
+
+// ---- evaluateImg for a whole request (include/yolact_hip.h "ym_eval_coco_add_ragged_packed") -----------------------------------
+// What the three launches know about their images, BY VALUE in the kernel arguments (like EvalRaggedTable of metrics.hip).  The
+// workspace is a region of doubles and, behind it, a region of ints.  Image b's doubles at dbl_off[b]: iou_box [max_det][g_b] and
+// area_box [max_det] (bbox), then iou_mask [max_det][g_b] (segm).  Its ints at int_off[b] (segm only): the partial counts inter
+// [chunks_b][max_det][g_b], area_a [chunks_b][max_det], area_b [chunks_b][g_b] (chunks_b = ceil(words_b / PWORDS), also for g_b = 0),
+// then area_mask [max_det].  An image that is padding owns no chunk of the first launch.
+struct CocoRaggedTable {
+    int chunk_first[YM_RAGGED_MAX_IMAGES + 1];   // prefix sum of the chunks: which image a workgroup of the first launch serves
+    int gt_first[YM_RAGGED_MAX_IMAGES + 1];      // first gt of image b in the gt arrays (and g_b as the difference)
+    int words[YM_RAGGED_MAX_IMAGES];             // img_h_b * ceil(img_w_b / 64)
+    long long det_off[YM_RAGGED_MAX_IMAGES], gt_off[YM_RAGGED_MAX_IMAGES];   // words from det_bits / gt_bits to the image's block
+    long long dbl_off[YM_RAGGED_MAX_IMAGES], int_off[YM_RAGGED_MAX_IMAGES];
+    long long log_row[YM_RAGGED_MAX_IMAGES];     // image_index * max_det; < 0 = padding
+};
+
+__device__ __forceinline__ int coco_ragged_count(const int* __restrict__ counts, int b, int max_det) { return min(max(counts[b], 0), max_det); }
+
+// The chunks of image b's masks: what the table's prefix says for an image of the first launch, the same number recomputed for the
+// finalize step (0 when segm is off: `words` stays 0).
+__device__ __forceinline__ int coco_ragged_chunks(const CocoRaggedTable& t, int b) { return (t.words[b] + PWORDS - 1) / PWORDS; }
+
+// grid: (all chunks of all live images, the largest number of gt groups of an image).  Rows at or past the image's count are not
+// loaded.  An image without ground truth keeps its chunks: its detections' popcounts (area_a) decide their ignore bits.
+__global__ __launch_bounds__(512) void k_coco_inter_ragged(const unsigned long long* __restrict__ det_bits,
+                                                           const unsigned long long* __restrict__ gt_bits, const int* __restrict__ counts,
+                                                           int B, int max_det, const CocoRaggedTable t, int* __restrict__ part) {
+    int b = 0;
+    while (b + 1 < B && (int)blockIdx.x >= t.chunk_first[b + 1]) ++b;
+    const int g = t.gt_first[b + 1] - t.gt_first[b];
+    if (blockIdx.y > 0 && (int)blockIdx.y * MAXR >= g) return;
+    const int n = coco_ragged_count(counts, b, max_det);
+    if (n == 0) return;
+    const int chunks = t.chunk_first[b + 1] - t.chunk_first[b];
+    int* inter = part + t.int_off[b];
+    int* area_a = inter + (size_t)chunks * max_det * g;
+    int* area_b = area_a + (size_t)chunks * max_det;
+    inter_packed_chunk(det_bits + t.det_off[b], n, max_det, gt_bits + t.gt_off[b], g, (long long)t.words[b], (int)blockIdx.x - t.chunk_first[b],
+                       (int)blockIdx.y, inter, area_a, area_b);
+}
+
+// grid: (groups of 64 items of the largest image, B).  The items of an image with n rows below its count: the n * g_b pairs
+// e = i * g_b + j, then the n rows.  The chunk sums of an item are split over FSL slices and joined in LDS (exact integers).  Slice 0
+// writes the mask side: a pair's rleIou quotient (k_coco_iou_mask's), a row's area_mask.  Slice 1 writes the box side: bbIou on
+// (x1, y1, x2 - x1, y2 - y1) of the int32 pixel box in fp64 (exact), a row's area_box = w * h.
+constexpr int FSL = 16;
+__global__ __launch_bounds__(64 * FSL) void k_coco_iou_ragged(const int* __restrict__ boxes_px, const double* __restrict__ gt_xywh,
+                                                              const uint8_t* __restrict__ gt_crowd, const int* __restrict__ counts,
+                                                              int max_det, int kinds, const CocoRaggedTable t, int* __restrict__ part,
+                                                              double* __restrict__ dbl) {
+    __shared__ int s_i[FSL][64], s_a[FSL][64], s_b[FSL][64];
+    const int b = blockIdx.y;
+    if (t.log_row[b] < 0) return;
+    const int g = t.gt_first[b + 1] - t.gt_first[b];
+    const int n = coco_ragged_count(counts, b, max_det);
+    const int pairs = n * g, items = pairs + n;
+    if ((int)blockIdx.x * 64 >= items) return;              // (uniform; n == 0 as well)
+    const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane;
+    const bool live = e < items, pair = e < pairs;
+    const int i = pair ? e / g : (live ? e - pairs : 0), j = pair ? e - i * g : 0;
+    const bool bbox = (kinds & 1) != 0, segm = (kinds & 2) != 0;
+    const int chunks = segm ? coco_ragged_chunks(t, b) : 0;
+    int* inter = part + t.int_off[b];
+    int* area_a = inter + (size_t)chunks * max_det * g;
+    int* area_b = area_a + (size_t)chunks * max_det;
+    int* area_mask = area_b + (size_t)chunks * g;
+    double* iou_box = dbl + t.dbl_off[b];
+    double* area_box = iou_box + (size_t)max_det * g;
+    double* iou_mask = bbox ? area_box + max_det : iou_box;
+    int it = 0, aa = 0, ab = 0;
+    if (live) {
+#pragma unroll 4
+        for (int c = sl; c < chunks; c += FSL) {
+            aa += area_a[(size_t)c * max_det + i];
+            if (pair) {
+                it += inter[((size_t)c * max_det + i) * g + j];
+                ab += area_b[(size_t)c * g + j];
+            }
+        }
+    }
+    s_i[sl][lane] = it; s_a[sl][lane] = aa; s_b[sl][lane] = ab;
+    __syncthreads();
+    if (!live) return;
+    if (sl == 0 && segm) {
+        int in = 0, da = 0, ga = 0;
+#pragma unroll
+        for (int q = 0; q < FSL; ++q) { in += s_i[q][lane]; da += s_a[q][lane]; ga += s_b[q][lane]; }
+        if (pair) {
+            double o = 0.0;
+            if (in != 0) {
+                const long long u = gt_crowd[t.gt_first[b] + j] ? (long long)da : (long long)da + ga - in;
+                o = (double)in / (double)u;
+            }
+            iou_mask[e] = o;
+        } else {
+            area_mask[i] = da;
+        }
+    }
+    if (sl == 1 && bbox) {
+        const int* pb = boxes_px + ((size_t)b * max_det + i) * 4;
+        const double x1 = (double)pb[0], y1 = (double)pb[1];
+        const double D[4] = {x1, y1, (double)pb[2] - x1, (double)pb[3] - y1};
+        if (pair) iou_box[e] = coco_bb_iou(D, gt_xywh + (size_t)(t.gt_first[b] + j) * 4, gt_crowd[t.gt_first[b] + j] != 0);
+        else area_box[i] = D[2] * D[3];
+    }
+}
+
+// grid: B.  Workgroup b is k_coco_match_log's workgroup for image b: its max_det padded rows, its count, its gts, its IoUs and
+// areas from the launch before, its log rows.  A padding entry exits at once.
+__global__ __launch_bounds__(MATCH_THREADS) void k_coco_match_log_ragged(
+        const long long* __restrict__ ids, const float* __restrict__ scores, const int* __restrict__ counts, int max_det,
+        const int* __restrict__ boxes_px, int kinds, const CocoRaggedTable t, const int* __restrict__ part, const double* __restrict__ dbl,
+        const int* __restrict__ gt_cls, const uint8_t* __restrict__ gt_crowd, const double* __restrict__ gt_area,
+        const double* __restrict__ thr, int T, const double* __restrict__ area_rng, int num_classes, int max_rank,
+        float* __restrict__ log_score, int* __restrict__ log_class, int* __restrict__ log_rank, unsigned* __restrict__ log_flags,
+        unsigned long long* __restrict__ npig, int* __restrict__ class_rows) {
+    const int b = blockIdx.x;
+    const long long row = t.log_row[b];
+    if (row < 0) return;
+    const int g = t.gt_first[b + 1] - t.gt_first[b], g0 = t.gt_first[b];
+    const bool bbox = (kinds & 1) != 0, segm = (kinds & 2) != 0;
+    const int chunks = segm ? coco_ragged_chunks(t, b) : 0;
+    const double* iou_box = dbl + t.dbl_off[b];
+    const double* area_box = iou_box + (size_t)max_det * g;
+    const double* iou_mask = bbox ? area_box + max_det : iou_box;
+    const int* area_mask = part + t.int_off[b] + (size_t)chunks * ((size_t)max_det * g + max_det + g);
+    coco_match_log_image(ids + (size_t)b * max_det, scores + (size_t)b * max_det, counts + b, max_det,
+                         boxes_px ? boxes_px + (size_t)b * max_det * 4 : nullptr, bbox ? iou_box : nullptr, segm ? iou_mask : nullptr,
+                         bbox ? area_box : nullptr, segm ? area_mask : nullptr, gt_cls + g0, gt_crowd + g0, gt_area + g0, g, thr, T,
+                         area_rng, num_classes, max_rank, log_score + row, log_class + row, log_rank + row,
+                         log_flags + row * WORDS_PER_ROW, npig, class_rows);
 }
 
 // ---- cocoeval.py accumulate ---------------------------------------------------------------------------------------------------
@@ -471,4 +621,136 @@ extern "C" int ym_coco_accumulate(const uint32_t* log_flags, const int32_t* log_
                        sorted_rank, (long long)rows, reinterpret_cast<const long long*>(seg), reinterpret_cast<const long long*>(npig), rec_thrs,
                        R, max_dets, M, T, num_classes, eps, kinds, precision, recall);
     return ym_check_launch("coco_accumulate");
+}
+
+// Where image b's doubles and ints lie in the workspace of ym_eval_coco_add_ragged_packed (CocoRaggedTable): a function of the sizes
+// alone, so a padding entry keeps its (unused) room and the workspace query needs no image_index.  false for arguments the entry refuses.
+static bool coco_ragged_layout(const ym_ragged_image* det_blocks, const int32_t* gt_first, int B, int max_det, int kinds, long long* dbl_off,
+                               long long* int_off, size_t* doubles, size_t* ints) {
+    if (!gt_first || B < 1 || B > YM_RAGGED_MAX_IMAGES || max_det < 1 || max_det > YM_EVAL_MAX_DET || kinds < 1 || kinds > 3) return false;
+    const bool bbox = (kinds & 1) != 0, segm = (kinds & 2) != 0;
+    if (segm && !det_blocks) return false;
+    size_t nd = 0, ni = 0;
+    for (int b = 0; b < B; ++b) {
+        const long long g = (long long)gt_first[b + 1] - gt_first[b];
+        if (g < 0 || g > MAXG) return false;
+        if (dbl_off) dbl_off[b] = (long long)nd;
+        if (int_off) int_off[b] = (long long)ni;
+        if (bbox) nd += (size_t)max_det * g + max_det;
+        if (segm) {
+            if (det_blocks[b].img_h <= 0 || det_blocks[b].img_w <= 0) return false;
+            const long long words = (long long)det_blocks[b].img_h * (long long)ym_mask_row(true, det_blocks[b].img_w);
+            if (words >= (1ll << 24)) return false;
+            const size_t chunks = (size_t)((words + PWORDS - 1) / PWORDS);
+            nd += (size_t)max_det * g;
+            ni += chunks * ((size_t)max_det * g + max_det + g) + max_det;
+        }
+    }
+    *doubles = nd;
+    *ints = ni;
+    return true;
+}
+
+extern "C" size_t ym_eval_coco_add_ragged_workspace_bytes(const ym_ragged_image* det_blocks, const int32_t* gt_first, int B, int max_det,
+                                                          int kinds) {
+    size_t nd = 0, ni = 0;
+    if (!coco_ragged_layout(det_blocks, gt_first, B, max_det, kinds, nullptr, nullptr, &nd, &ni)) return 0;
+    return nd * sizeof(double) + ni * sizeof(int) + 256;
+}
+
+extern "C" int ym_eval_coco_add_ragged_packed(const int64_t* ids, const float* scores, const int32_t* boxes_px, const int32_t* counts, int B,
+                                              int max_det, const uint64_t* det_bits, const ym_ragged_image* det_blocks,
+                                              const int32_t* gt_class, const uint8_t* gt_iscrowd, const double* gt_area,
+                                              const double* gt_xywh, const int32_t* gt_first, const uint64_t* gt_bits,
+                                              const ym_ragged_image* gt_blocks, const int64_t* image_index, const double* thresholds, int T,
+                                              const double* area_rng, int num_classes, int max_rank, int kinds, float* log_score,
+                                              int32_t* log_class, int32_t* log_rank, uint32_t* log_flags, int64_t log_rows, int64_t* npig,
+                                              int32_t* class_rows, void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    const char* what = "eval_coco_add_ragged_packed";
+    YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
+    YM_REQUIRE(max_det >= 1 && max_det <= YM_EVAL_MAX_DET, "%s: need 0 < max_det <= %d, got %d", what, YM_EVAL_MAX_DET, max_det);
+    YM_REQUIRE(T >= 1 && T <= YM_EVAL_MAX_THRESHOLDS, "%s: 1 .. %d thresholds (16 flag bits per word), got %d", what,
+               YM_EVAL_MAX_THRESHOLDS, T);
+    YM_REQUIRE(num_classes > 0 && max_rank > 0, "%s: num_classes = %d, max_rank = %d", what, num_classes, max_rank);
+    YM_REQUIRE(kinds >= 1 && kinds <= 3, "%s: kinds is a mask of bbox (1) and segm (2), got %d", what, kinds);
+    const bool bbox = (kinds & 1) != 0, segm = (kinds & 2) != 0;
+    YM_REQUIRE(ids && scores && counts && gt_first && image_index && thresholds && area_rng && log_score && log_class && log_rank &&
+                   log_flags && npig && class_rows && workspace,
+               "%s: null pointer", what);
+    YM_REQUIRE(!bbox || boxes_px, "%s: null pointer (bbox needs boxes_px)", what);
+    YM_REQUIRE(!segm || (det_bits && det_blocks && gt_blocks), "%s: null pointer (segm needs det_bits and both tables)", what);
+    YM_REQUIRE(gt_first[0] >= 0, "%s: gt_first[0] = %d", what, gt_first[0]);
+    for (int b = 0; b < B; ++b) {
+        const long long g = (long long)gt_first[b + 1] - gt_first[b];
+        YM_REQUIRE(g >= 0, "%s: gt_first is not ascending at image %d", what, b);
+        YM_REQUIRE(g <= MAXG, "%s: image %d has %lld gt annotations, at most %d are matched", what, b, g, MAXG);
+    }
+    YM_REQUIRE(gt_first[B] == 0 || (gt_class && gt_iscrowd && gt_area), "%s: null pointer", what);
+    YM_REQUIRE(gt_first[B] == 0 || !bbox || gt_xywh, "%s: null pointer (bbox needs gt_xywh)", what);
+    YM_REQUIRE(gt_first[B] == 0 || !segm || gt_bits, "%s: null pointer (segm needs gt_bits)", what);
+    if (segm) {
+        const int rc_det = ym_check_ragged_table(what, det_blocks, B, 8, [&](const ym_ragged_image& im) {
+            return (int64_t)max_det * im.img_h * (int64_t)ym_mask_row(true, im.img_w);
+        });
+        if (rc_det != YM_OK) return rc_det;
+        const int rc_gt = ym_check_ragged_table_indexed(what, gt_blocks, B, 8, [&](int b) {
+            return (int64_t)(gt_first[b + 1] - gt_first[b]) * gt_blocks[b].img_h * (int64_t)ym_mask_row(true, gt_blocks[b].img_w);
+        });
+        if (rc_gt != YM_OK) return rc_gt;
+        for (int b = 0; b < B; ++b) {
+            YM_REQUIRE(gt_blocks[b].img_h == det_blocks[b].img_h && gt_blocks[b].img_w == det_blocks[b].img_w,
+                       "%s: image %d: gt masks of %d x %d for detection masks of %d x %d", what, b, gt_blocks[b].img_h, gt_blocks[b].img_w,
+                       det_blocks[b].img_h, det_blocks[b].img_w);
+            YM_REQUIRE((long long)det_blocks[b].img_h * (long long)ym_mask_row(true, det_blocks[b].img_w) < (1ll << 24),
+                       "%s: image %d: need img_h * ceil(img_w / 64) < 2^24 words (exact int32 counts)", what, b);
+        }
+    }
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        if (image_index[b] < 0) continue;
+        YM_REQUIRE(image_index[b] < log_rows && (image_index[b] + 1) * max_det <= log_rows,
+                   "%s: image index %lld: its %d rows end past the %lld rows of the log", what, (long long)image_index[b], max_det,
+                   (long long)log_rows);
+        for (int a = 0; a < b; ++a)
+            YM_REQUIRE(image_index[a] != image_index[b], "%s: image index %lld twice in one call", what, (long long)image_index[b]);
+        any = true;
+    }
+    CocoRaggedTable t = {};
+    size_t nd = 0, ni = 0;
+    YM_REQUIRE(coco_ragged_layout(det_blocks, gt_first, B, max_det, kinds, t.dbl_off, t.int_off, &nd, &ni), "%s: bad sizes", what);
+    if (workspace_bytes < nd * sizeof(double) + ni * sizeof(int) + 256) { ym_set_error("%s: workspace too small", what); return YM_ENOSPC; }
+    if (!any) return YM_OK;                                  // (padding only)
+    int max_groups = 1, max_items = 0;
+    for (int b = 0; b < B; ++b) {
+        const int g = gt_first[b + 1] - gt_first[b];
+        const bool live = image_index[b] >= 0;
+        t.gt_first[b] = gt_first[b];
+        t.log_row[b] = live ? image_index[b] * max_det : -1;
+        if (segm) {
+            t.words[b] = det_blocks[b].img_h * (int)ym_mask_row(true, det_blocks[b].img_w);
+            t.det_off[b] = det_blocks[b].offset;
+            t.gt_off[b] = gt_blocks[b].offset;
+        }
+        t.chunk_first[b + 1] = t.chunk_first[b] + (live && segm ? ym_cdiv(t.words[b], PWORDS) : 0);
+        if (live) {
+            max_groups = max_groups > ym_cdiv(g, MAXR) ? max_groups : ym_cdiv(g, MAXR);
+            max_items = max_items > max_det * (g + 1) ? max_items : max_det * (g + 1);
+        }
+    }
+    t.gt_first[B] = gt_first[B];
+    for (int b = B; b < YM_RAGGED_MAX_IMAGES; ++b) { t.chunk_first[b + 1] = t.chunk_first[B]; t.gt_first[b + 1] = gt_first[B]; t.log_row[b] = -1; }
+    hipStream_t st = (hipStream_t)s;
+    double* dbl = (double*)workspace;
+    int* part = (int*)(dbl + nd);
+    if (segm)
+        hipLaunchKernelGGL(k_coco_inter_ragged, dim3((unsigned)t.chunk_first[B], (unsigned)max_groups), dim3(512), 0, st,
+                           reinterpret_cast<const unsigned long long*>(det_bits), reinterpret_cast<const unsigned long long*>(gt_bits), counts, B,
+                           max_det, t, part);
+    hipLaunchKernelGGL(k_coco_iou_ragged, dim3((unsigned)ym_cdiv(max_items, 64), (unsigned)B), dim3(64 * FSL), 0, st, boxes_px, gt_xywh,
+                       gt_iscrowd, counts, max_det, kinds, t, part, dbl);
+    hipLaunchKernelGGL(k_coco_match_log_ragged, dim3((unsigned)B), dim3(MATCH_THREADS), 0, st, reinterpret_cast<const long long*>(ids), scores,
+                       counts, max_det, boxes_px, kinds, t, (const int*)part, (const double*)dbl, gt_class, gt_iscrowd, gt_area, thresholds, T,
+                       area_rng, num_classes, max_rank, log_score, log_class, log_rank, log_flags, reinterpret_cast<unsigned long long*>(npig),
+                       class_rows);
+    return ym_check_launch(what);
 }

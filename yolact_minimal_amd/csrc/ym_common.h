@@ -38,9 +38,9 @@ struct YmRaggedTable { ym_ragged_image img[YM_RAGGED_MAX_IMAGES]; };
 __host__ __device__ inline size_t ym_mask_row(bool packed, int img_w) { return packed ? (size_t)((img_w + 63) >> 6) : (size_t)img_w; }
 
 // The checks every such table gets: 1..YM_RAGGED_MAX_IMAGES entries, positive sizes, every block at a multiple of
-// YM_RAGGED_ALIGN_BYTES bytes (`esz` = bytes per element of `offset`), no two blocks overlapping; `extent(entry)` = elements per block.
-template <class Extent>
-static inline int ym_check_ragged_table(const char* what, const ym_ragged_image* images, int B, int64_t esz, Extent extent) {
+// YM_RAGGED_ALIGN_BYTES bytes (`esz` = bytes per element of `offset`), no two blocks overlapping; `extent_of(b)` = elements of block b.
+template <class ExtentOf>
+static inline int ym_check_ragged_table_indexed(const char* what, const ym_ragged_image* images, int B, int64_t esz, ExtentOf extent_of) {
     YM_REQUIRE(images, "%s: null image table", what);
     YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
     for (int b = 0; b < B; ++b) {
@@ -51,9 +51,15 @@ static inline int ym_check_ragged_table(const char* what, const ym_ragged_image*
     }
     for (int a = 0; a < B; ++a)          // (B <= 32: a few hundred compares)
         for (int b = a + 1; b < B; ++b)
-            YM_REQUIRE(images[a].offset + extent(images[a]) <= images[b].offset || images[b].offset + extent(images[b]) <= images[a].offset,
+            YM_REQUIRE(images[a].offset + extent_of(a) <= images[b].offset || images[b].offset + extent_of(b) <= images[a].offset,
                        "%s: the blocks of images %d and %d overlap", what, a, b);
     return YM_OK;
+}
+
+// ... with the extent as a function of the entry alone: `extent(entry)` = elements per block.
+template <class Extent>
+static inline int ym_check_ragged_table(const char* what, const ym_ragged_image* images, int B, int64_t esz, Extent extent) {
+    return ym_check_ragged_table_indexed(what, images, B, esz, [&](int b) { return extent(images[b]); });
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to ONE DEVICE's copy of a kernel: a process that drives a second GPU (nms_batch

@@ -53,6 +53,7 @@ ABI_SYMBOLS = (
     'ym_val_preprocess_window', 'ym_after_nms_window_workspace_bytes', 'ym_after_nms_window', 'ym_after_nms_window_packed',
     'ym_mask_loss_batch_window', 'ym_mask_loss_fwd_bwd_window', 'ym_train_aug_image_batch_window', 'ym_train_aug_masks_batch_window',
     'ym_pack_masks_ragged', 'ym_eval_add_ragged_workspace_bytes', 'ym_eval_add_ragged_packed',
+    'ym_eval_coco_add_ragged_workspace_bytes', 'ym_eval_coco_add_ragged_packed',
 )
 
 
@@ -340,6 +341,12 @@ def lib():
         L.ym_coco_accumulate_workspace_bytes.argtypes = [i64]
         L.ym_coco_accumulate_workspace_bytes.restype = sz
         L.ym_coco_accumulate.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, vp, i32, i32, i32, ctypes.c_double, i32, vp, vp, vp, sz, vp]
+        L.ym_eval_coco_add_ragged_workspace_bytes.argtypes = [ctypes.POINTER(RaggedImage), ctypes.POINTER(ctypes.c_int32), i32, i32, i32]
+        L.ym_eval_coco_add_ragged_workspace_bytes.restype = sz
+        L.ym_eval_coco_add_ragged_packed.argtypes = [vp, vp, vp, vp, i32, i32, vp, ctypes.POINTER(RaggedImage), vp, vp, vp, vp,
+                                                     ctypes.POINTER(ctypes.c_int32), vp, ctypes.POINTER(RaggedImage),
+                                                     ctypes.POINTER(ctypes.c_int64), vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp,
+                                                     vp, vp, sz, vp]
         for name in ABI_SYMBOLS:
             fn = getattr(L, name)
             if name not in ('ym_last_error', 'ym_conv2d_workspace_bytes', 'ym_nms_workspace_bytes',
@@ -349,7 +356,7 @@ def lib():
                             'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes',
                             'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes',
                             'ym_ann_to_mask_ragged_workspace_bytes', 'ym_after_nms_window_workspace_bytes',
-                            'ym_eval_add_ragged_workspace_bytes'):
+                            'ym_eval_add_ragged_workspace_bytes', 'ym_eval_coco_add_ragged_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

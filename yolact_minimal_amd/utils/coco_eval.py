@@ -12,7 +12,12 @@ where the LAST gt wins among equal IoUs.  Parity with the real cocoapi is unpinn
 `summarize` is host numpy on those grids (`summarize_grids`, exactly cocoapi's `_summarize`).  Every image handed to `add` counts,
 also one without detections (its gts lower recall); `score_results` hands it every image of the annotation file, as `COCOeval` does.
 
-Ground truth comes from the annotation file (`coco_gt`), not from the val loader, which drops crowds and normalises boxes.
+`add_batch` is the metric stage of a whole request of B <= 32 images of different sizes in ONE call
+(`ym_eval_coco_add_ragged_packed`: at most three launches, packed masks only) against a `COCOGtBatch`; the log is the one B `add`
+calls leave.  `evaluate.evaluate_coco_pipelined` drives either with several requests in flight.
+
+Ground truth comes from the annotation file (`coco_gt`, `coco_gt_batch`), not from the val loader, which drops crowds and normalises
+boxes.
 
 Not covered: `keypoints`, `useCats = 0`, merging evaluators across ranks, NaN scores, more than 512 gts per image.
 """
@@ -129,6 +134,116 @@ def coco_gt(coco, image_id, label_map, device='cuda', masks=True):
         m = PackedMasks.pack(anns_to_masks([r['segmentation'] for r in rec], h, w, device))
     return COCOGt.from_arrays([r['cls'] for r in rec], [r['iscrowd'] for r in rec], [r['area'] for r in rec],
                               [r['bbox'] for r in rec], m, h, w, device)
+
+
+def _resolved(device):
+    """`device` with its index filled in: 'cuda' names the current device, so it equals 'cuda:N' for that N."""
+    d = torch.device(device)
+    return torch.device('cuda', torch.cuda.current_device()) if d.type == 'cuda' and d.index is None else d
+
+
+class COCOGtBatch:
+    """The ground truth of the B <= 32 images of one request on the device, as `ym_eval_coco_add_ragged_packed` takes it:
+    `sizes` [(height, width)] and `first` [B + 1] on the host (image b owns the annotations `first[b] .. first[b + 1]`); `cls` int32
+    [G], `crowd` uint8 [G], `area` float64 [G], `bbox` float64 [G, 4] (None when G = 0); with masks, `bits` = ONE flat int64 tensor of
+    packed blocks `[g_b, h_b, ceil(w_b / 64)]` at `offsets[b]` (every block at a multiple of 256 bytes; None when G = 0) and `table`,
+    their `hip.ragged_table`.  `table is None`: the bundle has no masks ('bbox' only)."""
+
+    __slots__ = ('sizes', 'first', 'cls', 'crowd', 'area', 'bbox', 'bits', 'offsets', 'table', 'device')
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def masks(self, b):
+        """Image b's gt masks: a `PackedMasks` view `[g_b, h_b, w_b]` of `bits` (None without masks or without annotations)."""
+        g, (h, w) = self.first[b + 1] - self.first[b], self.sizes[b]
+        if self.table is None or not g:
+            return None
+        wq = (w + 63) // 64
+        return PackedMasks(self.bits[self.offsets[b]:self.offsets[b] + g * h * wq].view(g, h, wq), h, w)
+
+    @classmethod
+    def _empty(cls_, sizes, g, device, masks, what):
+        self = object.__new__(cls_)
+        self.sizes, self.device = [(int(h), int(w)) for h, w in sizes], torch.device(device)
+        self.first = [0]
+        for v in g:
+            self.first.append(self.first[-1] + int(v))
+        self.cls = self.crowd = self.area = self.bbox = self.bits = self.offsets = self.table = None
+        if masks:
+            rows = iter(g)                                      # (aligned_layout asks for the extents in image order)
+            self.offsets, total = hip.aligned_layout(what, self.sizes, 8, lambda h, w: next(rows) * h * ((w + 63) // 64))
+            self.table = hip.ragged_table(self.sizes, self.offsets)
+            if self.first[-1]:
+                self.bits = torch.empty(max(total, 1), dtype=torch.int64, device=self.device)
+        elif not 1 <= len(self.sizes) <= hip.RAGGED_MAX_IMAGES:
+            raise RuntimeError(f'{what}: 1 .. {hip.RAGGED_MAX_IMAGES} images per call, got {len(self.sizes)}')
+        return self
+
+    @classmethod
+    def from_gts(cls_, gts):
+        """The per-image bundles `[COCOGt, ...]` of a request as one: device-side concatenation of the scalar fields and one copy
+        of every image's packed masks into its block.  The bundle has masks when every image that has annotations brought them."""
+        what = 'COCOGtBatch.from_gts'
+        gts = list(gts)
+        if not gts or any(not isinstance(gt, COCOGt) for gt in gts):
+            raise RuntimeError(f'{what}: a non-empty list of COCOGt expected')
+        live = [gt for gt in gts if gt.g]
+        masks = all(gt.masks is not None for gt in live)
+        self = cls_._empty([(gt.height, gt.width) for gt in gts], [gt.g for gt in gts], gts[0].cls.device, masks, what)
+        if live:
+            join = lambda ts: ts[0].contiguous() if len(ts) == 1 else torch.cat(ts, 0)   # noqa: E731
+            self.cls, self.crowd = join([gt.cls for gt in live]), join([gt.crowd for gt in live])
+            self.area, self.bbox = join([gt.area for gt in live]), join([gt.bbox for gt in live])
+        if masks:
+            for b, gt in enumerate(gts):
+                if gt.g:
+                    if (gt.masks.height, gt.masks.width) != (gt.height, gt.width):
+                        raise RuntimeError(f'{what}: image {b}: masks of {gt.masks.height} x {gt.masks.width} in a {gt.height} x {gt.width} image')
+                    self.masks(b).bits.copy_(gt.masks.bits)
+        return self
+
+
+def coco_gt_batch(coco, image_ids, label_map, device='cuda', masks=True, live=None):
+    """The gt bundle of the images `image_ids` (at most 32) of the `COCO` index, built from the annotation file: `coco_gt_records`
+    per image, ONE upload of the scalar fields, and with `masks` one `anns_to_masks_batch` (the ragged rasteriser) plus ONE
+    `ym_pack_masks_ragged` launch.  Equal to `COCOGtBatch.from_gts([coco_gt(coco, i, ...) for i in image_ids])`.  `live`: one flag
+    per image; an entry whose flag is false is a request's padding and brings its size only (no annotation of it is decoded,
+    uploaded or rasterised)."""
+    from .coco import anns_to_masks_batch
+    what = 'coco_gt_batch'
+    dev = torch.device(device)
+    image_ids = list(image_ids)
+    live = [True] * len(image_ids) if live is None else list(live)
+    if len(live) != len(image_ids):
+        raise RuntimeError(f'{what}: {len(image_ids)} image ids but {len(live)} live flags')
+    recs = [coco_gt_records(coco, i, label_map) if keep else [] for i, keep in zip(image_ids, live)]
+    sizes = [(int(coco.imgs[i]['height']), int(coco.imgs[i]['width'])) for i in image_ids]
+    g = [len(r) for r in recs]
+    self = COCOGtBatch._empty(sizes, g, dev, masks, what)
+    flat = [r for rec in recs for r in rec]
+    total = len(flat)
+    if not total:
+        return self
+    with torch.cuda.device(dev):
+        # bbox fp64 [G][4] | area fp64 [G] | cls int32 [G] | crowd uint8 [G] in one host buffer: every array starts at a multiple of its
+        # element size
+        host = np.empty(45 * total, np.uint8)
+        host[:32 * total].view(np.float64)[:] = np.asarray([r['bbox'] for r in flat], np.float64).reshape(-1)
+        host[32 * total:40 * total].view(np.float64)[:] = [r['area'] for r in flat]
+        host[40 * total:44 * total].view(np.int32)[:] = [r['cls'] for r in flat]
+        host[44 * total:] = [r['iscrowd'] for r in flat]
+        up = torch.from_numpy(host).to(dev)
+        self.bbox, self.area = up[:32 * total].view(torch.float64).view(total, 4), up[32 * total:40 * total].view(torch.float64)
+        self.cls, self.crowd = up[40 * total:44 * total].view(torch.int32), up[44 * total:]
+        if masks:
+            dense = anns_to_masks_batch([[r['segmentation'] for r in rec] for rec in recs], sizes, dev)
+            own = [b for b in range(len(sizes)) if g[b]]
+            hip.check(hip.lib().ym_pack_masks_ragged(
+                (ctypes.c_void_p * len(own))(*[dense[b].data_ptr() for b in own]), 1, (ctypes.c_int32 * len(own))(*[g[b] for b in own]),
+                hip.ragged_table([sizes[b] for b in own], [self.offsets[b] for b in own]), len(own), hip.ptr(self.bits, torch.int64),
+                hip.stream_ptr()), 'ym_pack_masks_ragged')
+    return self
 
 
 class DeviceCOCOeval:
@@ -292,6 +407,92 @@ class DeviceCOCOeval:
             self._seen.add(index)
             self._writers[cur.cuda_stream] = cur
         return index
+
+    def add_batch(self, ids, scores, boxes_px, masks, counts, gt_batch, image_indices, mask_table=None):
+        """One request of B <= 32 images of different sizes in ONE call (`ym_eval_coco_add_ragged_packed`: at most three launches
+        and nothing else on the device); the log and the counters end up exactly as after `add` on each image.  Runs on the
+        current stream; no host read.
+          ids / scores `[B, max_det]`, boxes_px int32 `[B, max_det, 4]`, counts int32 `[B]`: `after_nms_batch(..., sync=False)` rows,
+          with `max_det` the evaluator's.  Without 'bbox', `boxes_px` may be None: every row below its count is then a detection
+          (with the boxes, a row whose pixel box is empty is none, `eval.py:65`);
+          masks ('segm' only, else ignored): the list of B `PackedMasks` views that `after_nms_batch(dets, hs, ws, ..., packed=True)`
+          returns -- or, with `mask_table` (their `hip.ragged_table`), view 0 alone.  Dense masks raise;
+          gt_batch: the `COCOGtBatch` of the B images (`coco_gt_batch` / `COCOGtBatch.from_gts`);
+          image_indices: B image slots, `None` = the entry is padding (nothing of it is read, written or counted).
+        Returns the slots added.  A refused call (bad arguments, more than 512 annotations in an image) consumes no image index and
+        writes no log row; like `add`, it may already have grown the log for its largest index (capacity and buffers change, contents
+        do not) when the refusal comes from the C entry."""
+        from .draw import _ragged_mask_table
+        from .output_utils import _scratch
+        what = 'DeviceCOCOeval.add_batch'
+        if not isinstance(gt_batch, COCOGtBatch):
+            raise RuntimeError(f'{what}: gt_batch is a COCOGtBatch (coco_gt_batch / COCOGtBatch.from_gts)')
+        sizes, gt_first = gt_batch.sizes, gt_batch.first
+        batch, md = len(sizes), self.max_det
+        segm, bbox = 'segm' in self.kinds, 'bbox' in self.kinds
+        if tuple(ids.shape) != (batch, md) or tuple(scores.shape) != (batch, md) or (boxes_px is None and bbox) or \
+                (boxes_px is not None and tuple(boxes_px.shape) != (batch, md, 4)) or counts is None or counts.numel() != batch or \
+                len(image_indices) != batch:
+            raise RuntimeError(f'{what}: ids / scores [{batch}, {md}], boxes_px [{batch}, {md}, 4], {batch} counts and {batch} image indices '
+                               f"expected (max_det is the evaluator's; the gt bundle holds {batch} images), got {tuple(ids.shape)} / "
+                               f'{tuple(scores.shape)} / {None if boxes_px is None else tuple(boxes_px.shape)}')
+        if _resolved(gt_batch.device) != _resolved(self.device):
+            raise RuntimeError(f'{what}: the gt bundle is on {gt_batch.device}, the evaluator on {self.device}')
+        if segm:
+            if gt_batch.table is None:
+                raise RuntimeError(f"{what}: 'segm' needs a gt bundle with masks")
+            if mask_table is None:
+                first = masks[0] if isinstance(masks, (list, tuple)) and len(masks) else masks
+                if not isinstance(first, PackedMasks):
+                    raise RuntimeError(f'{what}: the batched metric stage takes packed masks only (after_nms_batch(..., packed=True))')
+                masks, mask_table = _ragged_mask_table(masks, sizes, md, what)
+            elif not isinstance(masks, PackedMasks):
+                raise RuntimeError(f'{what}: the batched metric stage takes packed masks only (after_nms_batch(..., packed=True))')
+        index = [-1 if i is None else int(i) for i in image_indices]
+        live = [i for i in index if i >= 0]
+        if any(i < 0 for i, given in zip(index, image_indices) if given is not None) or len(set(live)) != len(live) or \
+                any(i in self._seen for i in live):
+            raise RuntimeError(f'{what}: image indices {live} are negative, repeated or were added before')
+        most = max(gt_first[b + 1] - gt_first[b] for b in range(batch))
+        if most > hip.COCO_MAX_GT:
+            raise RuntimeError(f'{what}: at most {hip.COCO_MAX_GT} ground-truth annotations per image, got {most}')
+        if not live:
+            return []
+        kinds = sum(1 << KINDS.index(kd) for kd in self.kinds)
+        L = hip.lib()
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            first_c = (ctypes.c_int32 * (batch + 1))(*gt_first)
+            index_c = (ctypes.c_int64 * batch)(*index)
+            nbytes = L.ym_eval_coco_add_ragged_workspace_bytes(mask_table if segm else None, first_c, batch, md, kinds)
+            if nbytes == 0:
+                raise RuntimeError(f'{what}: ym_eval_coco_add_ragged_workspace_bytes refuses these sizes (h * ceil(w / 64) < 2^24 words per '
+                                   f'mask): {sizes}, gt rows {gt_first}')
+            ws = _scratch(self.device, nbytes)
+            # (the log grows for the largest index first; like `add`, the indices are consumed only behind the launch that writes them)
+            if max(live) >= self.capacity:
+                cap = self.capacity
+                while cap <= max(live):
+                    cap *= 2
+                self._grow(cap)
+            elif self._grown is not None and cur.cuda_stream not in self._synced:
+                cur.wait_event(self._grown)
+                self._synced.add(cur.cuda_stream)
+            have = gt_first[-1] > 0
+            hip.check(L.ym_eval_coco_add_ragged_packed(
+                hip.ptr(ids, torch.int64), hip.ptr(scores), hip.ptr(boxes_px, torch.int32), hip.ptr(counts, torch.int32), batch, md,
+                hip.ptr(masks.bits, torch.int64) if segm else None, mask_table if segm else None,
+                hip.ptr(gt_batch.cls, torch.int32) if have else None, hip.ptr(gt_batch.crowd, torch.uint8) if have else None,
+                hip.ptr(gt_batch.area, torch.float64) if have else None, hip.ptr(gt_batch.bbox, torch.float64) if have and bbox else None,
+                first_c, hip.ptr(gt_batch.bits, torch.int64) if have and segm else None, gt_batch.table if segm else None, index_c,
+                hip.ptr(self.thr, torch.float64), len(self.params.iouThrs), hip.ptr(self.area_rng, torch.float64), self.num_classes,
+                int(max(self.params.maxDets)), kinds, hip.ptr(self.score), hip.ptr(self.cls, torch.int32),
+                hip.ptr(self.rank, torch.int32), hip.ptr(self.flags, torch.int32), self.capacity * md, hip.ptr(self.npig, torch.int64),
+                hip.ptr(self.class_rows, torch.int32), ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()),
+                'ym_eval_coco_add_ragged_packed')
+            self._seen.update(live)
+            self._writers[cur.cuda_stream] = cur
+        return live
 
     # ---- accumulate / summarize ---------------------------------------------------------------------------------------------
     def _sorted_order(self):

@@ -261,4 +261,4 @@ def save_latest(net, cfg_name, step):
 
 
 from .device_metrics import DeviceAPData  # noqa: E402,F401  (the device-resident accumulator; it imports map_table from here lazily)
-from .coco_eval import DeviceCOCOeval, coco_gt, score_results  # noqa: E402,F401  (the COCO-protocol evaluator: eval.py --coco_api's second half)
+from .coco_eval import COCOGtBatch, DeviceCOCOeval, coco_gt, coco_gt_batch, score_results  # noqa: E402,F401  (the COCO-protocol evaluator: eval.py --coco_api's second half)
