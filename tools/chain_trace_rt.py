@@ -4,6 +4,8 @@ between CU groups (found in round 4: up to 16 ms apart inside one XCD), so its c
 not trustworthy; here the trace build stamps s_memrealtime (100 MHz, chip-wide) and the stamped launches are CAPTURED in a hipGraph
 (eager launches are spaced by the host).  Per launch: dispatch ramp (first -> last workgroup entry), duration (first entry -> last
 exit), the phases of the workgroup that exits LAST (what the next launch waits for), and the dead time to the next launch.
+The wave kernels also record the counter read by their FIRST instruction (YM_TRACE_ENTRY_PTR): stamp 0 needs the trace pointer, an
+argument, so "entry -> stamp 0" is the first batch of argument loads and "entry -> first tile landed" the whole prologue.
 
     python tools/chain_trace_rt.py [bs] [hw] [blocks]
 """
@@ -12,7 +14,8 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ['YM_LIB_PATH'] = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'trace', 'libyolact_hip_trace.so')
+# (YM_TRACE_LIB: another trace build, e.g. an older commit's, to compare against)
+os.environ['YM_LIB_PATH'] = os.environ.get('YM_TRACE_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'trace', 'libyolact_hip_trace.so')
 import torch  # noqa: E402
 from yolact_minimal_amd import hip  # noqa: E402
 from yolact_minimal_amd.conv_plan import ConvPlan  # noqa: E402
@@ -47,15 +50,18 @@ descs[2][2].seg[0].out = x_wide.data_ptr()
 descs[2][2].scale = None
 n = 3 * nblocks
 trace = torch.zeros(n * REGION, dtype=torch.int64, device=dev)
+entry = torch.zeros(n * (REGION // 4), dtype=torch.int64, device=dev)
 
 
 def run(stamp):
     for k in range(n):
         if stamp:
             os.environ['YM_TRACE_PTR'] = str(trace.data_ptr() + k * REGION * 8)
+            os.environ['YM_TRACE_ENTRY_PTR'] = str(entry.data_ptr() + k * (REGION // 4) * 8)
             os.environ['YM_TRACE_REALTIME'] = os.environ.get('YM_CHAIN_RT', '1')
         else:
             os.environ.pop('YM_TRACE_PTR', None)
+            os.environ.pop('YM_TRACE_ENTRY_PTR', None)
         hip.conv2d_fwd(descs[k % 3][2], ws)
 
 
@@ -85,6 +91,7 @@ for name, stamp in (('no stamps', False), ('stamped', True)):
 raw = trace.cpu().reshape(n, REGION // 4, 4).clone()
 raw[:, :, 0] &= (1 << 60) - 1
 raw = raw.double() / 100.0             # s_memrealtime: 100 MHz -> us
+ent = entry.cpu().reshape(n, REGION // 4).double() / 100.0
 print('per launch [us]: WGs | ramp (first->last entry) | duration (first entry->last exit) | median exit, last exit after first entry | '
       'LAST workgroup: entry +, prologue / K loop / epilogue | mean prologue / K loop / epilogue | dead time to next launch')
 tot = {}
@@ -105,6 +112,17 @@ for k in range(n):
         t.append(row)
     print(f"  {k:2d} {descs[k % 3][0]:32s} {row['wgs']:4d} | {row['ramp']:5.2f} | {row['dur']:6.2f} | {row['med_exit']:6.2f} {row['dur']:6.2f} | "
           f"+{row['l_entry']:5.2f}  {row['l_pro']:5.2f} / {row['l_k']:5.2f} / {row['l_epi']:5.2f} | {row['pro']:5.2f} / {row['kl']:5.2f} / {row['epi']:5.2f} | {gap:6.2f}")
+print('prologue split of the wave kernels, means over the workgroups of the launches of blocks 1.. [us]: '
+      'entry -> stamp 0 (first argument batch) | stamp 0 -> first tile landed | entry -> first tile landed')
+for c in range(3):
+    a0, a1, a2, cnt = 0.0, 0.0, 0.0, 0
+    for k in range(3 + c, n, 3):
+        ok = (raw[k, :, 0] > 0) & (raw[k, :, 1] > 0) & (ent[k] > 0)
+        if int(ok.sum()):
+            a0 += float((raw[k, ok, 0] - ent[k, ok]).sum()); a1 += float((raw[k, ok, 1] - raw[k, ok, 0]).sum())
+            a2 += float((raw[k, ok, 1] - ent[k, ok]).sum()); cnt += int(ok.sum())
+    if cnt:
+        print(f"  {descs[c][0]:32s} {descs[c][1]} {a0 / cnt:5.2f} | {a1 / cnt:5.2f} | {a2 / cnt:5.2f}   ({cnt} workgroups)")
 print('means over blocks 1..:')
 for c, rows in sorted(tot.items()):
     m = {k_: sum(r_[k_] for r_ in rows if r_[k_] == r_[k_]) / max(1, sum(1 for r_ in rows if r_[k_] == r_[k_])) for k_ in rows[0]}

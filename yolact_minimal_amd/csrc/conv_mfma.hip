@@ -51,6 +51,7 @@ constexpr int PITCH = 36;  // floats
 template <int BM, int BN, int MODE, int NS, bool DL = false, bool PF = false, bool RG = false, int SPL = 0>
 __global__ __launch_bounds__(256) void conv_igemm_f32(const ConvP p) {
     static_assert(SPL == 0 || (SPL <= 3 && !DL && !PF && (NS == 2 || NS == 3) && MODE != 1), "split-bf16: register staging, Cin % 32 == 0");
+    ym_fetch_conv_hot(p);
     constexpr int LB = SPL ? 2 : NS;            // LDS buffers (split mode: always two; NS = 3 there means two REGISTER sets)
     constexpr int TM = BM / 64, TN = BN / 64;   // 32x32 MFMA tiles per wave (wave tile = BM/2 x BN/2)
     constexpr int AR = BM / 32, BR = BN / 32;   // staging rows per thread
@@ -987,7 +988,7 @@ int fill_params(const ym_conv_desc* d, const Plan& pl, void* workspace, ConvP& p
     p.bn_sum = d->bn_sum; p.bn_sumsq = d->bn_sumsq; p.bn_ordered = (d->bn_sum && d->bn_ordered) ? 1 : 0;
     p.bnb_y = d->bnb_y; p.bnb_out = d->bnb_out; p.bnb_mean = d->bnb_mean; p.bnb_invstd = d->bnb_invstd;
     p.bnb_gamma = d->bnb_gamma; p.bnb_beta = d->bnb_beta; p.bnb_relu = d->bnb_relu;
-    p.trace = nullptr; p.trace_epoch = nullptr; p.trace_ring = 0; p.trace_stride = 0; p.trace_rt = 0; p.trace_hw = nullptr;
+    p.trace = nullptr; p.trace_epoch = nullptr; p.trace_ring = 0; p.trace_stride = 0; p.trace_rt = 0; p.trace_hw = nullptr; p.trace_entry = nullptr;
 #ifdef YM_TRACE
     if (const char* e = getenv("YM_TRACE_PTR")) p.trace = (long long*)strtoull(e, nullptr, 10);
     if (const char* e = getenv("YM_TRACE_EPOCH_PTR")) p.trace_epoch = (const int*)strtoull(e, nullptr, 10);
@@ -995,6 +996,7 @@ int fill_params(const ym_conv_desc* d, const Plan& pl, void* workspace, ConvP& p
     if (const char* e = getenv("YM_TRACE_GRID")) p.trace_stride = atoi(e);
     if (const char* e = getenv("YM_TRACE_REALTIME")) p.trace_rt = atoi(e);
     if (const char* e = getenv("YM_TRACE_HW_PTR")) p.trace_hw = (int*)strtoull(e, nullptr, 10);
+    if (const char* e = getenv("YM_TRACE_ENTRY_PTR")) p.trace_entry = (long long*)strtoull(e, nullptr, 10);
     if (p.trace_ring <= 0) p.trace_epoch = nullptr;
     if (const char* e = getenv("YM_PERS_ABL")) { if (!d->bn_sum) p.bnb_relu = atoi(e); }      // conv_persist.hip ablations (trace build only)
 #endif

@@ -57,6 +57,7 @@ __global__ __launch_bounds__(256) void conv_igemm_pers(const ConvP p) {
     static_assert(BM == 64 && BN == 64, "the accumulator staging aliases one ring stage: (BM + BN) * 128 B == BM * BN * 4 B");
     static_assert(MODE == 0 || MODE == 2, "Cin % 32 == 0 convolution / data gradient");
     static_assert(NS >= 2 && NS <= 12, "ring depth");
+    ym_fetch_conv_hot(p);
     constexpr int AR = BM / 32, BR = BN / 32;   // staging rows per thread
     constexpr int RP = 32;                      // LDS floats per tile row (unpadded: the DMA places lane l's 16 bytes at base + 16 l)
     constexpr int D = NS - 1;                   // prefetch distance in K tiles

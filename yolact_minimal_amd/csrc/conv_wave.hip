@@ -26,22 +26,47 @@ struct Frag {
     f32x4 v[N][4];   // [tile row-block][k group] : lane holds k = 8g + 4h .. +3 of its row
 };
 
+// Scalar epilogue: outputs that are not one plain NHWC tensor (segments, odd Cout, unaligned operands); epilogue_store of
+// conv_common.h on the wave kernels' own arguments.
+__device__ __forceinline__ void wave_epilogue_store(const WaveArgs& p, const WaveSegs& sg, int m, int n, float acc) {   // sg: *ym_wave_segs()
+    float v = acc;
+    v = __builtin_fmaf(v, p.scale ? p.scale[n] : 1.f, p.shift ? p.shift[n] : 0.f);
+    if (p.residual) v += p.residual[(size_t)m * p.Cout + n];
+    const int b = (int)p.fd_howo.div((unsigned)m), pix = m - b * (int)p.fd_howo.d;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        if (s < sg.nseg && n >= sg.seg[s].n0 && n < sg.seg[s].n1) {
+            const SegDev& g = sg.seg[s];
+            g.out[(size_t)b * g.bstride + (size_t)pix * g.pitch + (n - g.n0)] = ym_apply_act(v, g.act);
+        }
+    }
+}
+
 // Stage a wave's partial (32 TM) x (32 TN) tile in LDS, combine the KW K slices of a tile in a fixed order (deterministic), fused
 // epilogue.  `slabs`: [WPB][32 TM][32 TN + 4] floats of LDS that no DMA targets any more.
 template <int TM, int TN, int KW, int WPB>
-__device__ __forceinline__ void wave_tile_finish(const ConvP& p, float* slabs, f32x16 (&acc)[TM][TN], int wave, int lane, bool tile_ok,
-                                                 int tile_local, int kslice, int m0, int n0) {
+__device__ __forceinline__ void wave_tile_finish(const WaveArgs& p, float* slabs, f32x16 (&acc)[TM][TN], int wave, int lane,
+                                                 bool tile_ok, int tile_local, int kslice, int m0, int n0) {
     constexpr int WM = 32 * TM, WN = 32 * TN;
     constexpr int CP = WN + 4;               // LDS pitch of a staged tile (floats)
     const int frag_row = lane & 31, khalf = lane >> 5;
     // the residual rows of this lane are requested before the tile is staged (a wave with a tile of its own makes up to four
-    // passes over it: four dependent global loads took 3.3 us of a 14.5 us launch, tools/chain_trace_rt.py)
+    // passes over it: four dependent global loads took 3.3 us of a 14.5 us launch, tools/chain_trace_rt.py); the BatchNorm scale
+    // and shift of its columns likewise: behind the barrier they were one more dependent global round trip of every tile
     constexpr int C4_ = WN / 4, LANES_ = KW * 64, NPASS = (WM * C4_ + LANES_ - 1) / LANES_;
     f32x4 pre_res[NPASS];
+    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+    if (p.vec && tile_ok) {
+        const int n_ = n0 + ((kslice * 64 + lane) % C4_) * 4;
+        if (n_ < p.Cout) {
+            if (p.scale) sc = *reinterpret_cast<const f32x4*>(p.scale + n_);
+            if (p.shift) sh = *reinterpret_cast<const f32x4*>(p.shift + n_);
+        }
+    }
     const bool pre = p.vec && p.residual != nullptr && tile_ok;
     if (pre) {
         const int lt_ = kslice * 64 + lane, col4_ = lt_ % C4_, row0_ = lt_ / C4_;
-        const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc((void*)p.residual, 0, (unsigned)((size_t)p.M * p.Cout * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc((void*)p.residual, 0, p.res_bytes, 0x00020000);
 #pragma unroll
         for (int k = 0; k < NPASS; ++k) {
             const int m = m0 + row0_ + k * (LANES_ / C4_), n = n0 + col4_ * 4;
@@ -66,10 +91,7 @@ __device__ __forceinline__ void wave_tile_finish(const ConvP& p, float* slabs, f
         const int col4 = lt % C4, row0 = lt / C4;
         const int n = n0 + col4 * 4;
         if (n < p.Cout) {
-            f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-            if (p.scale) sc = *reinterpret_cast<const f32x4*>(p.scale + n);
-            if (p.shift) sh = *reinterpret_cast<const f32x4*>(p.shift + n);
-            const int act = p.seg[0].act;
+            const int act = p.act;
 #pragma unroll
             for (int k = 0; k < NPASS; ++k) {
                 const int row = row0 + k * (LANES / C4);
@@ -82,10 +104,11 @@ __device__ __forceinline__ void wave_tile_finish(const ConvP& p, float* slabs, f
                 if (p.residual) v += pre_res[k];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = ym_apply_act(v[e], act);
-                *reinterpret_cast<f32x4*>(p.seg[0].out + (size_t)m * p.Cout + n) = v;
+                *reinterpret_cast<f32x4*>(p.out + (size_t)m * p.Cout + n) = v;
             }
         }
     } else {
+        const WaveSegs& sg = *ym_wave_segs();
         for (int e = lt; e < WM * WN; e += LANES) {
             const int row = e / WN, col = e - row * WN;
             const int m = m0 + row, n = n0 + col;
@@ -93,7 +116,7 @@ __device__ __forceinline__ void wave_tile_finish(const ConvP& p, float* slabs, f
                 float v = slab0[row * CP + col];
 #pragma unroll
                 for (int s = 1; s < KW; ++s) v += slab0[(size_t)s * WM * CP + row * CP + col];
-                epilogue_store(p, m, n, v);
+                wave_epilogue_store(p, sg, m, n, v);
             }
         }
     }
@@ -101,7 +124,8 @@ __device__ __forceinline__ void wave_tile_finish(const ConvP& p, float* slabs, f
 
 // TM,TN: 32x32 MFMA tiles per wave; KW: waves sharing one output tile (K split); WPB: waves per block
 template <int TM, int TN, int KW, int WPB>
-__global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const ConvP p) {
+__global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const WaveArgs p, const WaveSegs) {
+    ym_fetch_wave_args(p);
     constexpr int TPB = WPB / KW;            // output tiles per block
     constexpr int WM = 32 * TM, WN = 32 * TN;
     constexpr int D = 3;                     // register ring depth
@@ -112,12 +136,13 @@ __global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const ConvP p) {
     const int tile_local = wave / KW, kslice = wave - tile_local * KW;
     const int frag_row = lane & 31, khalf = lane >> 5;
 
-    const int bid = ym_xcd_remap(blockIdx.x, gridDim.x);
+    const int bid = ym_xcd_remap(blockIdx.x, p.remap_n);
     const int tile = bid * TPB + tile_local;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const bool tile_ok = tile < ntiles;
-    const int tile_m = tile_ok ? tile / p.tiles_n : 0, tile_n = tile_ok ? tile - tile_m * p.tiles_n : 0;
+    const bool tile_ok = tile < p.ntiles;
+    int tile_m = 0, tile_n = 0;
+    if (tile_ok) ym_tile_decode(p, tile, tile_m, tile_n);        // (the launch sets ONE group: tile ids run n-fastest)
     const int m0 = tile_m * WM, n0 = tile_n * WN;
+    const int Cin = (int)p.fd_cin.d, KW_ = (int)p.fd_kw.d;
 
     // ---- per-lane operand rows -----------------------------------------------------------------
     int a_pix[TM], a_ih0[TM], a_iw0[TM];
@@ -125,11 +150,16 @@ __global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const ConvP p) {
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + i * 32 + frag_row;
         if (tile_ok && m < p.M) {
-            const int b = m / p.HoWo, rem = m - b * p.HoWo;
-            const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
-            a_ih0[i] = oh * p.stride - p.pad;
-            a_iw0[i] = ow * p.stride - p.pad;
-            a_pix[i] = (b * p.H + a_ih0[i]) * p.W + a_iw0[i];
+            if (p.fast1x1) {                   // wave-uniform: the row IS the input pixel, its one tap is always inside the image
+                a_ih0[i] = 0; a_iw0[i] = 0; a_pix[i] = m;
+            } else {
+                unsigned ub, urem, uoh, uow;
+                p.fd_howo.divmod((unsigned)m, ub, urem);
+                p.fd_wo.divmod(urem, uoh, uow);
+                a_ih0[i] = (int)uoh * p.stride - p.pad;
+                a_iw0[i] = (int)uow * p.stride - p.pad;
+                a_pix[i] = ((int)ub * p.H + a_ih0[i]) * p.W + a_iw0[i];
+            }
         } else {
             a_ih0[i] = -(1 << 20); a_iw0[i] = -(1 << 20); a_pix[i] = 0;
         }
@@ -138,18 +168,17 @@ __global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const ConvP p) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int n = n0 + j * 32 + frag_row;
-        wrow[j] = (tile_ok && n < p.Cout) ? p.w + (size_t)n * p.Kpad + khalf * 4 : nullptr;
+        wrow[j] = (tile_ok && n < p.Cout) ? p.w + (size_t)n * (p.kpad_bytes / 4) + khalf * 4 : nullptr;
     }
 
     // this wave's K tiles: kslice, kslice + KW, ...   (tap walker is wave-uniform)
     const int nt = tile_ok ? (p.nkt - kslice + KW - 1) / KW : 0;
     int kh, kw, c0;
     {
-        const int k0 = kslice * BK;
-        const int tap = k0 / p.Cin;
-        c0 = k0 - tap * p.Cin;
-        kh = tap / p.KW;
-        kw = tap - kh * p.KW;
+        unsigned tap, uc0, ukh, ukw;
+        p.fd_cin.divmod((unsigned)(kslice * BK), tap, uc0);
+        p.fd_kw.divmod(tap, ukh, ukw);
+        c0 = (int)uc0; kh = (int)ukh; kw = (int)ukw;
     }
     int kt_next = kslice;
 
@@ -162,7 +191,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const ConvP p) {
             const int ih = a_ih0[i] + kh, iw = a_iw0[i] + kw;
             const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
             if (ok) {
-                const float* src = p.in + (size_t)(a_pix[i] + tap_off) * p.Cin + c0 + khalf * 4;
+                const float* src = p.in + (size_t)(a_pix[i] + tap_off) * Cin + c0 + khalf * 4;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) A.v[i][g] = *reinterpret_cast<const f32x4*>(src + g * 8);
             } else {
@@ -183,9 +212,9 @@ __global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const ConvP p) {
         }
         kt_next += KW;
         c0 += BK * KW;
-        while (c0 >= p.Cin) {
-            c0 -= p.Cin;
-            if (++kw == p.KW) { kw = 0; ++kh; }
+        while (c0 >= Cin) {
+            c0 -= Cin;
+            if (++kw == KW_) { kw = 0; ++kh; }
         }
     };
 
@@ -242,7 +271,9 @@ __global__ __launch_bounds__(WPB * 64) void conv_wave_f32(const ConvP p) {
 // dispatcher then balances single tiles over the CUs instead of groups of four (1184 tiles of layer3's conv3 = 296 four-wave
 // workgroups = two of them on 40 of the 256 CUs).
 template <int TM, int TN, int KW, int NS, int WPB = 4>
-__global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
+__global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const WaveArgs p, const WaveSegs) {
+    YM_ENTRY_STAMP();
+    ym_fetch_wave_args(p);
     static_assert(WPB % KW == 0 && WPB <= 4, "the K waves of a tile share a workgroup");
     constexpr int TPB = WPB / KW;            // output tiles per block
     constexpr int WM = 32 * TM, WN = 32 * TN;
@@ -259,22 +290,23 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
     const int tile_local = wave / KW, kslice = wave - tile_local * KW;
     const int frag_row = lane & 31, khalf = lane >> 5;
     YM_STAMP(0);
+    YM_STAMP_ENTRY_STORE();
     // Tail split (ym_conv_desc.tail_tiles, KW == 4 and a 32x32 tile only): 296 tiles on 256 CUs leave 40 CUs with two workgroups, and
     // the launch lasts as long as those (tools/chain_trace_rt.py: layer3's 3x3 at batch 1, median workgroup exit 14.7 us, last 22.7).
     // The LAST tail_tiles tiles are therefore computed as tail_split K slices each, by workgroups that fill the second slot of
     // every CU with a fraction of a tile; their partial tiles meet through the workspace (sc1 stores, arrival counter, the last
     // arriver sums in slice order and runs the epilogue: conv_igemm_f32's exchange) while the whole tiles are still in their K loops.
     constexpr bool TAIL = TM * TN == 1 && KW == 4 && WPB == 4;
-    const bool in_tail = TAIL && (int)blockIdx.x >= p.main_blocks;
+    const bool in_tail = TAIL && (int)blockIdx.x >= p.main_tiles;       // (one workgroup per whole tile: main blocks = main tiles)
     int tile, tslice = 0, tsplit = 1;
     if (in_tail) {
         unsigned q, r;
-        p.fd_tail.divmod(blockIdx.x - (unsigned)p.main_blocks, q, r);
-        tile = p.main_tiles + (int)q; tslice = (int)r; tsplit = p.tail_split;
+        p.fd_tail.divmod(blockIdx.x - (unsigned)p.main_tiles, q, r);
+        tile = p.main_tiles + (int)q; tslice = (int)r; tsplit = (int)p.fd_tail.d;
     } else {
-        tile = ym_xcd_remap(blockIdx.x, TAIL ? p.main_blocks : (int)gridDim.x) * TPB + tile_local;
+        tile = ym_xcd_remap(blockIdx.x, p.remap_n) * TPB + tile_local;
     }
-    const bool tile_ok = tile < p.tiles_m * p.tiles_n;
+    const bool tile_ok = tile < p.ntiles;
     int tile_m = 0, tile_n = 0;
     if (tile_ok) ym_tile_decode(p, tile, tile_m, tile_n);
     const int m0 = tile_m * WM, n0 = tile_n * WN;
@@ -283,28 +315,43 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
 
     // ---- DMA coordinates: instruction i of an operand covers its rows 8 i .. 8 i + 7, lane l fills slot l & 7 of row 8 i + (l >> 3),
     // i.e. fetches chunk (l & 7) ^ ((row >> 1) & 7) = (l & 7) ^ ((4 i + (l >> 4)) & 7) -------------------------------------------------
+    // A 1x1 / stride-1 / unpadded convolution (two of every three layer3 launches) is a plain GEMM: row m is input pixel m, there is
+    // one filter tap, no border.  That path (wave-uniform branch on p.fast1x1) has the lane offsets of A ready here -- no division,
+    // no bounds test -- and its tap walker never fires; rows past M carry the out-of-range marker as on the general path.
     const int drow = lane >> 3;
+    const bool fast = p.fast1x1 != 0;
+    const int Cin = (int)p.fd_cin.d, KW_ = (int)p.fd_kw.d;
     int a_pix[AR], a_ih0[AR], a_iw0[AR];
     unsigned a_off[AR], wrow[BR];
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-        const int m = m0 + 8 * i + drow;
-        if (tile_ok && m < p.M) {
-            unsigned ub, urem, uoh, uow;
-            p.fd_howo.divmod((unsigned)m, ub, urem);
-            p.fd_wo.divmod(urem, uoh, uow);
-            a_ih0[i] = (int)uoh * p.stride - p.pad;
-            a_iw0[i] = (int)uow * p.stride - p.pad;
-            a_pix[i] = ((int)ub * p.H + a_ih0[i]) * p.W + a_iw0[i];
-        } else {
-            a_ih0[i] = -(1 << 20); a_iw0[i] = -(1 << 20); a_pix[i] = 0;
-        }
-    }
 #pragma unroll
     for (int j = 0; j < BR; ++j) {
         const int n = n0 + 8 * j + drow;
         const int c4 = (lane & 7) ^ ((4 * j + (lane >> 4)) & 7);
-        wrow[j] = (tile_ok && n < p.Cout) ? (unsigned)((n * p.Kpad + c4 * 4) * 4) : p.w_bytes;       // past Cout: parked at the buffer's end
+        wrow[j] = (tile_ok && n < p.Cout) ? (unsigned)n * p.kpad_bytes + (unsigned)(c4 * 16) : p.w_bytes;       // past Cout: parked at the buffer's end
+    }
+    if (fast) {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const int m = m0 + 8 * i + drow;
+            const int c4 = (lane & 7) ^ ((4 * i + (lane >> 4)) & 7);
+            a_off[i] = (tile_ok && m < p.M) ? (unsigned)m * p.cin_bytes + (unsigned)(c4 * 16) : OOB;
+            a_pix[i] = 0; a_ih0[i] = 0; a_iw0[i] = 0;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const int m = m0 + 8 * i + drow;
+            if (tile_ok && m < p.M) {
+                unsigned ub, urem, uoh, uow;
+                p.fd_howo.divmod((unsigned)m, ub, urem);
+                p.fd_wo.divmod(urem, uoh, uow);
+                a_ih0[i] = (int)uoh * p.stride - p.pad;
+                a_iw0[i] = (int)uow * p.stride - p.pad;
+                a_pix[i] = ((int)ub * p.H + a_ih0[i]) * p.W + a_iw0[i];
+            } else {
+                a_ih0[i] = -(1 << 20); a_iw0[i] = -(1 << 20); a_pix[i] = 0;
+            }
+        }
     }
 
     // this wave's K tiles: a contiguous range (the filter-tap walker is wave-uniform)
@@ -313,14 +360,14 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
     const int per = (k_hi - k_lo + KW - 1) / KW;
     const int kt_beg = k_lo + kslice * per, kt_end = tile_ok ? min(k_hi, kt_beg + per) : kt_beg;
     const int nt = max(0, kt_end - kt_beg);
-    int kh, kw, c0;
-    {
+    int kh = 0, kw = 0, c0 = kt_beg * BK;
+    if (!fast) {
         unsigned tap, uc0, ukh, ukw;
         p.fd_cin.divmod((unsigned)(kt_beg * BK), tap, uc0);
         p.fd_kw.divmod(tap, ukh, ukw);
         c0 = (int)uc0; kh = (int)ukh; kw = (int)ukw;
     }
-    bool tap_dirty = true;
+    bool tap_dirty = !fast;
     int ld_kt = kt_beg;
     float* ring = smem + (size_t)wave * NS * STAGE;
 
@@ -335,7 +382,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
                 const int ih = a_ih0[i] + kh, iw = a_iw0[i] + kw;
                 const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
                 const int c4 = (lane & 7) ^ ((4 * i + (lane >> 4)) & 7);
-                a_off[i] = (unsigned)(((a_pix[i] + kh * p.W + kw) * p.Cin + c4 * 4) * 4) | (ok ? 0u : OOB);
+                a_off[i] = ((unsigned)(a_pix[i] + kh * p.W + kw) * p.cin_bytes + (unsigned)(c4 * 16)) | (ok ? 0u : OOB);
             }
         }
         float* a = ring + stage * STAGE;           // wave-uniform; lane l lands at + 16 l bytes of each 1 KB block
@@ -354,9 +401,9 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
         }
         ++ld_kt;
         c0 += BK;
-        if (c0 >= p.Cin) {
+        if (!fast && c0 >= Cin) {                  // (1x1 fast path: c0 is the K offset itself; tiles past K are fetched, never consumed)
             c0 = 0;
-            if (++kw == p.KW) { kw = 0; ++kh; }
+            if (++kw == KW_) { kw = 0; ++kh; }
             tap_dirty = true;
         }
     };
@@ -419,7 +466,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
 #ifdef YM_TRACE
     // ablations of the trace build (YM_PERS_ABL -> p.bnb_relu, tools/wave_ablation.py): 1 = operand stream only (DMA + its counted
     // wait, no LDS reads, no MFMAs), 2 = LDS reads + MFMAs only (whatever the ring holds), 3 = MFMAs only (register operands)
-    const int abl = p.bnb_relu;
+    const int abl = p.abl;
 #endif
     auto tile_step = [&](auto S) __attribute__((always_inline)) {
         constexpr int ST = decltype(S)::value;
@@ -472,12 +519,18 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
             // 32x32 tile, 256 lanes: every lane owns ONE float4 of the tile.  Combine the four K waves through LDS, publish the partial
             // tile of this K slice, arrive; the last arriver of the tile sums the slices in slice order and runs the epilogue.
             constexpr int CP = WN + 4;
+            const int lt = threadIdx.x, col4 = lt & 7, row = lt >> 3;
+            const int n = n0 + col4 * 4, m = m0 + row;
+            // (requested ahead of the exchange: whichever workgroup arrives last has them at hand)
+            f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+            if (m < p.M && n < p.Cout) {
+                if (p.scale) sc = *reinterpret_cast<const f32x4*>(p.scale + n);
+                if (p.shift) sh = *reinterpret_cast<const f32x4*>(p.shift + n);
+            }
             float* mine = smem + (size_t)wave * WM * CP;
 #pragma unroll
             for (int r = 0; r < 16; ++r) mine[(4 * khalf + (r & 3) + 8 * (r >> 2)) * CP + frag_row] = acc[0][0][r];
             __syncthreads();
-            const int lt = threadIdx.x, col4 = lt & 7, row = lt >> 3;
-            const int n = n0 + col4 * 4, m = m0 + row;
             f32x4 v = *reinterpret_cast<const f32x4*>(smem + row * CP + col4 * 4);
 #pragma unroll
             for (int w2 = 1; w2 < KW; ++w2) v += *reinterpret_cast<const f32x4*>(smem + (size_t)w2 * WM * CP + row * CP + col4 * 4);
@@ -502,15 +555,12 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
                 f32x4 sum = part[0];
 #pragma unroll
                 for (int s2 = 1; s2 < 8; ++s2) if (s2 < tsplit) sum += part[s2];
-                f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-                if (p.scale) sc = *reinterpret_cast<const f32x4*>(p.scale + n);
-                if (p.shift) sh = *reinterpret_cast<const f32x4*>(p.shift + n);
                 sum = __builtin_elementwise_fma(sum, sc, sh);
                 if (p.residual) sum += *reinterpret_cast<const f32x4*>(p.residual + (size_t)m * p.Cout + n);
-                const int act = p.seg[0].act;
+                const int act = p.act;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) sum[e] = ym_apply_act(sum[e], act);
-                *reinterpret_cast<f32x4*>(p.seg[0].out + (size_t)m * p.Cout + n) = sum;
+                *reinterpret_cast<f32x4*>(p.out + (size_t)m * p.Cout + n) = sum;
             }
             YM_STAMP(3);
             return;
@@ -520,17 +570,46 @@ __global__ __launch_bounds__(WPB * 64) void conv_wdma_f32(const ConvP p) {
     YM_STAMP(3);
 }
 
+// ConvP (what ym_conv2d_fwd filled, with this launch's tiling and tile order set) -> the kernels' own argument block.
+void make_wave_args(const ConvP& p, int remap_n, WaveArgs& a, WaveSegs& sg) {
+    a.in = p.in; a.w = p.w; a.in_bytes = p.in_bytes; a.w_bytes = p.w_bytes;
+    a.main_tiles = p.main_tiles; a.ntiles = p.tiles_m * p.tiles_n;
+    a.fd_tail = p.fd_tail;
+    a.n_groups = p.n_groups; a.fd_grp = p.fd_grp; a.fd_gn = p.fd_gn; a.fd_gn_last = p.fd_gn_last;
+    a.M = p.M; a.Cout = p.Cout;
+    a.fast1x1 = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.Kpad == p.Cin && p.Ho == p.H && p.Wo == p.W;
+    a.cin_bytes = (unsigned)p.Cin * 4u; a.kpad_bytes = (unsigned)p.Kpad * 4u;
+    a.fd_howo = p.fd_howo; a.fd_wo = p.fd_wo;
+    a.stride = p.stride; a.pad = p.pad; a.H = p.H; a.W = p.W;
+    a.nkt = p.nkt; a.tail_ktps = p.tail_ktps;
+    a.fd_cin = p.fd_cin; a.fd_kw = p.fd_kw;
+    a.residual = p.residual; a.scale = p.scale; a.shift = p.shift; a.out = p.seg[0].out;
+    a.ws = p.ws; a.counters = p.counters;
+    a.res_bytes = (unsigned)((size_t)p.M * p.Cout * 4); a.ws_bytes = p.ws_bytes;
+    a.vec = p.vec; a.act = p.seg[0].act; a.remap_n = remap_n;
+    for (unsigned& r : a.reserved_) r = 0;
+#ifdef YM_TRACE
+    a.trace = p.trace; a.trace_epoch = p.trace_epoch; a.trace_ring = p.trace_ring; a.trace_stride = p.trace_stride;
+    a.trace_rt = p.trace_rt; a.abl = p.bnb_relu; a.trace_hw = p.trace_hw; a.trace_entry = p.trace_entry;
+#endif
+    sg.nseg = p.nseg;
+    for (int i = 0; i < 3; ++i) sg.seg[i] = p.seg[i];
+}
+
 template <int TM, int TN, int KW, int WPB>
 int launch(ConvP p, hipStream_t st) {
     constexpr int TPB = WPB / KW;
     p.tiles_m = ym_cdiv(p.M, 32 * TM);
     p.tiles_n = ym_cdiv(p.Cout, 32 * TN);
-    p.ksplit = 1;
+    ym_set_tile_order(p, 1, false);          // one group: tile ids run n-fastest
     const int grid = ym_cdiv(p.tiles_m * p.tiles_n, TPB);
     const size_t lds = (size_t)WPB * 32 * TM * (32 * TN + 4) * sizeof(float);
     static YmLdsAttr attr = {};
     if (int rc = ym_ensure_dyn_lds(attr, reinterpret_cast<const void*>(conv_wave_f32<TM, TN, KW, WPB>), lds, "conv_wave_f32")) return rc;
-    hipLaunchKernelGGL((conv_wave_f32<TM, TN, KW, WPB>), dim3(grid), dim3(WPB * 64), lds, st, p);
+    WaveArgs a;
+    WaveSegs sg;
+    make_wave_args(p, grid, a, sg);
+    hipLaunchKernelGGL((conv_wave_f32<TM, TN, KW, WPB>), dim3(grid), dim3(WPB * 64), lds, st, a, sg);
     return ym_check_launch("conv_wave_f32");
 }
 
@@ -552,18 +631,17 @@ int launch_dma(ConvP p, hipStream_t st) {
     constexpr int TPB = WPB / KW;
     p.tiles_m = ym_cdiv(p.M, 32 * TM);
     p.tiles_n = ym_cdiv(p.Cout, 32 * TN);
-    p.fd_tiles_n = FastDiv::make((unsigned)p.tiles_n);
     ym_set_tile_order(p, 0, true);           // (the wave tiles differ from the planner's: the order is chosen for THIS tiling)
-    p.ksplit = 1;
     int grid = ym_cdiv(p.tiles_m * p.tiles_n, TPB);
-    if (TM * TN == 1 && KW == 4 && WPB == 4) {           // (the caller planned the tail: main_tiles / tail_split / tail_ktps / counters)
-        p.main_blocks = p.main_tiles;
+    if (TM * TN == 1 && KW == 4 && WPB == 4)             // (the caller planned the tail: main_tiles / tail_split / tail_ktps / counters)
         grid = p.main_tiles + (p.tiles_m * p.tiles_n - p.main_tiles) * p.tail_split;
-    }
     const size_t lds = (size_t)WPB * NS * (32 * TM + 32 * TN) * 32 * sizeof(float);
     static YmLdsAttr attr = {};
     if (int rc = ym_ensure_dyn_lds(attr, reinterpret_cast<const void*>(conv_wdma_f32<TM, TN, KW, NS, WPB>), lds, "conv_wdma_f32")) return rc;
-    hipLaunchKernelGGL((conv_wdma_f32<TM, TN, KW, NS, WPB>), dim3(grid), dim3(WPB * 64), lds, st, p);
+    WaveArgs a;
+    WaveSegs sg;
+    make_wave_args(p, TM * TN == 1 && KW == 4 && WPB == 4 ? p.main_tiles : grid, a, sg);
+    hipLaunchKernelGGL((conv_wdma_f32<TM, TN, KW, NS, WPB>), dim3(grid), dim3(WPB * 64), lds, st, a, sg);
     return ym_check_launch("conv_wdma_f32");
 }
 
