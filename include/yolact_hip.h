@@ -839,6 +839,39 @@ int ym_mask_iou_packed(const uint64_t* bits_a, int n, const uint64_t* bits_b, in
 /* ym_rle_encode from bits [n][H][Wq]: same outputs, same "buffers too small" protocol. */
 int ym_rle_encode_packed(const uint64_t* bits, int n, int H, int W, uint32_t* counts, int cap_runs, int32_t* nruns, uint8_t* str,
                          int cap_str, int32_t* str_len, void* workspace, size_t workspace_bytes, ym_stream_t s);
+/* ym_rle_encode_ragged_packed: the detection dump of a whole request (eval.py:59-67, the rows MakeJson.add_bbox / add_mask receive)
+ * for B <= YM_RAGGED_MAX_IMAGES images of different sizes in at most THREE launches (encode, scan, gather), without a host read.
+ * ids / scores [B][max_det], boxes_px [B][max_det][4], counts [B] and det_bits + det_blocks are what ym_after_nms_ragged_packed left
+ * (the uniform entry's [B][max_det][H][Wq] is the table {H, W, b * max_det * H * Wq}); a reader of whole words needs the blocks
+ * 8-byte aligned only: det_bits 8-byte aligned, offsets in words, blocks not overlapping.  `live` is a HOST array of B flags, 0 =
+ * the image is padding; it travels by value with the table.
+ *   Row r of image b is a record iff live[b], r < counts[b] (read on the device) and (box[3] - box[1]) * (box[2] - box[0]) > 0 in
+ * 64-bit integers (eval.py:65).  Every row gets its records[b * max_det + r]; a row that is no record gets all zeros (state 0) and
+ * its mask words are never read.  A record carries the row's class, score and box and the string ym_rle_encode_packed writes for its
+ * mask: the strings of the state-1 rows lie back to back in `strings` in (image, row) order, str_off = the exclusive sum of the
+ * str_len before it (integer sums in a fixed order: the layout is a function of the lengths alone), header = {total string bytes,
+ * records, records of state 2, 0}.  Each mask is encoded into a slab of 4 * cap_runs bytes of the workspace first; a mask of more
+ * than cap_runs runs or a string longer than its slab gets state 2, str_len 0 and the runs it needs in nruns (encode it again with
+ * larger buffers).  Nothing is written past strings_bytes or past a slab.
+ *   Workspace: ym_rle_encode_ragged_workspace_bytes = B * max_det * cap_runs * 4 bytes of transition positions + B * max_det slabs of
+ * 4 * cap_runs bytes, in that order (0 for arguments the entry would refuse).  `strings` holds at least the worst case
+ * B * max_det * 4 * cap_runs bytes.  YM_ENOSPC when either is short.  YM_EINVAL, before any launch, for B outside
+ * 1..YM_RAGGED_MAX_IMAGES, max_det < 1, cap_runs < 1, a width above 4096 or img_h * img_w >= 2^31, blocks that are misaligned or
+ * overlap, B * max_det * 4 * cap_runs >= 2^31, null pointers. */
+typedef struct ym_rle_record {   /* one detection row of a request, 40 bytes */
+    int32_t class_id;            /* ids[b][r] */
+    float   score;
+    int32_t box[4];              /* boxes_px[b][r] */
+    int32_t str_off, str_len;    /* its string in the request's compact buffer */
+    int32_t nruns;               /* runs of the mask (also when state == 2) */
+    int32_t state;               /* 0 no record, 1 encoded, 2 buffers too small */
+} ym_rle_record;
+size_t ym_sizeof_rle_record(void);
+size_t ym_rle_encode_ragged_workspace_bytes(const ym_ragged_image* det_blocks, int B, int max_det, int cap_runs);
+int ym_rle_encode_ragged_packed(const int64_t* ids, const float* scores, const int32_t* boxes_px, const int32_t* counts, int B, int max_det,
+                                const uint64_t* det_bits, const ym_ragged_image* det_blocks, const uint8_t* live, int cap_runs,
+                                ym_rle_record* records, uint8_t* strings, int64_t strings_bytes, int32_t* header, void* workspace,
+                                size_t workspace_bytes, ym_stream_t s);
 /* ym_draw_detections_batch / ym_draw_cutout_objects with the mask term read from bits [B][max_det][H][Wq] / [n][H][Wq]: output
  * bytes identical to the dense calls. */
 int ym_draw_detections_batch_packed(const uint8_t* img, const uint64_t* mask_bits, const int64_t* ids, const float* scores,

@@ -15,7 +15,12 @@ eight `after_nms` calls, each over windows of at least `--window-ms` of back-to-
 The metric stage (`--sections metrics`): the b8_d2 pipeline with `batched_metrics=False` (one `DeviceAPData.add` per image: the
 yardstick) and `True` (one `add_batch` per request), alternated `--rounds` times in the same process; and device and wall time of ONE
 `add_batch` over 8 of those sizes against eight `add` calls on the same rows, at ~100 and at 10 detections per image x 15 gt.
-`--sections` picks among legs, after_nms and metrics (default: all).  Prints one JSON line."""
+The detection dumps (`--sections json`, not in the default set): (a) eight per-image `rle_encode` calls plus the three `.cpu()` reads
+of an image's ids, scores and boxes against ONE `BatchMakeJson.add_batch` plus its collection, on the same eight images; (b) the b8_d2
+pipeline whose results are read back per request and fed to a `MakeJson` image by image (the yardstick) against
+`evaluate_json_pipelined` on the same pipeline, alternated `--rounds` times, each clocked until its records are on the host and until
+its two files are written.  The two dumps must be byte-identical before either is timed.
+`--sections` picks among legs, after_nms, metrics and json (default: the first three).  Prints one JSON line."""
 import argparse
 import gc
 import json
@@ -106,12 +111,127 @@ def metric_stage(padded, sizes8, gts, cfg, nc, dev, args):
     return out
 
 
+def per_image_json(make_json, image_id, ids_p, class_p, boxes_p, masks_p):
+    """One image into a `MakeJson` the way dropin/reference_loops.py's `coco_api='device'` branch does it: three `.cpu()` reads, one
+    `rle_encode`, eval.py:65's filter."""
+    from yolact_minimal_amd.utils.common_utils import rle_encode
+    ids_p = list(ids_p.cpu().numpy().astype(int))
+    class_p = list(class_p.cpu().numpy().astype(float))
+    boxes_p = boxes_p.cpu().numpy()
+    rles = rle_encode(masks_p)
+    for j in range(len(rles)):
+        if (boxes_p[j, 3] - boxes_p[j, 1]) * (boxes_p[j, 2] - boxes_p[j, 0]) > 0:
+            make_json.add_bbox(image_id, ids_p[j], boxes_p[j, :], class_p[j])
+            make_json.add_mask(image_id, ids_p[j], rles[j], class_p[j])
+
+
+def json_stage(padded, args):
+    """(a) the stage alone on the eight images of `padded`: device (HIP events) and wall milliseconds per 8 images."""
+    from yolact_minimal_amd.utils.common_utils import BatchMakeJson, MakeJson
+    ids, scores, boxes_px, masks, counts = padded
+    n = counts.tolist()
+    image_ids = list(range(8))
+
+    def eight(make_json=None):
+        for b in range(8):
+            if make_json is not None:
+                per_image_json(make_json, b, ids[b, :n[b]], scores[b, :n[b]], boxes_px[b, :n[b]], masks[b][:n[b]])
+            else:                                                 # (the stage without the dicts: what add_batch + collect replaces)
+                from yolact_minimal_amd.utils.common_utils import rle_encode
+                ids[b, :n[b]].cpu(), scores[b, :n[b]].cpu(), boxes_px[b, :n[b]].cpu(), rle_encode(masks[b][:n[b]])
+    holder = [BatchMakeJson()]
+
+    def batched():
+        holder[0].add_batch(ids, scores, boxes_px, masks, counts, image_ids)
+        holder[0].wait()
+    one, many = MakeJson(), BatchMakeJson()
+    eight(one)
+    many.add_batch(ids, scores, boxes_px, masks, counts, image_ids)
+    many.finish()
+    assert json.dumps(one.bbox_data) == json.dumps(many.bbox_data) and json.dumps(one.mask_data) == json.dumps(many.mask_data)
+    fns = {'eight_rle_encode': eight, 'add_batch_collect': batched}
+    calls = {k: calls_for(f, args.window_ms) for k, f in fns.items()}
+    rows = {f'{k}_{unit}_ms': [] for k in fns for unit in ('device', 'wall')}
+    for _ in range(args.rounds):
+        for k, f in fns.items():
+            holder[0] = BatchMakeJson()                           # (a window's requests are dropped with it)
+            d, w_ = timed(f, calls[k])
+            rows[k + '_device_ms'].append(round(d, 4))
+            rows[k + '_wall_ms'].append(round(w_, 4))
+    out = summary(rows)
+    out['counts'] = n
+    out['records'] = len(one.mask_data)
+    out['calls_per_window'] = calls
+    return out
+
+
+def json_loop(net, cfg, pipe, loader, args):
+    """(b) the loop at the pipeline's batch and depth: read every request back and feed a `MakeJson` image by image (the yardstick)
+    against `evaluate_json_pipelined`; images per second until the records are on the host, and until the two files are written."""
+    import tempfile
+    from yolact_minimal_amd.evaluate import evaluate_json_pipelined
+    from yolact_minimal_amd.utils.common_utils import MakeJson
+    batch = pipe.batch
+
+    def yardstick(samples):
+        make_json, queued = MakeJson(), []
+
+        def feed(done):
+            first, real = queued.pop(0)
+            for b in range(real):
+                if done[b][0] is not None:
+                    per_image_json(make_json, first + b, *done[b])
+        for first in range(0, len(samples), batch):
+            entries = samples[first:first + batch]
+            real = len(entries)
+            entries = entries + [entries[-1]] * (batch - real)
+            imgs = torch.cat([e[0] for e in entries], 0)
+            queued.append((first, real))
+            done = pipe.submit(imgs, out_hw=[(e[3], e[4]) for e in entries])
+            if done is not None:
+                feed(done)
+        for done in pipe.drain():
+            feed(done)
+        return make_json
+
+    def pipelined(samples):
+        make_json = evaluate_json_pipelined(net, cfg, samples, list(range(len(samples))), pipe=pipe)
+        make_json.wait()
+        return make_json
+
+    def leg(fn, samples, tmp):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        make_json = fn(samples)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        paths = (os.path.join(tmp, 'bbox_detections.json'), os.path.join(tmp, 'mask_detections.json'))
+        make_json.dump(*paths)
+        t2 = time.perf_counter()
+        return len(samples) / (t1 - t0), len(samples) / (t2 - t0), paths
+    fns = {'per_image': yardstick, 'add_batch': pipelined}
+    rows = {f'{k}_{what}': [] for k in fns for what in ('on_host', 'files_written')}
+    with tempfile.TemporaryDirectory() as tmp:
+        files = {}
+        for k, fn in fns.items():                                 # warm-up, then the files at the timed sizes (short last group included)
+            leg(fn, loader(32), tmp)
+            files[k] = [open(p, 'rb').read() for p in leg(fn, loader(args.images - 3), tmp)[2]]
+        assert files['per_image'] == files['add_batch'], 'the per-image dumps and the add_batch dumps differ'
+        for _ in range(args.rounds):
+            for k, fn in fns.items():
+                on_host, written, _ = leg(fn, loader(), tmp)
+                rows[k + '_on_host'].append(round(on_host, 2))
+                rows[k + '_files_written'].append(round(written, 2))
+    return {'img_per_s_rounds': rows, 'img_per_s': summary(rows), 'dumps_identical': True,
+            'dump_bytes': [len(b) for b in files['add_batch']], 'batch': batch, 'depth': pipe.depth}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--images', type=int, default=192, help='images per pass of a leg')
     ap.add_argument('--window-ms', type=float, default=300.0, help='least wall time of a timed window of calls')
-    ap.add_argument('--sections', default='legs,after_nms,metrics', help='comma-separated: legs, after_nms, metrics')
+    ap.add_argument('--sections', default='legs,after_nms,metrics', help='comma-separated: legs, after_nms, metrics, json')
     args = ap.parse_args()
     sections = set(args.sections.split(','))
     assert torch.cuda.is_available(), 'ragged_eval_bench measures on the GPU; there is nothing to measure without one'
@@ -139,7 +259,7 @@ def main():
 
     legs = {'b1_d4': (1, 4), 'b8_d2': (8, 2), 'b4_d2': (4, 2)}
     if 'legs' not in sections:
-        legs = {'b8_d2': (8, 2)} if 'metrics' in sections else {}
+        legs = {'b8_d2': (8, 2)} if sections & {'metrics', 'json'} else {}
     pipes = {k: eval_pipeline(net, cfg, img, 480, 640, depth=d, batch=b) for k, (b, d) in legs.items()}
 
     def leg(name, samples, step=None, batched_metrics=False, keep=None):
@@ -180,6 +300,8 @@ def main():
         result['metric_stage_loop_img_per_s_rounds'] = loop
         result['metric_stage_loop_img_per_s'] = summary(loop)
         result['metric_stage_logs_equal'] = same
+    if 'json' in sections:
+        result['json_loop'] = json_loop(net, cfg, pipes['b8_d2'], loader, args)
     for p in pipes.values():
         p.drain()
     del pipes
@@ -207,6 +329,8 @@ def main():
         return out
     if 'metrics' in sections:
         result['metric_stage_8_images_ms'] = metric_stage(ragged(True), sizes8, gts, cfg, nc, dev, args)
+    if 'json' in sections:
+        result['json_stage_8_images_ms'] = json_stage(ragged(True), args)
     if 'after_nms' not in sections:
         print(json.dumps(result))
         return

@@ -82,18 +82,17 @@ __device__ __forceinline__ unsigned long long block_transitions(unsigned long lo
     return t;
 }
 
-template <class Src>
-__global__ __launch_bounds__(NT) void k_rle_encode(const void* __restrict__ masks, int H, int W, uint32_t* __restrict__ pos_ws,
-                                                   uint32_t* __restrict__ counts, int cap, int32_t* __restrict__ nruns,
-                                                   uint8_t* __restrict__ str, int cap_str, int32_t* __restrict__ str_len) {
+// One mask by one workgroup of NT threads (every thread calls it): maskApi.c rleEncode + rleToString.  `pos` [cap] receives the
+// positions of the transitions, `out` [cap_str] the string.  Returns the number of runs R; *len = the string's bytes, or -1 when
+// R > cap or the string is longer than cap_str ("buffers too small": nothing is written past either).  Both values are uniform.
+// kCounts: the run lengths are also an OUTPUT (`cnt` [cap], ym_rle_encode's `counts`) and the string reads them back; without it
+// `cnt` is unused and a count is the difference of two positions (cnt[j] - cnt[j-2] follows from four).
+template <class Src, bool kCounts>
+__device__ __forceinline__ int rle_encode_mask(const Src& m, int H, int W, uint32_t* __restrict__ pos, uint32_t* __restrict__ cnt, int cap,
+                                               uint8_t* __restrict__ out, int cap_str, int* s_col /*[MAXW]*/, int* s_wave /*[NT/64 + 1]*/,
+                                               int* len_out) {
     typedef typename Src::T Px;
-    __shared__ int s_col[MAXW];
-    __shared__ int s_wave[NT / 64 + 1];
     const int tid = threadIdx.x;
-    const Src m(masks, blockIdx.x, H, W);
-    uint32_t* pos = pos_ws + (size_t)blockIdx.x * cap;
-    uint32_t* cnt = counts + (size_t)blockIdx.x * cap;
-    uint8_t* out = str + (size_t)blockIdx.x * cap_str;
     const unsigned P = (unsigned)H * (unsigned)W;
 
     // pass 1: transitions per column (the pixel before (0, x) in column-major order is (H-1, x-1); before (0,0): background)
@@ -145,10 +144,9 @@ __global__ __launch_bounds__(NT) void k_rle_encode(const void* __restrict__ mask
     }
     const int T = carry;                 // transitions; runs = T + 1 (the last run ends at P)
     const int R = T + 1;
-    if (tid == 0) nruns[blockIdx.x] = R;
     if (R > cap) {                       // caller's buffers are too small: report the size needed, encode nothing
-        if (tid == 0) str_len[blockIdx.x] = -1;
-        return;
+        *len_out = -1;
+        return R;
     }
     // pass 2: positions of the transitions, in column-major order
     if constexpr (Src::kBits) {
@@ -191,12 +189,12 @@ __global__ __launch_bounds__(NT) void k_rle_encode(const void* __restrict__ mask
     __threadfence_block();
     __syncthreads();
     // counts[j] = pos[j] - pos[j-1]  (pos[-1] = 0, pos[T] = P)
-    for (int j = tid; j < R; j += NT) {
-        const unsigned hi = j < T ? pos[j] : P, lo = j > 0 ? pos[j - 1] : 0u;
-        cnt[j] = hi - lo;
+    const auto count_at = [&](int j) -> unsigned { return (j < T ? pos[j] : P) - (j > 0 ? pos[j - 1] : 0u); };
+    if constexpr (kCounts) {
+        for (int j = tid; j < R; j += NT) cnt[j] = count_at(j);
+        __threadfence_block();
+        __syncthreads();
     }
-    __threadfence_block();
-    __syncthreads();
     // rleToString: x = cnts[j] (j > 2: minus cnts[j-2]); 5 bits per char, bit 5 = "more", sign-aware termination, +48
     int scarry = 0;
     for (int j0 = 0; j0 < R; j0 += NT) {
@@ -205,8 +203,13 @@ __global__ __launch_bounds__(NT) void k_rle_encode(const void* __restrict__ mask
         int len = 0;
         uint8_t ch[8];
         if (j < R) {
-            x = (long long)cnt[j];
-            if (j > 2) x -= (long long)cnt[j - 2];
+            if constexpr (kCounts) {
+                x = (long long)cnt[j];
+                if (j > 2) x -= (long long)cnt[j - 2];
+            } else {
+                x = (long long)count_at(j);
+                if (j > 2) x -= (long long)count_at(j - 2);
+            }
             bool more = true;
             while (more) {
                 int c = (int)(x & 0x1f);
@@ -224,7 +227,102 @@ __global__ __launch_bounds__(NT) void k_rle_encode(const void* __restrict__ mask
         scarry += total;
         __syncthreads();
     }
-    if (tid == 0) str_len[blockIdx.x] = scarry <= cap_str ? scarry : -1;
+    *len_out = scarry <= cap_str ? scarry : -1;
+    return R;
+}
+
+template <class Src>
+__global__ __launch_bounds__(NT) void k_rle_encode(const void* __restrict__ masks, int H, int W, uint32_t* __restrict__ pos_ws,
+                                                   uint32_t* __restrict__ counts, int cap, int32_t* __restrict__ nruns,
+                                                   uint8_t* __restrict__ str, int cap_str, int32_t* __restrict__ str_len) {
+    __shared__ int s_col[MAXW];
+    __shared__ int s_wave[NT / 64 + 1];
+    const Src m(masks, blockIdx.x, H, W);
+    int len;
+    const int R = rle_encode_mask<Src, true>(m, H, W, pos_ws + (size_t)blockIdx.x * cap, counts + (size_t)blockIdx.x * cap, cap,
+                                             str + (size_t)blockIdx.x * cap_str, cap_str, s_col, s_wave, &len);
+    if (threadIdx.x == 0) {
+        nruns[blockIdx.x] = R;
+        str_len[blockIdx.x] = len;
+    }
+}
+
+// ---- the detection rows of a whole request (include/yolact_hip.h "ym_rle_encode_ragged_packed") -------------------------------------
+// What the encode launch knows about its images, BY VALUE in the kernel arguments (like CocoRaggedTable of coco_eval.hip).
+struct RleRaggedTable {
+    int img_h[YM_RAGGED_MAX_IMAGES], img_w[YM_RAGGED_MAX_IMAGES];
+    long long off[YM_RAGGED_MAX_IMAGES];         // words from det_bits to the image's block
+    unsigned live;                               // bit b: image b is no padding
+};
+
+constexpr int RLE_SLAB_PER_RUN = 4;              // bytes of a mask's string slab per run of cap_runs (rle_encode's cap_str)
+constexpr int GATHER_THREADS = 256;
+
+// grid: B * max_det, workgroup g = row g % max_det of image g / max_det.  A row that is no record writes state 0 and leaves before the
+// first barrier without touching its mask words; a record's string goes to its slab, its length and run count to the record.
+__global__ __launch_bounds__(NT) void k_rle_encode_ragged(const long long* __restrict__ ids, const float* __restrict__ scores,
+                                                          const int* __restrict__ boxes_px, const int* __restrict__ counts, int max_det,
+                                                          const unsigned long long* __restrict__ det_bits, const RleRaggedTable t, int cap,
+                                                          uint32_t* __restrict__ pos_ws, uint8_t* __restrict__ slabs,
+                                                          ym_rle_record* __restrict__ records) {
+    __shared__ int s_col[MAXW];
+    __shared__ int s_wave[NT / 64 + 1];
+    const int g = blockIdx.x, b = g / max_det, r = g - b * max_det;
+    ym_rle_record rec = {};
+    bool is_record = ((t.live >> b) & 1u) != 0 && r < counts[b];
+    if (is_record) {
+        const int* pb = boxes_px + (size_t)g * 4;
+        rec.class_id = (int32_t)ids[g];
+        rec.score = scores[g];
+        for (int k = 0; k < 4; ++k) rec.box[k] = pb[k];
+        is_record = ((long long)pb[3] - pb[1]) * ((long long)pb[2] - pb[0]) > 0;     // eval.py:65
+    }
+    if (!is_record) {                                        // (uniform: a function of the block index and of counts[b] alone)
+        if (threadIdx.x == 0) records[g] = ym_rle_record{};
+        return;
+    }
+    const int H = t.img_h[b], W = t.img_w[b];
+    const BitSrc m(det_bits + t.off[b], r, H, W);
+    const int cap_str = cap * RLE_SLAB_PER_RUN;
+    int len;
+    rec.nruns = rle_encode_mask<BitSrc, false>(m, H, W, pos_ws + (size_t)g * cap, nullptr, cap, slabs + (size_t)g * cap_str, cap_str, s_col,
+                                               s_wave, &len);
+    rec.state = len >= 0 ? 1 : 2;
+    rec.str_len = len >= 0 ? len : 0;
+    if (threadIdx.x == 0) records[g] = rec;
+}
+
+// one workgroup: str_off = the exclusive sum of str_len over the rows in (image, row) order, and the header.  Integer sums in a
+// fixed order: the layout is a function of the lengths alone.
+__global__ __launch_bounds__(NT) void k_rle_scan_records(ym_rle_record* __restrict__ records, int rows, int32_t* __restrict__ header) {
+    __shared__ int s_wave[NT / 64 + 1];
+    int bytes = 0, recs = 0, over = 0;
+    for (int r0 = 0; r0 < rows; r0 += NT) {
+        const int i = r0 + threadIdx.x;
+        const int state = i < rows ? records[i].state : 0;
+        const int len = state == 1 ? records[i].str_len : 0;
+        int total;
+        const int pre = block_exscan(len, &total, s_wave);
+        if (i < rows) records[i].str_off = bytes + pre;
+        bytes += total;
+        block_exscan(state != 0, &total, s_wave);
+        recs += total;
+        block_exscan(state == 2, &total, s_wave);
+        over += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { header[0] = bytes; header[1] = recs; header[2] = over; header[3] = 0; }
+}
+
+// grid: B * max_det.  The string of an encoded row moves from its slab to its place in the request's compact buffer.
+__global__ __launch_bounds__(GATHER_THREADS) void k_rle_gather_strings(const ym_rle_record* __restrict__ records,
+                                                                       const uint8_t* __restrict__ slabs, int slab,
+                                                                       uint8_t* __restrict__ strings, long long strings_bytes) {
+    const ym_rle_record rec = records[blockIdx.x];
+    if (rec.state != 1 || rec.str_len > slab || (long long)rec.str_off + rec.str_len > strings_bytes) return;
+    const uint8_t* src = slabs + (size_t)blockIdx.x * slab;
+    uint8_t* dst = strings + rec.str_off;
+    for (int k = threadIdx.x; k < rec.str_len; k += GATHER_THREADS) dst[k] = src[k];
 }
 
 }  // namespace
@@ -251,4 +349,77 @@ extern "C" int ym_rle_encode_packed(const uint64_t* bits, int n, int H, int W, u
                                     int cap_str, int32_t* str_len, void* workspace, size_t workspace_bytes, ym_stream_t s) {
     return rle_encode_launch<BitSrc>("rle_encode_packed", bits, n, H, W, counts, cap_runs, nruns, str, cap_str, str_len, workspace,
                                      workspace_bytes, s);
+}
+
+// ---- ym_rle_encode_ragged_packed: validation and layout are host code that runs before the first HIP call ------------------------------
+// The checks of the sizes, shared with the workspace query.  Workspace: positions [rows][cap_runs] uint32, then the string slabs
+// [rows][slab = 4 * cap_runs] bytes; rows = B * max_det.
+static int rle_ragged_check(const char* what, const ym_ragged_image* det_blocks, int B, int max_det, int cap_runs, size_t* rows,
+                            size_t* slab) {
+    YM_REQUIRE(B >= 1 && B <= YM_RAGGED_MAX_IMAGES, "%s: 1 .. %d images per call, got %d", what, YM_RAGGED_MAX_IMAGES, B);
+    YM_REQUIRE(max_det >= 1 && cap_runs >= 1, "%s: need max_det >= 1 and cap_runs >= 1, got %d and %d", what, max_det, cap_runs);
+    YM_REQUIRE(det_blocks, "%s: null image table", what);
+    for (int b = 0; b < B; ++b) {
+        const ym_ragged_image& im = det_blocks[b];
+        YM_REQUIRE(im.img_h > 0 && im.img_w > 0 && im.img_w <= MAXW, "%s: image %d is %d x %d, need 0 < W <= %d", what, b, im.img_h, im.img_w,
+                   MAXW);
+        YM_REQUIRE((long long)im.img_h * im.img_w < (1ll << 31), "%s: image %d: mask too large", what, b);
+    }
+    // (a reader of whole words: the offsets count words, so every block is 8-byte aligned when det_bits is -- esz = the alignment
+    //  unit makes the shared check's 256-byte rule, which the writers need, vacuous; sizes, offsets >= 0 and overlaps are checked)
+    const int rc = ym_check_ragged_table(what, det_blocks, B, YM_RAGGED_ALIGN_BYTES, [&](const ym_ragged_image& im) {
+        return (int64_t)max_det * im.img_h * (int64_t)ym_mask_row(true, im.img_w);
+    });
+    if (rc != YM_OK) return rc;
+    const long long n = (long long)B * max_det, sl = (long long)cap_runs * RLE_SLAB_PER_RUN;
+    YM_REQUIRE(n * sl < (1ll << 31), "%s: B * max_det * slab = %d * %d * %lld bytes: need < 2^31", what, B, max_det, sl);
+    *rows = (size_t)n;
+    *slab = (size_t)sl;
+    return YM_OK;
+}
+
+extern "C" size_t ym_sizeof_rle_record(void) { return sizeof(ym_rle_record); }
+
+extern "C" size_t ym_rle_encode_ragged_workspace_bytes(const ym_ragged_image* det_blocks, int B, int max_det, int cap_runs) {
+    size_t rows = 0, slab = 0;
+    if (rle_ragged_check("rle_encode_ragged_workspace_bytes", det_blocks, B, max_det, cap_runs, &rows, &slab) != YM_OK) return 0;
+    return rows * (size_t)cap_runs * sizeof(uint32_t) + rows * slab;
+}
+
+extern "C" int ym_rle_encode_ragged_packed(const int64_t* ids, const float* scores, const int32_t* boxes_px, const int32_t* counts, int B,
+                                           int max_det, const uint64_t* det_bits, const ym_ragged_image* det_blocks, const uint8_t* live,
+                                           int cap_runs, ym_rle_record* records, uint8_t* strings, int64_t strings_bytes, int32_t* header,
+                                           void* workspace, size_t workspace_bytes, ym_stream_t s) {
+    const char* what = "rle_encode_ragged_packed";
+    static_assert(sizeof(ym_rle_record) == 40, "ym_rle_record is 40 bytes");
+    YM_REQUIRE(ids && scores && boxes_px && counts && det_bits && det_blocks && live && records && strings && header && workspace,
+               "%s: null pointer", what);
+    YM_REQUIRE(((uintptr_t)det_bits & 7) == 0 && ((uintptr_t)records & 3) == 0 && ((uintptr_t)header & 3) == 0 && ((uintptr_t)workspace & 3) == 0,
+               "%s: det_bits must be 8-byte aligned; records, header and workspace 4-byte aligned", what);
+    size_t rows = 0, slab = 0;
+    const int rc = rle_ragged_check(what, det_blocks, B, max_det, cap_runs, &rows, &slab);
+    if (rc != YM_OK) return rc;
+    const size_t need = rows * (size_t)cap_runs * sizeof(uint32_t) + rows * slab;
+    if (workspace_bytes < need) { ym_set_error("%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, need); return YM_ENOSPC; }
+    if (strings_bytes < (int64_t)(rows * slab)) {
+        ym_set_error("%s: strings of %lld bytes, the worst case B * max_det * 4 * cap_runs = %zu is needed", what, (long long)strings_bytes,
+                     rows * slab);
+        return YM_ENOSPC;
+    }
+    RleRaggedTable t = {};
+    for (int b = 0; b < B; ++b) {
+        t.img_h[b] = det_blocks[b].img_h;
+        t.img_w[b] = det_blocks[b].img_w;
+        t.off[b] = det_blocks[b].offset;
+        if (live[b]) t.live |= 1u << b;
+    }
+    hipStream_t st = (hipStream_t)s;
+    uint32_t* pos_ws = (uint32_t*)workspace;
+    uint8_t* slabs = (uint8_t*)(pos_ws + rows * (size_t)cap_runs);
+    hipLaunchKernelGGL(k_rle_encode_ragged, dim3((unsigned)rows), dim3(NT), 0, st, reinterpret_cast<const long long*>(ids), scores, boxes_px,
+                       counts, max_det, reinterpret_cast<const unsigned long long*>(det_bits), t, cap_runs, pos_ws, slabs, records);
+    hipLaunchKernelGGL(k_rle_scan_records, dim3(1), dim3(NT), 0, st, records, (int)rows, header);
+    hipLaunchKernelGGL(k_rle_gather_strings, dim3((unsigned)rows), dim3(GATHER_THREADS), 0, st, records, slabs, (int)slab, strings,
+                       (long long)strings_bytes);
+    return ym_check_launch(what);
 }

@@ -7,7 +7,8 @@ is `DeviceAPData.add(..., image_index=i)` on that same stream: nothing of an ima
 sample order whatever order the slots finish in.  The one download is `calc_map`'s AP grid at the end.  Requests of several images
 (`batch` > 1) add image by image by default, or with `batched_metrics=True` through one `DeviceAPData.add_batch` per request.
 `evaluate_coco_pipelined` runs the same requests into `utils/coco_eval.DeviceCOCOeval` (the COCO protocol's twelve numbers), image by
-image or through one `DeviceCOCOeval.add_batch` per request.
+image or through one `DeviceCOCOeval.add_batch` per request, and `evaluate_json_pipelined` into the detection dumps
+(`utils/common_utils.BatchMakeJson`, one `add_batch` per request).
 """
 import torch
 
@@ -180,3 +181,46 @@ def evaluate_coco_pipelined(net, cfg, samples, coco, image_ids, depth=4, packed_
     if pipe is not None:
         pipe.drain()
     return ev.summarize(), ev
+
+
+def evaluate_json_pipelined(net, cfg, samples, image_ids, depth=4, pipe=None, batch=1, make_json=None):
+    """`evaluate_pipelined`'s requests dumped for the COCO API (`eval.py --coco_api`'s `bbox_detections.json` /
+    `mask_detections.json`): sample i is image `image_ids[i]`, and the metric stage of a request is ONE
+    `utils/common_utils.BatchMakeJson.add_batch` on the slot's stream -- no host read; the records of a request are fetched when a
+    later request finds its event completed, the rest by `dump`.  Packed masks only (a `pipe` with dense masks raises before anything
+    runs).  A short last request is padded with copies of its last image, which yield no record.  With `batch` = 1 a request is the
+    uniform entry's batch of one.  `pipe`, `depth`, `batch`: as for `evaluate_pipelined`; `make_json`: a `BatchMakeJson` to add to.
+    Returns the `BatchMakeJson` (`dump(bbox_path, mask_path)` writes the files; `dropin/reference_loops.coco_summary` scores it)."""
+    from .utils.common_utils import BatchMakeJson
+    device = next(net.parameters()).device
+    if pipe is not None:
+        batch = pipe.batch
+        if not pipe.packed_masks:
+            raise RuntimeError('evaluate_json_pipelined: the pipeline must produce packed masks (BatchMakeJson.add_batch is packed-only)')
+    dumps = BatchMakeJson() if make_json is None else make_json
+    if not isinstance(dumps, BatchMakeJson):
+        raise RuntimeError('evaluate_json_pipelined: make_json is a BatchMakeJson')
+    image_ids = list(image_ids)
+
+    def items():
+        for i, (img, _, _, img_h, img_w) in enumerate(samples):
+            yield img.to(device), (), image_ids[i], img_h, img_w
+
+    def metric_stage(first, real, payloads, sizes, ids, scores, boxes_px, masks, counts):
+        dumps.add_batch(ids, scores, boxes_px, masks, counts, [p if b < real else None for b, p in enumerate(payloads)])
+
+    if batch > 1:
+        pipe = _submit_groups(net, cfg, items(), device, batch, depth, True, pipe, metric_stage)
+    else:                                                       # (requests of one image: the uniform entry's batch of one)
+        for img, _, img_id, img_h, img_w in items():
+            if pipe is None:
+                pipe = eval_pipeline(net, cfg, img, img_h, img_w, depth, True)
+
+            def consume(ids, scores, boxes_px, masks, counts, img=img, img_id=img_id):
+                img.record_stream(torch.cuda.current_stream(device))
+                dumps.add_batch(ids, scores, boxes_px, masks, counts, [img_id])
+
+            pipe.submit(img, out_hw=(img_h, img_w), consumer=consume)
+    if pipe is not None:
+        pipe.drain()
+    return dumps

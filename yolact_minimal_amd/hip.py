@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     'ym_mask_loss_batch_window', 'ym_mask_loss_fwd_bwd_window', 'ym_train_aug_image_batch_window', 'ym_train_aug_masks_batch_window',
     'ym_pack_masks_ragged', 'ym_eval_add_ragged_workspace_bytes', 'ym_eval_add_ragged_packed',
     'ym_eval_coco_add_ragged_workspace_bytes', 'ym_eval_coco_add_ragged_packed',
+    'ym_sizeof_rle_record', 'ym_rle_encode_ragged_workspace_bytes', 'ym_rle_encode_ragged_packed',
 )
 
 
@@ -134,6 +135,16 @@ class RaggedImage(ctypes.Structure):
     of `ym_val_preprocess_batch` / `ym_draw_detections_ragged` (frame size, first element of the frame in the frame buffer)."""
     _fields_ = [('img_h', ctypes.c_int32), ('img_w', ctypes.c_int32), ('offset', ctypes.c_int64)]
 
+
+class RleRecord(ctypes.Structure):
+    """ym_rle_record: one detection row of `ym_rle_encode_ragged_packed` (40 bytes).  `RLE_RECORD_DTYPE` is the same layout for numpy."""
+    _fields_ = [('class_id', ctypes.c_int32), ('score', ctypes.c_float), ('box', ctypes.c_int32 * 4), ('str_off', ctypes.c_int32),
+                ('str_len', ctypes.c_int32), ('nruns', ctypes.c_int32), ('state', ctypes.c_int32)]
+
+
+RLE_RECORD_DTYPE = [('class_id', '<i4'), ('score', '<f4'), ('box', '<i4', (4,)), ('str_off', '<i4'), ('str_len', '<i4'),
+                    ('nruns', '<i4'), ('state', '<i4')]
+RLE_SLAB_PER_RUN = 4            # bytes of a mask's string slab per run of cap_runs (ym_rle_encode_ragged_packed)
 
 RAGGED_MAX_IMAGES = 32          # YM_RAGGED_MAX_IMAGES
 RAGGED_ALIGN_BYTES = 256        # YM_RAGGED_ALIGN_BYTES
@@ -347,6 +358,12 @@ def lib():
                                                      ctypes.POINTER(ctypes.c_int32), vp, ctypes.POINTER(RaggedImage),
                                                      ctypes.POINTER(ctypes.c_int64), vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp,
                                                      vp, vp, sz, vp]
+        L.ym_sizeof_rle_record.argtypes = []
+        L.ym_sizeof_rle_record.restype = sz
+        L.ym_rle_encode_ragged_workspace_bytes.argtypes = [ctypes.POINTER(RaggedImage), i32, i32, i32]
+        L.ym_rle_encode_ragged_workspace_bytes.restype = sz
+        L.ym_rle_encode_ragged_packed.argtypes = [vp, vp, vp, vp, i32, i32, vp, ctypes.POINTER(RaggedImage), ctypes.POINTER(ctypes.c_uint8), i32,
+                                                  vp, vp, i64, vp, vp, sz, vp]
         for name in ABI_SYMBOLS:
             fn = getattr(L, name)
             if name not in ('ym_last_error', 'ym_conv2d_workspace_bytes', 'ym_nms_workspace_bytes',
@@ -356,7 +373,8 @@ def lib():
                             'ym_unordered_sum_launches', 'ym_bn_train_fwd_workspace_bytes', 'ym_greedy_nms_batch_workspace_bytes',
                             'ym_eval_ap_workspace_bytes', 'ym_coco_accumulate_workspace_bytes',
                             'ym_ann_to_mask_ragged_workspace_bytes', 'ym_after_nms_window_workspace_bytes',
-                            'ym_eval_add_ragged_workspace_bytes', 'ym_eval_coco_add_ragged_workspace_bytes'):
+                            'ym_eval_add_ragged_workspace_bytes', 'ym_eval_coco_add_ragged_workspace_bytes',
+                            'ym_sizeof_rle_record', 'ym_rle_encode_ragged_workspace_bytes'):
                 fn.restype = ctypes.c_int
         _lib = L
     return _lib

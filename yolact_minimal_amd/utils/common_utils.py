@@ -217,6 +217,212 @@ class MakeJson:
                 json.dump(data, f)
 
 
+class _JsonRequest:
+    """One request of `BatchMakeJson`: where it stands among the records added one by one, and its numpy blocks once collected.
+    While its launches may still run it is also the token that keeps the mask allocation and its transfer block alive."""
+    __slots__ = ('bbox_at', 'mask_at', 'image_ids', 'sizes', 'records', 'blob', 'redone', 'event', 'block', 'masks', 'offsets',
+                 'cap_runs', 'device')
+
+
+class _JsonBlock:
+    """The buffers of one request in flight: header + records on the device and their pinned host copy (one fixed-size D2H), the
+    compact string buffer, the event behind the copy.  Taken from and given back to `BatchMakeJson`'s free list."""
+    __slots__ = ('key', 'out', 'host', 'strings', 'event')
+
+
+class BatchMakeJson(MakeJson):
+    """`MakeJson` as a pipeline consumer: `add_batch` takes the `after_nms_batch(..., sync=False, packed=True)` rows of a request of
+    B <= 32 images of different sizes (`ym_rle_encode_ragged_packed`: at most three launches) and reads nothing on the host; the
+    records of a request are fetched once its event has completed (by a later `add_batch`, or by `dump`), and the per-detection
+    dicts are built by `dump` alone: in request order, inside a request in (image, row) order, under eval.py:65's filter -- the files
+    are byte for byte those of `rle_encode` -> `add_bbox` / `add_mask` image by image.  Records added through `add_bbox` /
+    `add_mask` keep their position between the requests."""
+
+    def __init__(self, coco_label_map=None):
+        super().__init__(coco_label_map)
+        self._requests = []                                 # in add order, until `finish` folds them into bbox_data / mask_data
+        self._tokens = []                                   # the requests whose launches may still run
+        self._free = {}                                     # (device, B, max_det, cap_runs) -> [_JsonBlock]
+        self._side = {}                                     # device -> the stream the collected strings are copied on
+
+    # ---- the request --------------------------------------------------------------------------------------------------------
+    def add_batch(self, ids, scores, boxes_px, masks, counts, image_ids, mask_table=None, cap_runs=4096):
+        """ids / scores `[B, max_det]`, boxes_px int32 `[B, max_det, 4]`, counts int32 `[B]`; `masks`: the list of B `PackedMasks`
+        views of the ragged `after_nms_batch`, view 0 with `mask_table` (their `hip.ragged_table`), or the uniform padded
+        `PackedMasks [B, max_det, H, Wq]`; dense masks raise.  `image_ids`: one per image, `None` = the entry is padding.  Runs on
+        the current stream, no host read: the launches, one asynchronous D2H of header + records into a pinned block of the free
+        list, an event.  A mask of more than `cap_runs` runs is encoded again by `rle_encode` when the request is collected."""
+        from .draw import _ragged_mask_table
+        from .output_utils import _scratch
+        what = 'BatchMakeJson.add_batch'
+        if not torch.is_tensor(ids) or not ids.is_cuda or ids.dim() != 2:
+            raise RuntimeError(f'{what}: ids [B, max_det] as a CUDA (HIP) tensor expected; there is no CPU path')
+        batch, md = ids.shape
+        if tuple(scores.shape) != (batch, md) or boxes_px is None or tuple(boxes_px.shape) != (batch, md, 4) or counts is None or \
+                counts.numel() != batch or len(image_ids) != batch:
+            raise RuntimeError(f'{what}: ids / scores [{batch}, {md}], boxes_px [{batch}, {md}, 4], {batch} counts and {batch} image ids '
+                               f'expected, got {tuple(scores.shape)} / {None if boxes_px is None else tuple(boxes_px.shape)} / '
+                               f'{None if counts is None else counts.numel()} / {len(image_ids)}')
+        packed_only = f'{what}: the batched stages take packed masks only (after_nms_batch(..., packed=True))'
+        if mask_table is not None:
+            if not isinstance(masks, PackedMasks) or len(mask_table) != batch:
+                raise RuntimeError(packed_only + f'; with mask_table: view 0 and {batch} table entries')
+            sizes = [(e.img_h, e.img_w) for e in mask_table]
+            offsets = [e.offset for e in mask_table]
+        elif isinstance(masks, (list, tuple)):
+            if not len(masks) or not isinstance(masks[0], PackedMasks):
+                raise RuntimeError(packed_only)
+            sizes = [(m.height, m.width) for m in masks]
+            masks, mask_table = _ragged_mask_table(masks, sizes, md, what)
+            offsets = [e.offset for e in mask_table]
+        elif isinstance(masks, PackedMasks):                    # the uniform padded form: B blocks of one size back to back
+            h, w = masks.height, masks.width
+            if masks.dim() != 4 or masks.shape != (batch, md, h, w) or not masks.bits.is_contiguous():
+                raise RuntimeError(f'{what}: uniform masks are a contiguous PackedMasks [{batch}, {md}, H, Wq], got {masks.shape}')
+            sizes = [(h, w)] * batch
+            offsets = [b * md * h * masks.bits.shape[3] for b in range(batch)]
+            mask_table = hip.ragged_table(sizes, offsets)
+        else:
+            raise RuntimeError(packed_only)
+        dev = ids.device
+        if masks.bits.device != dev:
+            raise RuntimeError(f'{what}: masks on {masks.bits.device}, detections on {dev}')
+        self._collect_done()
+        L = hip.lib()
+        with torch.cuda.device(dev):
+            nbytes = L.ym_rle_encode_ragged_workspace_bytes(mask_table, batch, md, int(cap_runs))
+            if nbytes == 0:
+                raise RuntimeError(f'{what}: ym_rle_encode_ragged_workspace_bytes refuses {batch} images of {sizes} with max_det {md} and '
+                                   f'cap_runs {cap_runs} (width <= 4096, h * w < 2^31, B * max_det * 4 * cap_runs < 2^31)')
+            blk = self._take_block(dev, batch, md, int(cap_runs))
+            ws = _scratch(dev, nbytes)
+            live = (ctypes.c_uint8 * batch)(*[i is not None for i in image_ids])
+            hip.check(L.ym_rle_encode_ragged_packed(
+                hip.ptr(ids.contiguous(), torch.int64), hip.ptr(scores.contiguous()), hip.ptr(boxes_px.contiguous(), torch.int32),
+                hip.ptr(counts.contiguous(), torch.int32), batch, md, hip.ptr(masks.bits, torch.int64), mask_table, live, int(cap_runs),
+                ctypes.c_void_p(blk.out.data_ptr() + 16), ctypes.c_void_p(blk.strings.data_ptr()), blk.strings.numel(),
+                ctypes.c_void_p(blk.out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), hip.stream_ptr()),
+                'ym_rle_encode_ragged_packed')
+            blk.host.copy_(blk.out, non_blocking=True)
+            blk.event.record()
+        req = self._new_request(image_ids, sizes)
+        req.event, req.block, req.masks, req.offsets, req.cap_runs, req.device = blk.event, blk, masks, offsets, int(cap_runs), dev
+        self._tokens.append(req)
+
+    def add_records(self, records, strings, image_ids, sizes):
+        """A request that is already on the host: `records` `[B, max_det]` of `hip.RLE_RECORD_DTYPE` (state 0 or 1), `strings` the
+        bytes their str_off / str_len index, one image id (`None` = padding) and one (h, w) per image."""
+        records = np.asarray(records, dtype=np.dtype(hip.RLE_RECORD_DTYPE))
+        if records.ndim != 2 or records.shape[0] != len(image_ids) or len(sizes) != len(image_ids) or (records['state'] == 2).any():
+            raise RuntimeError(f'BatchMakeJson.add_records: records [B, max_det] of state 0 / 1 with B image ids and B sizes expected, got '
+                               f'{records.shape} for {len(image_ids)} ids and {len(sizes)} sizes')
+        req = self._new_request(image_ids, sizes)
+        req.records, req.blob = records.copy(), np.frombuffer(bytes(strings), dtype=np.uint8)
+
+    def _new_request(self, image_ids, sizes):
+        req = _JsonRequest()
+        req.bbox_at, req.mask_at = len(self.bbox_data), len(self.mask_data)
+        req.image_ids, req.sizes = list(image_ids), [(int(h), int(w)) for h, w in sizes]
+        req.records = req.blob = req.event = req.block = req.masks = req.offsets = None
+        req.redone = {}
+        self._requests.append(req)
+        return req
+
+    def _take_block(self, dev, batch, md, cap_runs):
+        key = (str(dev), batch, md, cap_runs)
+        free = self._free.setdefault(key, [])
+        if free:
+            return free.pop()
+        blk = _JsonBlock()
+        rows = batch * md
+        nbytes = 16 + rows * ctypes.sizeof(hip.RleRecord)
+        blk.key = key
+        blk.out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        blk.host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        blk.strings = torch.empty(rows * cap_runs * hip.RLE_SLAB_PER_RUN, dtype=torch.uint8, device=dev)
+        blk.event = torch.cuda.Event()
+        return blk
+
+    # ---- collecting ---------------------------------------------------------------------------------------------------------
+    def _collect_done(self):
+        """Every queued request whose event has completed; never waits for one that has not."""
+        waiting = []
+        for req in self._tokens:
+            if req.event.query():
+                self._collect(req)
+            else:
+                waiting.append(req)
+        self._tokens = waiting
+
+    def _collect(self, req):
+        """The finished request as numpy blocks: the record array, exactly header[0] string bytes, and the strings of the rows that
+        did not fit (`rle_encode` on the held mask view).  The copies run on a stream of their own: the caller's current stream
+        may hold a forward pass that has only just been queued."""
+        blk, dev = req.block, req.device
+        host = blk.host.numpy()
+        total = int(host[:16].view('<i4')[0])
+        batch = len(req.image_ids)
+        req.records = host[16:].view(np.dtype(hip.RLE_RECORD_DTYPE)).reshape(batch, -1).copy()
+        side = self._side.get(str(dev))
+        if side is None:
+            side = self._side[str(dev)] = torch.cuda.Stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(side):
+            req.blob = blk.strings[:total].cpu().numpy() if total else np.zeros(0, dtype=np.uint8)
+            over = np.argwhere(req.records['state'] == 2)
+            if len(over):
+                req.masks.record_stream(side)                   # (allocated on the request's stream, read here)
+                base = req.masks.bits
+                for b, r in over.tolist():
+                    h, w = req.sizes[b]
+                    wq = (w + 63) // 64
+                    row = base.as_strided((1, h, wq), (h * wq, wq, 1), base.storage_offset() + req.offsets[b] + r * h * wq)
+                    need = int(req.records['nruns'][b, r])
+                    req.redone[(b, r)] = rle_encode(PackedMasks(row, h, w), cap_runs=max(2 * req.cap_runs, need + 1))[0]['counts']
+        self._free[blk.key].append(blk)
+        req.event = req.block = req.masks = None
+
+    def wait(self):
+        """Wait for the requests in flight and collect them.  Returns the requests not yet folded into the lists, in order, as
+        `(records [B, max_det], string bytes, image ids)` numpy blocks."""
+        for req in self._tokens:
+            req.event.synchronize()
+            self._collect(req)
+        self._tokens = []
+        return [(req.records, req.blob, req.image_ids) for req in self._requests]
+
+    def finish(self):
+        """Wait for the requests in flight, collect them, and fold every request into `bbox_data` / `mask_data` at its place."""
+        self.wait()
+        if not self._requests:
+            return
+        singles = (self.bbox_data, self.mask_data)
+        self.bbox_data, self.mask_data = [], []
+        at = [0, 0]
+        for req in self._requests:
+            self.bbox_data += singles[0][at[0]:req.bbox_at]
+            self.mask_data += singles[1][at[1]:req.mask_at]
+            at = [req.bbox_at, req.mask_at]
+            rec, blob = req.records, req.blob
+            for b, r in np.argwhere(rec['state'] != 0).tolist():
+                one = rec[b, r]
+                if req.image_ids[b] is None:                    # (padding: the device marks none of its rows)
+                    continue
+                if one['state'] == 1:
+                    counts = blob[one['str_off']:one['str_off'] + one['str_len']].tobytes().decode('ascii')
+                else:
+                    counts = req.redone[(b, r)]
+                h, w = req.sizes[b]
+                MakeJson.add_bbox(self, req.image_ids[b], one['class_id'], one['box'], one['score'])
+                MakeJson.add_mask(self, req.image_ids[b], one['class_id'], {'size': [h, w], 'counts': counts}, one['score'])
+        self.bbox_data += singles[0][at[0]:]
+        self.mask_data += singles[1][at[1]:]
+        self._requests = []
+
+    def dump(self, bbox_path='results/bbox_detections.json', mask_path='results/mask_detections.json'):
+        self.finish()
+        super().dump(bbox_path, mask_path)
+
+
 # ---- harness helpers the reference scripts import from this module (host only) -----------------------------------------
 class ProgressBar:
     """`ProgressBar(length, max_val).get_bar(i)` -> a `length`-character bar (reference common_utils.py:15-38; eval.py:32,81)."""
